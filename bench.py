@@ -13,7 +13,12 @@ launcher (WORLD_SIZE set).  Reads shard across ranks with no collective in the
 hot loop ("scaling": "weak"); rank 0 creates the weights and broadcasts them
 once over RCCL.
 
-Beside the headline ``value`` the line carries, on every run:
+A plain run sets up, warms up, times ``--steps`` calls and prints the headline
+(``value``, ``ms_per_step``, ...); ``--dump-outputs DIR`` also writes the last
+timed call's outputs as DIR/<name>.npy.  With ``--full`` the line carries,
+beside the headline:
+  pool_check    the timed calls' outputs against a fresh single engine, and
+                one_call_in_flight, the same calls one at a time;
   roofline      the dominant kernel against its HBM roofline (live in-kernel
                 timing) + the fused encoder FFN block against the MFMA peak;
   mfma          algorithmic MFMA utilisation, path-level and encoder-only,
@@ -100,7 +105,19 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"])
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="launcher/rank plumbing self-test on CPU (gloo, no engine, no measurement)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run every other leg (pool check, one call in flight, rooflines, MFMA "
+                         "view, exact fp32, host-inclusive, configs[2..4], CPU baseline), each still under its own "
+                         "switch above; without it only the headline is measured")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed call's outputs (what translate_greedy / "
+                         "translate_beam returned on rank 0) as DIR/<name>.npy in float32")
+    args = ap.parse_args()
+    if not args.full:
+        # a plain run measures the headline and nothing else
+        args.config_legs = args.read_shard = args.exact = args.host_inclusive = args.cpu_baseline = 0
+        args.no_roofline = True
+    return args
 
 
 # ----------------------------------------------------------------- launcher
@@ -133,7 +150,8 @@ def dist_setup(args):
             torch.distributed.init_process_group("nccl", device_id=torch.device("cuda", local))
         else:
             torch.distributed.init_process_group("gloo")
-    elif args.backend == "nccl" and args.read_shard and not args.selftest_cpu and torch.cuda.is_available():
+    elif (args.backend == "nccl" and (args.read_shard or args.workload == "reads") and not args.selftest_cpu
+          and torch.cuda.is_available()):
         # N = 1 without a launcher: a one-rank RCCL group, so the read-shard leg's weight broadcast (from HIP
         # memory) and its gloo control exchanges run as at N > 1 (shard.run_distributed)
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -302,6 +320,18 @@ def count_bases(tok: np.ndarray, eos: int) -> int:
     is_eos = tok == eos
     first = np.where(is_eos.any(1), is_eos.argmax(1), tok.shape[1])
     return int(((np.arange(tok.shape[1])[None, :] < first[:, None]) & (tok >= 4)).sum())
+
+
+def dump_outputs(path: str, out: dict) -> None:
+    """--dump-outputs: every array of one translate call's result dict
+    (tokens, scores; + lens, steps for beam) as ``path/<name>.npy`` in float32
+    (token ids and lengths are small integers, exact in float32).  Inputs and
+    weights are seeded, so two builds run with the same arguments can be
+    compared file by file."""
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        if isinstance(v, torch.Tensor):
+            np.save(os.path.join(path, name + ".npy"), v.detach().cpu().numpy().astype(np.float32))
 
 
 # ----------------------------------------------------------------- roofline
@@ -676,6 +706,8 @@ def run_batch(args, world, rank, dev, cfg, W):
     run_calls(eng, max(args.warmup, eng.lanes), call)  # every lane captures its graphs
     dt, outs = timed(eng, args.steps, call, world, every_lane=True)
     out = outs[(args.steps - 1) % eng.lanes]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     # bases = base tokens before the first EOS (outside the timed region)
     tok = out["tokens"].cpu().numpy()
     if args.mode == "beam":
@@ -697,8 +729,10 @@ def run_batch(args, world, rank, dev, cfg, W):
         "bases_per_sec": round(bases_per_step * args.steps * world / dt, 1),
         "timed_seconds": round(dt, 3),
         "min_length": args.min_length,
-        "pool_check": pool_check(cfg, W, args, args.mode, args.batch, beam, call, outs),
     }
+    if not args.full:
+        return res, eng, sig_np, lens_np
+    res["pool_check"] = pool_check(cfg, W, args, args.mode, args.batch, beam, call, outs)
     roof_iso = None
     greedy_roof = rank == 0 and not args.no_roofline and args.mode == "greedy"
     if eng.lanes > 1:

@@ -3,7 +3,7 @@ vals=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 for rep in 1 2; do
   for v in $vals; do
-    timeout -k 10 300 python -u bench.py --inflight $v --steps 40 --warmup 3 --cpu-baseline 0 --exact 0 --host-inclusive 0 \
+    timeout -k 10 300 python -u bench.py --full --inflight $v --steps 40 --warmup 3 --cpu-baseline 0 --exact 0 --host-inclusive 0 \
       --read-shard 0 --config-legs 0 "$@" > $O/abi_${v}_$rep.json 2> $O/abi_${v}_$rep.err || exit $?
     python3 -c "
 import json; d=json.loads(open('$O/abi_${v}_$rep.json').read().strip().splitlines()[-1])

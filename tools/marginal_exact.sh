@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-$(pwd)}; O=$R/gpurun_out; mkdir -p $O; cd $R
 for rep in 1 2; do
   for v in "$@"; do
-    NANODEC_AB=1 NANODEC_LIB=$R/tools/_ab/$v.so timeout -k 10 300 python -u bench.py --allow-switches --steps 80 --warmup 3 \
+    NANODEC_AB=1 NANODEC_LIB=$R/tools/_ab/$v.so timeout -k 10 300 python -u bench.py --full --allow-switches --steps 80 --warmup 3 \
       --cpu-baseline 0 --exact 1 --host-inclusive 0 --read-shard 0 --config-legs 0 --no-roofline \
       > $O/margx_${v}_$rep.json 2> $O/margx_${v}_$rep.err || exit $?
     python3 -c "

@@ -12,7 +12,7 @@ if [ "$part" = a ]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > gpurun_out/${t}_smoke.log 2>&1 || exit $?
   timeout -k 10 900 python -u -m pytest tests -q -m gpu --timeout 240 --timeout-method thread -p no:cacheprovider \
     > gpurun_out/${t}_gpu_tests.log 2>&1 || exit $?
-  timeout -k 10 600 python -u bench.py > gpurun_out/${t}_bench.json 2> gpurun_out/${t}_bench.err || exit $?
+  bash tools/gpu.sh bench ${t}_bench || exit $?  # the --full line
 else
   bash tools/prof_round.sh $t || exit $?
   ND_GEMM_F32=1 bash tools/gpu.sh prof ${t}_exact_one_call --inflight 1 --allow-switches || exit $?

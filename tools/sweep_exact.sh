@@ -6,7 +6,7 @@ for rep in 1 2; do
   i=0
   for a in "$@"; do
     i=$((i + 1))
-    timeout -k 10 300 python -u bench.py --steps 160 --warmup 3 --cpu-baseline 0 --exact 1 --host-inclusive 0 \
+    timeout -k 10 300 python -u bench.py --full --steps 160 --warmup 3 --cpu-baseline 0 --exact 1 --host-inclusive 0 \
       --read-shard 0 --config-legs 0 $a > $O/sweepx_${i}_$rep.json 2> $O/sweepx_${i}_$rep.err || exit $?
     python3 -c "
 import json; d=json.loads(open('$O/sweepx_${i}_$rep.json').read().strip().splitlines()[-1]); e=d['exact_fp32']

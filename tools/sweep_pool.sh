@@ -6,7 +6,7 @@ tag=$1; shift
 B="--config-legs 0 --steps 40 --warmup 5 --cpu-baseline 0 --exact 0 --host-inclusive 0 --read-shard 0 --no-roofline"
 i=0
 for a in "$@"; do
-  timeout -k 10 300 python -u bench.py $B $a > $O/${tag}_$i.json 2> $O/${tag}_$i.err || exit $?
+  timeout -k 10 300 python -u bench.py --full $B $a > $O/${tag}_$i.json 2> $O/${tag}_$i.err || exit $?
   python3 -c "import json,sys; d=json.loads(open('$O/${tag}_$i.json').read().strip().splitlines()[-1]); print('$a', '->', d['value'], d['ms_per_step'], d.get('pool_check',{}).get('result'))"
   i=$((i+1))
 done
