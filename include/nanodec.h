@@ -242,7 +242,7 @@ int nd_set_ctx_path(nd_ctx* ctx, int path);
  * an fp16 hi/lo pair, 22 significant bits, three fp16 MFMA products summed in
  * fp32 accumulators); 1 = exact fp32 (fp32-MFMA kernels for every GEMM, the
  * encoder attention and the BiLSTM recurrence), the reference's own fp32
- * arithmetic (nn.Linear / bmm in fp32).  Default from ND_GEMM_F32.  The
+ * arithmetic (nn.Linear / bmm in fp32).  Off when a context is created.  The
  * captured graphs of both forms are kept (keyed by it). */
 int nd_set_exact_fp32(nd_ctx* ctx, int enable);
 
@@ -475,7 +475,7 @@ int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* a
                                  int32_t max_steps, float* out, int32_t R, int32_t rpc, const int32_t* done,
                                  void* stream);
 
-/* Memory-bank context attention (greedy form, engine.hip
+/* Memory-bank context attention (greedy form, model.hip
  * derive_memory_bank_weights; replaces the context MultiHeadedAttention of
  * decoder/transformer.py:88-92 for one row per chunk, rpc == 1): row c of
  * qp = Q' [C, 8*256] (P16; column block h = head h's query mapped into

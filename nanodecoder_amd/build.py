@@ -63,9 +63,11 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
-# Host-side AddressSanitizer build of the C-ABI: engine.hip's host
-# code instrumented, device code not (GPU ASan is unavailable); linked with the
-# regular objects of the other kernels into tests/asan_driver.cpp's driver.
+# Host-side AddressSanitizer build of the C-ABI: the host code of
+# engine.hip, model.hip and ops_api.hip instrumented, device code not (GPU ASan
+# is unavailable); linked with the regular objects of the kernel files into
+# tests/asan_driver.cpp's driver.
+ASAN_HOST_SRCS = ("engine.hip", "model.hip", "ops_api.hip")
 ASAN_HOST = "-gline-tables-only -Xarch_host -fsanitize=address -Xarch_host -fno-omit-frame-pointer -fno-gpu-sanitize".split()
 ASAN_LINK = "-fsanitize=address -fno-gpu-sanitize".split()
 ASAN_BIN = os.path.join(HERE, "asan_driver")  # beside the .so: built files under _build/ stay home
@@ -75,21 +77,18 @@ ASAN_SRC = os.path.join(os.path.dirname(HERE), "tests", "asan_driver.cpp")
 def build_asan(verbose: bool = False) -> str:
     build(verbose=verbose)
     objs = [os.path.join(BUILD, os.path.basename(p)[:-4] + ".o") for p in sorted(glob.glob(os.path.join(CSRC, "*.hip")))
-            if os.path.basename(p) != "engine.hip"]
-    eng_src, eng_obj = os.path.join(CSRC, "engine.hip"), os.path.join(BUILD, "asan_engine.o")
+            if os.path.basename(p) not in ASAN_HOST_SRCS]
+    host = [(os.path.join(CSRC, n), os.path.join(BUILD, "asan_" + n[:-4] + ".o")) for n in ASAN_HOST_SRCS]
     drv_obj = os.path.join(BUILD, "asan_driver.o")
     dep_t = _newest_dep()
-    jobs = []
-    if not os.path.exists(eng_obj) or os.path.getmtime(eng_obj) < max(os.path.getmtime(eng_src), dep_t):
-        jobs.append((eng_src, eng_obj))
-    if not os.path.exists(drv_obj) or os.path.getmtime(drv_obj) < max(os.path.getmtime(ASAN_SRC), dep_t):
-        jobs.append((ASAN_SRC, drv_obj))
+    jobs = [(src, obj) for src, obj in host + [(ASAN_SRC, drv_obj)]
+            if not os.path.exists(obj) or os.path.getmtime(obj) < max(os.path.getmtime(src), dep_t)]
     for src, obj in jobs:
         cmd = [HIPCC] + CFLAGS + ASAN_HOST + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc (asan) failed for {os.path.basename(src)}:\n{r.stdout}\n{r.stderr}")
-    deps = [eng_obj, drv_obj] + objs
+    deps = [obj for _, obj in host] + [drv_obj] + objs
     if jobs or not os.path.exists(ASAN_BIN) or os.path.getmtime(ASAN_BIN) < max(os.path.getmtime(o) for o in deps):
         cmd = [HIPCC, f"--offload-arch={ARCH}"] + ASAN_LINK + ["-o", ASAN_BIN] + deps
         r = subprocess.run(cmd, capture_output=True, text=True)

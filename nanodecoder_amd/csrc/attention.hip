@@ -34,10 +34,9 @@ __device__ __forceinline__ void row_part(f32x4 v, int lane, float* part) {
   }
 }
 
-template <bool QKV>
 __global__ void __launch_bounds__(256)
 enc_embed_kernel(const float* __restrict__ signal, const float* __restrict__ w, const float* __restrict__ b,
-                 float* __restrict__ x, float* __restrict__ part, int n_rows, EmbedQkv eq) {
+                 float* __restrict__ x, float* __restrict__ part, int n_rows) {
   // encoder/transformer.py:104,113 — Linear(1, d) applied to the scalar sample
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= n_rows) return;
@@ -46,28 +45,12 @@ enc_embed_kernel(const float* __restrict__ signal, const float* __restrict__ w, 
   const f32x4 v = s * wv + bv;
   st4(x + (size_t)row * ND_D + lane * 4, v);
   if (part) row_part(v, lane, part + (size_t)row * ND_PART_LD * 2);
-  if constexpr (QKV) {  // layer 0's q | k | v (encoder/transformer.py:44, the rank-2 form of EmbedQkv)
-    const float rs = ln_rsqrt(fmaf(s, fmaf(s, eq.mww, 2.0f * eq.mwb), eq.mbb) + ND_LN_EPS);
-    float* o = eq.qkv + (size_t)row * 3 * ND_D + lane * 4;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int n = j * ND_D + lane * 4;
-      st4(o + j * ND_D, (s * ld4(eq.ac + n) + ld4(eq.ac + 3 * ND_D + n)) * rs + ld4(eq.bias + n));
-    }
-  }
 }
 
 hipError_t launch_enc_embed(const float* signal, const float* w_in, const float* b_in, float* x, float* part, int B,
-                            int T, hipStream_t s, const EmbedQkv* eq) {
+                            int T, hipStream_t s) {
   const int rows = B * T;
-  if (eq) {
-    if (!eq->ac || !eq->bias || !eq->qkv) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(enc_embed_kernel<true>, dim3((rows + 3) / 4), dim3(256), 0, s, signal, w_in, b_in, x, part,
-                       rows, *eq);
-  } else {
-    hipLaunchKernelGGL(enc_embed_kernel<false>, dim3((rows + 3) / 4), dim3(256), 0, s, signal, w_in, b_in, x, part,
-                       rows, EmbedQkv());
-  }
+  hipLaunchKernelGGL(enc_embed_kernel, dim3((rows + 3) / 4), dim3(256), 0, s, signal, w_in, b_in, x, part, rows);
   return hipGetLastError();
 }
 
@@ -539,11 +522,7 @@ static int enc_attn_grid() {
 hipError_t launch_enc_attention(const float* qkv, const float* signal, const int* span, float* out, int B, int T,
                                 hipStream_t s, bool exact, int* ovf) {
   if (T > ENC_MAXT || T <= 0) return hipErrorInvalidValue;
-  static const bool f32 = [] {
-    const char* e = getenv("ND_ENC_ATTN_F32");  // 1: the fp32-MFMA kernel
-    return e && atoi(e) != 0;
-  }();
-  if (f32 || exact)
+  if (exact)
     hipLaunchKernelGGL(enc_attention_kernel, dim3(ND_H, B), dim3(1024), 0, s, qkv, signal, span, out, T);
   else
     hipLaunchKernelGGL(enc_attention_h3_kernel<2>, dim3(std::min(B * ND_H, enc_attn_grid())), dim3(512), 0, s, qkv,

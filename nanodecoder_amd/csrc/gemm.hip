@@ -1433,16 +1433,6 @@ hipError_t init_gemm_attributes() {
   return e != hipSuccess ? e : set_p16s_attr<2, 2>();
 }
 
-static bool gemm_f32_only() {
-  static const bool f32only = [] {
-    const char* e = getenv("ND_GEMM_F32");  // 1: fp32 MFMA kernels even where a split weight exists
-    return e && atoi(e) != 0;
-  }();
-  return f32only;
-}
-
-bool gemm_f32_forced() { return gemm_f32_only(); }
-
 static hipError_t check_args(const GemmArgs& g) {
   if (g.K % 32 != 0 || (g.norm && g.K != ND_D)) return hipErrorInvalidValue;
   if (g.part_in && (g.part_n_in < 1 || g.part_n_in > ND_PART_LD || (ND_D % g.part_n_in) != 0))
@@ -1453,7 +1443,6 @@ static hipError_t check_args(const GemmArgs& g) {
 
 hipError_t launch_gemm(GemmArgs& g, hipStream_t s) {
   if (g.M <= 0) return hipSuccess;
-  if (gemm_f32_only() && g.W) g.Wh = nullptr;
   if (!g.W && !g.Wh) return hipErrorInvalidValue;
   hipError_t e = check_args(g);
   if (e != hipSuccess) return e;
@@ -1483,12 +1472,11 @@ hipError_t launch_gemm(GemmArgs& g, hipStream_t s) {
 
 hipError_t launch_gemm_p16(GemmArgs& g, hipStream_t s) {
   if (g.M <= 0) return hipSuccess;
-  if (gemm_f32_only() && g.W) g.Wh = nullptr;
   if (!g.W && !g.Wh) return hipErrorInvalidValue;
   hipError_t e = check_args(g);
   if (e != hipSuccess) return e;
   constexpr int big_min = 2048;  // rows from which the LDS-tiled kernel takes P16 GEMMs
-  if (g.M >= big_min && !g.prefer_p16 && !g.c_rm && g.Wh_rm && !gemm_f32_only() && g.N % 64 == 0 &&
+  if (g.M >= big_min && !g.prefer_p16 && !g.c_rm && g.Wh_rm && g.N % 64 == 0 &&
       (g.N >= 512 || g.K >= 1024)) {
     // many rows (beam search over large batches): the encoder's LDS-tiled
     // split-fp16 kernel on P16 activations, with the row-major weight image

@@ -86,8 +86,6 @@ hipError_t launch_split_weight(const float* W, int N, int K, uint16_t* Wh, float
 // P16 kernels: [N/16][K/32][hi | lo][64 lanes][8 halves] of W * 2^s (scale as
 // launch_split_weight; synchronises the stream).  N % 16 == 0, K % 32 == 0.
 hipError_t launch_pack_p16h(const float* W, int ld, int N, int K, uint16_t* out, float* wscale, hipStream_t s);
-// ND_GEMM_F32=1: the fp32-MFMA kernels everywhere (split images unused)
-bool gemm_f32_forced();
 // launches per GEMM route (include/nanodec.h ND_ROUTE_*) since the last reset
 long long gemm_route_count(int route, bool reset);
 // raises the dynamic-LDS limit of the LDS-staged GEMM kernels (once per process)
@@ -105,13 +103,12 @@ hipError_t launch_fold_layernorm(const float* W, const float* bias, const float*
 // projection is the rank-2 form
 //   LN(x) W'^T + b'' = (s a + c) / sqrt(s^2 m_ww + 2 s m_wb + m_bb + eps) + b''
 // a = W' w', c = W' b', m_.. the means of w'^2, w'b', b'^2 (W', b'': the
-// LN-folded QKV weight and bias), so the layer's QKV GEMM becomes a write of
-// the [M, 768] rows beside the embedding's.
+// LN-folded QKV weight and bias), so the layer needs no QKV GEMM.
 struct EmbedQkv {
   const float* ac = nullptr;  // [2][768]: a, c
   const float* bias = nullptr;
   float mww = 0.f, mwb = 0.f, mbb = 0.f;
-  float* qkv = nullptr;       // [M, 768] row-major
+  float* qkv = nullptr;       // unread (the rows are never materialised); keeps R2Args' kernel-argument layout
 };
 // Layer 0's attention in the same closed form: per head h the query, key
 // and value of position t are u_h y_t + v_h r_t + w_h (y = s r, r the LN
@@ -131,12 +128,11 @@ hipError_t launch_enc_attention_rank2(const float* signal, const int* span, cons
 // ac and the three means (double scal[3]) from the LN-folded weight [768, 256]
 hipError_t launch_embed_qkv_prep(const float* w_in, const float* b_in, const float* nwqkv, float* ac, double* scal,
                                  hipStream_t s);
-// x[b*T+t][:] = signal[b][t] * w_in + b_in (Linear(1, d)); part: full-row stats;
-// eq: also layer 0's q | k | v rows (EmbedQkv)
+// x[b*T+t][:] = signal[b][t] * w_in + b_in (Linear(1, d)); part: full-row stats
 hipError_t launch_enc_embed(const float* signal, const float* w_in, const float* b_in, float* x, float* part, int B,
-                            int T, hipStream_t s, const EmbedQkv* eq = nullptr);
+                            int T, hipStream_t s);
 // flash attention over qkv [B*T, 768]; mask signal==0; keys >= span excluded
-// exact: the fp32-MFMA kernel instead of split-fp16 (also forced by ND_ENC_ATTN_F32=1);
+// exact: the fp32-MFMA kernel instead of split-fp16;
 // ovf: split-fp16 range guard word (nullable)
 hipError_t launch_enc_attention(const float* qkv, const float* signal, const int* span, float* out, int B, int T,
                                 hipStream_t s, bool exact = false, int* ovf = nullptr);

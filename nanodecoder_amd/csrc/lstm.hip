@@ -8,7 +8,7 @@
 // with 16 waves, wave w owns the four gates (i, f, g, o) of units
 // 8w .. 8w + 7 as two 16-column tiles (i | f, g | o) of MFMA B operands (8
 // waves: 16 units, four tiles), split-fp16 hi/lo on v_mfma_f32_16x16x32_f16
-// (or fp32 on v_mfma_f32_16x16x4_f32 with ND_LSTM_F32=1, NS = 16).  h_{t-1}
+// (or fp32 on v_mfma_f32_16x16x4_f32 in exact fp32, NS = 16).  h_{t-1}
 // is the A operand, read from LDS (rows NS..15 zero).  A lane finds the other
 // half of its unit's gates in lane ^ 8 (one DPP move); with NS < 16 the gate
 // sums then fan out to the lanes of the padding rows (permlane swaps), and
@@ -408,12 +408,7 @@ lstm_dir_kernel(const float* __restrict__ xp,      // [B*T, 1024] input projecti
 hipError_t launch_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum,
                              const float* whh, const int* len, int B, int T, float* out, const float* bn_scale,
                              const float* bn_shift, bool layer0, hipStream_t s, bool exact) {
-  static const bool f32_env = [] {
-    const char* e = getenv("ND_LSTM_F32");  // 1: fp32 MFMAs for the recurrence
-    const char* g = getenv("ND_GEMM_F32");
-    return (e && atoi(e) != 0) || (g && atoi(g) != 0);
-  }();
-  const bool f32 = f32_env || exact;
+  const bool f32 = exact;
   // split-fp16: 4 sequences per workgroup (measured: 0.95 ms per layer at 4, 1.04 at 8, 1.52 at 16), the
   // cell's sigmoid / tanh on the hardware exp and reciprocal; fp32 MFMAs: 16 sequences per workgroup
   const int ns = f32 ? 16 : 4;

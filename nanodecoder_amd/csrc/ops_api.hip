@@ -1,0 +1,358 @@
+// libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads): single
+// launches on the caller's stream, with no context.  The nd_op_* calls exist for the op-level tests.
+#include "engine.hpp"
+
+static hipError_t gemm(const float* A, int lda, const float* W, int N, int K, const float* bias, float* C, int ldc,
+                       int M, hipStream_t s, bool norm = false, bool relu = false, const float* R = nullptr,
+                       int ldr = 0) {
+  nd::GemmArgs g;
+  g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
+  g.norm = norm; g.M = M; g.N = N; g.K = K; g.relu = relu;
+  return nd::launch_gemm(g, s);
+}
+
+int nd_op_gemm(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
+               int32_t K, int32_t norm, int32_t relu, void* stream) {
+  hipError_t e = gemm(A, K, W, N, K, bias, C, N, M, (hipStream_t)stream, norm != 0, relu != 0, R, N);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_split_weight(const float* W, int32_t N, int32_t K, uint16_t* Wh, float* wscale, void* stream) {
+  hipError_t e = nd::launch_split_weight(W, N, K, Wh, wscale, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("split_weight: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_gemm_split(const float* A, const uint16_t* Wh, float wscale, const float* bias, const float* R, float* C,
+                     int32_t M, int32_t N, int32_t K, int32_t norm, int32_t relu, void* stream) {
+  if (!Wh) return fail(ND_ERR_ARG, "gemm_split: null Wh");
+  G g(A, K, nullptr, N, K, bias, C, N, M);
+  g.a.Wh = Wh;
+  g.a.wscale = wscale;
+  g.a.norm = norm != 0;
+  g.a.relu = relu != 0;
+  if (R) g.res(R, N);
+  hipError_t e = g.run((hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_split: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_gemm_split_q24(const float* A, const uint16_t* Wh, float wscale, const float* bias, void* img,
+                         int32_t plane_rows, int32_t M, int32_t N, int32_t K, int32_t norm, void* stream) {
+  if (!Wh || !img || plane_rows < M) return fail(ND_ERR_ARG, "gemm_split_q24: null Wh / image, or plane_rows < M");
+  G g(A, K, nullptr, N, K, bias, nullptr, N, M);
+  g.a.Wh = Wh;
+  g.a.wscale = wscale;
+  g.a.norm = norm != 0;
+  g.q24(static_cast<uint8_t*>(img), (size_t)plane_rows * CTXQ_ROW);
+  hipError_t e = g.run((hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_split_q24: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+static int ensure_attributes() {
+  static hipError_t e = nd::init_kernel_attributes();
+  return e == hipSuccess ? ND_OK : fail(ND_ERR_HIP, "hipFuncSetAttribute failed");
+}
+
+int nd_op_dec_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h, float w2s,
+                  const float* b2, float* x, float* xpart, int32_t M, int32_t F, int32_t nsplit, float* slab,
+                  int32_t* tickets, const int32_t* skip, int32_t skip_rpc, int32_t* overflow, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  nd::DecFfn df;
+  df.nsplit = nsplit;
+  df.slab = slab;
+  df.tickets = tickets;
+  df.skip = skip;
+  df.skip_rpc = skip_rpc;
+  hipError_t e = nd::launch_dec_ffn(y, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, df, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ffn: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int64_t nd_op_dec_ffn_slab_floats(int32_t M, int32_t nsplit) {
+  return M > 0 && nsplit > 0 ? (int64_t)nd::dec_ffn_slab_floats(M, nsplit) : 0;
+}
+
+int nd_op_gemm_p16(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M,
+                   int32_t N, int32_t K, const float* part_in, int32_t part_n_in, float* part_out, int32_t relu,
+                   int32_t* part_n_out, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  nd::GemmArgs g;
+  g.A = A; g.W = W; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K; g.relu = relu != 0;
+  g.norm = part_in != nullptr; g.part_in = part_in; g.part_n_in = part_n_in; g.part_out = part_out;
+  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16: ") + hipGetErrorString(e));
+  if (part_n_out) *part_n_out = g.part_n_out;
+  return ND_OK;
+}
+
+int nd_op_pack_p16h(const float* W, int32_t N, int32_t K, uint16_t* out, float* wscale, void* stream) {
+  hipError_t e = nd::launch_pack_p16h(W, K, N, K, out, wscale, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("pack_p16h: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_enc_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h, float w2s,
+                  const float* b2, float* x, float* xpart, int32_t M, int32_t F, int32_t* overflow, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  hipError_t e = nd::launch_enc_ffn(y, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_ffn: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_enc_ffn_wo(const float* att, const float* x_in, const uint16_t* woh, float wos, const float* bo,
+                     const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h, float w2s, const float* b2,
+                     float* x, float* xpart, const uint16_t* qkvh, float qkvs, const float* qkvb, float* qkv,
+                     int32_t M, int32_t F, int32_t* overflow, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  nd::EncWo wo;
+  wo.att = att;
+  wo.woh = woh;
+  wo.wos = wos;
+  wo.bo = bo;
+  nd::EncQkv qk;
+  qk.wh = qkvh;
+  qk.ws = qkvs;
+  qk.bias = qkvb;
+  qk.out = qkv;
+  hipError_t e = nd::launch_enc_ffn(x_in, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, (hipStream_t)stream,
+                                    &wo, qkvh ? &qk : nullptr);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_ffn_wo: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_gemm_p16_split(const float* A, const uint16_t* Wh, float wscale, const float* bias, const float* R, float* C,
+                         int32_t M, int32_t N, int32_t K, const float* part_in, int32_t part_n_in, float* part_out,
+                         int32_t relu, int32_t* part_n_out, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!Wh) return fail(ND_ERR_ARG, "gemm_p16_split: null Wh");
+  nd::GemmArgs g;
+  g.A = A; g.Wh = Wh; g.wscale = wscale; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K;
+  g.relu = relu != 0; g.norm = part_in != nullptr; g.part_in = part_in; g.part_n_in = part_n_in;
+  g.part_out = part_out;
+  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_split: ") + hipGetErrorString(e));
+  if (part_n_out) *part_n_out = g.part_n_out;
+  return ND_OK;
+}
+
+static int gemm_p16_splitk(const float* A, const uint16_t* Wh, const float* W, float wscale, const float* bias,
+                           const float* R, float* C, int32_t M, int32_t N, int32_t K, float* part_out, float* slab,
+                           int32_t* tickets, int32_t tiles, int32_t* part_n_out, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!A || (!Wh && !W) || !C || !slab || !tickets || tiles < 1)
+    return fail(ND_ERR_ARG, "gemm_p16_splitk: bad arguments");
+  if ((K != 1024 && K != 2048) || N % 32 || M <= 128 || ((M + 31) / 32) * (N / 32) > tiles)
+    return fail(ND_ERR_ARG, "gemm_p16_splitk: needs K 1024 / 2048, N % 32 == 0, M > 128 and enough tiles");
+  nd::GemmArgs g;
+  g.A = A; g.Wh = Wh; g.W = W; g.wscale = wscale; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K;
+  g.part_out = part_out;
+  g.sk_slab = slab; g.sk_cnt = tickets; g.sk_tiles = tiles;
+  const long long before = nd::gemm_route_count(ND_ROUTE_P16_SPLITK, false);
+  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_splitk: ") + hipGetErrorString(e));
+  if (nd::gemm_route_count(ND_ROUTE_P16_SPLITK, false) == before) return fail(ND_ERR_ARG, "gemm_p16_splitk: not taken");
+  if (part_n_out) *part_n_out = g.part_n_out;
+  return ND_OK;
+}
+
+int nd_op_gemm_p16_splitk(const float* A, const uint16_t* Wh, float wscale, const float* bias, const float* R,
+                          float* C, int32_t M, int32_t N, int32_t K, float* part_out, float* slab, int32_t* tickets,
+                          int32_t tiles, int32_t* part_n_out, void* stream) {
+  if (!Wh) return fail(ND_ERR_ARG, "gemm_p16_splitk: null Wh");
+  return gemm_p16_splitk(A, Wh, nullptr, wscale, bias, R, C, M, N, K, part_out, slab, tickets, tiles, part_n_out,
+                         stream);
+}
+
+int nd_op_gemm_p16_splitk_f32(const float* A, const float* W, const float* bias, const float* R, float* C,
+                              int32_t M, int32_t N, int32_t K, float* part_out, float* slab, int32_t* tickets,
+                              int32_t tiles, int32_t* part_n_out, void* stream) {
+  if (!W) return fail(ND_ERR_ARG, "gemm_p16_splitk_f32: null W");
+  return gemm_p16_splitk(A, nullptr, W, 1.0f, bias, R, C, M, N, K, part_out, slab, tickets, tiles, part_n_out,
+                         stream);
+}
+
+int nd_op_gemm_p16_split_rm(const float* A, const uint16_t* Wh, float wscale, const uint16_t* Wh_rm, float wscale_rm,
+                            const float* bias, const float* R, float* C, int32_t M, int32_t N, int32_t K,
+                            const float* part_in, int32_t part_n_in, float* part_out, int32_t relu,
+                            int32_t* part_n_out, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!Wh || !Wh_rm) return fail(ND_ERR_ARG, "gemm_p16_split_rm: null weight image");
+  nd::GemmArgs g;
+  g.A = A; g.Wh = Wh; g.wscale = wscale; g.Wh_rm = Wh_rm; g.wscale_rm = wscale_rm; g.bias = bias; g.R = R; g.C = C;
+  g.M = M; g.N = N; g.K = K; g.relu = relu != 0; g.norm = part_in != nullptr; g.part_in = part_in;
+  g.part_n_in = part_n_in; g.part_out = part_out;
+  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_split_rm: ") + hipGetErrorString(e));
+  if (part_n_out) *part_n_out = g.part_n_out;
+  return ND_OK;
+}
+
+int nd_op_pack_p16(const float* src, float* dst, int32_t M, int32_t N, void* stream) {
+  hipError_t e = nd::launch_pack_p16(src, N, dst, M, N, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("pack_p16: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_fold_layernorm(const float* W, const float* bias, const float* ln_g, const float* ln_b, float* W_out,
+                         float* b_out, int32_t N, int32_t K, void* stream) {
+  hipError_t e = nd::launch_fold_layernorm(W, bias, ln_g, ln_b, W_out, b_out, N, K, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("fold_layernorm: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B, int32_t T,
+                        void* stream) {
+  hipError_t e = nd::launch_enc_attention(qkv, signal, span, out, B, T, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_attention: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_self_attention(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
+                             int32_t max_steps, float* out, int32_t R, void* stream) {
+  hipError_t e = nd::launch_dec_self_attention(qkv, cache, anc, anc_ld, step, max_steps, out, R, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_self_attention_beam(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
+                                  int32_t max_steps, float* out, int32_t R, int32_t rpc, const int32_t* done,
+                                  void* stream) {
+  if (!qkv || !cache || !anc || !out || rpc < 2 || rpc > 8 || R % rpc)
+    return fail(ND_ERR_ARG, "dec_self_attention_beam: bad arguments");
+  hipError_t e = nd::launch_dec_self_attention(qkv, cache, anc, anc_ld, step, max_steps, out, R, (hipStream_t)stream,
+                                               rpc, done);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_beam: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
+                                 int32_t max_steps, float* out, int32_t R, int32_t rpc, const int32_t* done,
+                                 void* stream) {
+  if (!qkv || !cache || !out || rpc < 1 || rpc > 8 || R % rpc || (rpc > 1 && !anc))
+    return fail(ND_ERR_ARG, "dec_self_attention_q24: bad arguments");
+  hipError_t e = nd::launch_dec_self_attention(qkv, static_cast<float*>(cache), anc, anc_ld, step, max_steps, out, R,
+                                               (hipStream_t)stream, rpc, done, nd::QkvRows(), nullptr, nullptr, 0,
+                                               true);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_q24: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int32_t* span, float pad_val,
+                            float* out, int32_t C, int32_t rpc, int32_t T, int32_t ldT, int32_t grid, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  hipError_t e = nd::launch_dec_mem_attention(qp, mem, signal, span, pad_val, out, C, rpc, T, ldT, (hipStream_t)stream,
+                                              nullptr, nullptr, 0, grid);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_mem_attention: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
+                     const int32_t* len, int32_t B, int32_t T, float* out, const float* bn_scale,
+                     const float* bn_shift, int32_t layer0, void* stream) {
+  if (B < 1 || T < 1 || !whh || !len || !out || (layer0 ? (!signal || !wih0 || !bsum) : !xp))
+    return fail(ND_ERR_ARG, "lstm_layer: bad arguments");
+  if ((bn_scale == nullptr) != (bn_shift == nullptr))
+    return fail(ND_ERR_ARG, "lstm_layer: bn_scale and bn_shift must both be set or both be null");
+  hipError_t e = nd::launch_lstm_layer(xp, signal, wih0, bsum, whh, len, B, T, out, bn_scale, bn_shift, layer0 != 0,
+                                       (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("lstm_layer: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_normalize_reads(const double* d_raw, const int64_t* d_offsets, int32_t R, int32_t method, float* d_out,
+                       void* stream) {
+  hipError_t e = nd::launch_read_normalize(d_raw, (const long long*)d_offsets, R, method, d_out, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("normalize_reads: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_window_reads(const float* d_sig, const int64_t* d_offsets, const int32_t* d_read, const int32_t* d_start,
+                    const int32_t* d_len, int32_t C, int32_t T, float* d_signal, void* stream) {
+  hipError_t e = nd::launch_read_window(d_sig, (const long long*)d_offsets, d_read, d_start, d_len, C, T, d_signal,
+                                        (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("window_reads: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_memory_pack(const float* x, const float* ln_g, const float* ln_b, float* out, int32_t B, int32_t T,
+                      int32_t ldT, void* stream) {
+  hipError_t e = nd::launch_memory_pack(x, ln_g, ln_b, out, B, T, ldT, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("memory_pack: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_bank_pack_d8(const float* x, const float* ln_g, const float* ln_b, void* bank, float* kscale,
+                       int32_t* kemax, const int32_t* span, int32_t B, int32_t T, int32_t* ovf, void* stream) {
+  if (!x || !bank || !kscale || !kemax || (ln_g == nullptr) != (ln_b == nullptr))
+    return fail(ND_ERR_ARG, "bank_pack_d8: bad arguments");
+  hipError_t e = nd::launch_bank_pack_d8(x, ln_g, ln_b, bank, kscale, kemax, span, B, T, ovf, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("bank_pack_d8: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_bank_d8(const float* qp, const void* bank, const float* kscale, const int32_t* kemax,
+                      const float* signal, const int32_t* span, float pad_val, float* out, int32_t C, int32_t T,
+                      int32_t* ovf, int32_t grid, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!qp || !bank || !kscale || !kemax || !signal || !span || !out || grid < 0)
+    return fail(ND_ERR_ARG, "dec_bank_d8: bad arguments");
+  hipError_t e = nd::launch_dec_bank_d8(qp, bank, kscale, kemax, signal, span, pad_val, out, C, T,
+                                        (hipStream_t)stream, nullptr, nullptr, 0, ovf, false, grid);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_bank_d8: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_ctx_attention(const float* q, const float* kv, int32_t ld, int32_t koff, const float* signal,
+                            const int32_t* span, float pad_val, float* out, int32_t C, int32_t rpc, int32_t T,
+                            void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  hipError_t e = nd::launch_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, out, C, rpc, T,
+                                              (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_ctx_pack_q24(const float* kv, int32_t ld, int32_t layers, void* out, const int32_t* span, int32_t B,
+                       int32_t T, void* stream) {
+  if (!kv || !out || !span) return fail(ND_ERR_ARG, "ctx_pack_q24: bad arguments");
+  hipError_t e = nd::launch_ctx_pack_q24(kv, ld, layers, static_cast<uint8_t*>(out), span, B, T, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("ctx_pack_q24: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int32_t koff, int32_t q24,
+                                 const float* signal, const int32_t* span, float pad_val, float* out, int32_t C,
+                                 int32_t rpc, int32_t T, const int32_t* clist, int32_t ccap, int32_t nsplit,
+                                 float* part, const int32_t* done, void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!q || !kv || !signal || !span || !out || !clist || (nsplit > 1 && !part))
+    return fail(ND_ERR_ARG, "dec_ctx_attention_list: bad arguments");
+  hipError_t e = nd::launch_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, out, C, rpc, T,
+                                              (hipStream_t)stream, nullptr, nullptr, 0, done, q24 != 0, clist, ccap,
+                                              nsplit, part);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_list: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_alive_list(const int32_t* done, int32_t C, int32_t* list, int32_t cap, int32_t* ovf, void* stream) {
+  if (!done || !list) return fail(ND_ERR_ARG, "alive_list: bad arguments");
+  hipError_t e = nd::launch_alive_list(done, C, list, cap, ovf, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("alive_list: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int nd_op_dec_ctx_attention_q24(const float* q, const void* kvq, int32_t layers, int32_t layer, const float* signal,
+                                const int32_t* span, float pad_val, float* out, int32_t C, int32_t rpc, int32_t T,
+                                void* stream) {
+  if (int rc = ensure_attributes()) return rc;
+  if (!q || !kvq || !signal || !span || !out || layer < 0 || layer >= layers)
+    return fail(ND_ERR_ARG, "dec_ctx_attention_q24: bad arguments");
+  const uint8_t* plane = static_cast<const uint8_t*>(kvq) + (size_t)layer * C * T * CTXQ_ROW;
+  hipError_t e = nd::launch_dec_ctx_attention(q, plane, CTXQ_ROW, 0, signal, span, pad_val, out, C, rpc, T,
+                                              (hipStream_t)stream, nullptr, nullptr, 0, nullptr, true);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_q24: ") + hipGetErrorString(e));
+  return ND_OK;
+}

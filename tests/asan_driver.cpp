@@ -1,5 +1,5 @@
 // Host-side AddressSanitizer driver of the C-ABI (SURVEY §5 "race detection
-// / sanitizers").  Linked with engine.hip's host code compiled under
+// / sanitizers").  Linked with the host code (engine.hip, model.hip, ops_api.hip) compiled under
 // -Xarch_host -fsanitize=address (device code unsanitized: GPU ASan is not
 // available), see nanodecoder_amd/build.py build_asan().  Test
 // infrastructure, run by tests/test_asan.py.

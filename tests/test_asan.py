@@ -1,5 +1,5 @@
 """Host-code AddressSanitizer run of the C-ABI (SURVEY §5 "race detection /
-sanitizers"): tests/asan_driver.cpp linked with engine.hip's host code built
+sanitizers"): tests/asan_driver.cpp linked with the host code (engine.hip, model.hip, ops_api.hip) built
 under -fsanitize=address (nanodecoder_amd/build.py build_asan; device code is
 not instrumented).  CPU: every entry point's argument validation and the
 no-device error path, leak detection on.  GPU: the whole lifecycle (weight

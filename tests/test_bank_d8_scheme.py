@@ -123,7 +123,7 @@ def test_context_product_scale():
 
 
 def bank_dim_scales(g, b):
-    """engine.hip derive_bank_dim_scales: per-dimension powers of two c_i =
+    """model.hip derive_bank_dim_scales: per-dimension powers of two c_i =
     2^clamp(floor(log2(a_i / median a)), 0, 12), a_i = 3 |g_i| + |b_i|, of the
     encoder's final LayerNorm affine; the bank holds m_i / c_i."""
     a = 3.0 * np.abs(np.asarray(g, np.float64)) + np.abs(np.asarray(b, np.float64))

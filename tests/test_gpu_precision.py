@@ -150,7 +150,7 @@ def test_bank_d8_outlier_dimension_vs_fp64():
     function-preserving case, tests/outlier_util.py).
 
     (a) The engine's form: the bank holds each dimension divided by a power
-    of two taken from the LN affine (engine.hip derive_bank_dim_scales,
+    of two taken from the LN affine (model.hip derive_bank_dim_scales,
     restated in tests/test_bank_d8_scheme.py::bank_dim_scales), folded back
     into q' and the output: the outlier costs no bits, so every dimension
     meets the plain rows' bar, 2e-5 of its magnitude.
@@ -227,7 +227,7 @@ def test_ctx_q24_outlier_dimension_vs_fp64(layer):
     with key dimension 45 and value dimension 45 (head 1) 10^3 x the rest, q
     reading the key dimension 10^-3 as strongly: the image's raw form (the
     engine rebalances such a dimension away before it reaches the image,
-    engine.hip rebalance_attention; test_beam_outlier_model_vs_oracle).
+    model.hip rebalance_attention; test_beam_outlier_model_vs_oracle).
     Bound: an element carries 2^-24 of the power of two above its head's
     largest value (2^12 here), so 2^-12 absolute on head 1's other
     dimensions, whose context values take that plus the softmax's response
@@ -283,7 +283,7 @@ def test_self_q24_history_outlier_dimension_vs_fp64():
     per (key, head), appended every step) with key and value dimension 45
     10^3 x the rest on every step, q reading the key dimension 10^-3 as
     strongly; 40 steps through a fixed ancestry (the history's raw form: the
-    engine rebalances such a dimension away, engine.hip rebalance_attention).
+    engine rebalances such a dimension away, model.hip rebalance_attention).
     Same bound as the context image: head 1's other dimensions within 2^-11,
     the outlier dimension within 2^-12 of its magnitude, the other heads 2e-5
     (measured round 6: 2.4e-4, 5.0e-5)."""
@@ -358,7 +358,7 @@ def test_beam_outlier_model_vs_oracle():
 
 def test_reload_after_rebalance_keeps_the_model():
     """nd_finalize rebalances the decoder attentions' projections in place
-    (engine.hip rebalance_attention); a tensor loaded into the context after
+    (model.hip rebalance_attention); a tensor loaded into the context after
     that gets the same exact scales, so reloading the same weights and
     finalizing again gives bitwise the same outputs (greedy and beam)."""
     import ctypes

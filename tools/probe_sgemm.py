@@ -1,6 +1,6 @@
 """Probe: the library's fp32 GEMM rate (torch.mm -> hipBLASLt / rocBLAS) at the
 exact-fp32 encoder's shapes (M = 256 chunks x 512 samples), beside the
-engine's own fp32 GEMM (nd_op_gemm with exact fp32 forced, ND_GEMM_F32=1).
+engine's own fp32 GEMM (nd_op_gemm: it has no split image, so it runs the fp32 kernels).
 
 Only a yardstick for what fp32 MFMA work reaches on this chip at these
 shapes; the product never calls the library GEMM (its LN prologue and
