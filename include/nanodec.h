@@ -474,6 +474,17 @@ int nd_op_dec_self_attention_beam(const float* qkv, float* cache, const int32_t*
 int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
                                  int32_t max_steps, float* out, int32_t R, int32_t rpc, const int32_t* done,
                                  void* stream);
+/* The greedy rows' layer-0 form (one row per chunk, no ancestry): table
+ * [table_steps * V, 3*d] row-major holds q | k | v of input token v at step s
+ * in row s * V + v.  Row r's own q | k | v is row step * V + tok[r] (step 0:
+ * tok0 for every row, tok unused), its key t < step the k | v part of row
+ * t * V + (t == 0 ? tok0 : hist[r * hist_ld + t - 1]): hist [R, hist_ld]
+ * holds the token each row picked at every earlier step (values in [0, V)).
+ * cache (nullable) is neither read nor written; out [R, d] P16-packed.
+ * step < min(table_steps, max_steps). */
+int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int32_t V, const int32_t* tok,
+                                   int32_t tok0, const int32_t* hist, int32_t hist_ld, float* cache, int32_t step,
+                                   int32_t max_steps, float* out, int32_t R, void* stream);
 
 /* Memory-bank context attention (greedy form, model.hip
  * derive_memory_bank_weights; replaces the context MultiHeadedAttention of

@@ -864,8 +864,16 @@ __device__ __forceinline__ void merge_waves_part(float* accs, float* ms, float* 
 // head's scales, the step's own key is quantised the same way in registers
 // (the one value every later step reads back), and the scores and v are
 // dequantised exactly as the context attention does.
+// TAB (round 7; greedy rows in table mode, QkvRows.hist): layer 0's key t < step of row r is a bit-for-bit
+// copy of the k | v part of table row t * V + tok_in(r, t), tok_in(r, 0) = BOS, tok_in(r, t) = the token the
+// head picked at step t - 1 (qr.hist).  The history is read from the table, which every row, lane and call
+// shares (default load policy: it stays in L2), and the cache is neither read nor written; the arithmetic is
+// the cache form's, so the outputs are bitwise the same.  A row's tokens are workgroup-uniform: pass 0's are
+// scalar loads (wave 0 of the HEAD form fetches them before it runs the head, whose store to the same
+// buffer would otherwise sit between them and their use), the later passes' (beyond NW * KW keys) come from
+// one lane-indexed vector load issued at the top, so no form waits for loads in flight to issue more.
 #define SELF_Q24_ROW CTXQ_ROW
-template <int NW, int KW, bool ANC, bool HEAD, bool Q24>
+template <int NW, int KW, bool ANC, bool HEAD, bool Q24, bool TAB = false>
 __global__ void __launch_bounds__(NW * 64)
 dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cache, const int* __restrict__ anc,
                           int anc_ld, int step, int S, float* __restrict__ out, int rpc, const int* __restrict__ skip,
@@ -901,7 +909,49 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
   u32v3 kr[KW], vr[KW];  // Q24: the lane's 12 bytes of k and of v
   f32x2 sr[KW];          // Q24: its head's {k scale, v scale}
   const int wu = __builtin_amdgcn_readfirstlane(wave);
+  static_assert(!TAB || (!ANC && !Q24), "table history: greedy rows, fp32");
+  static_assert(!HEAD || TAB, "the head-fused form reads its history from the table");
+  // TAB: the tokens behind this wave's keys.  Key t's table row needs the token picked at step t - 1
+  // (t == 0: BOS); t is clamped into the history like the loads below, so the index is at most step - 2,
+  // written by an earlier launch.  tk: pass 0's, scalar loads.  tvl: the later passes' (forms of several
+  // passes: NW * KW = 128), pass p's key u in lane p * KW + u, one vector load, parked in the wave's own
+  // LDS row (stash_tvl) at a point where it has long arrived: the later passes then wait on LDS, not on
+  // every load in flight
+  constexpr bool MULTI = TAB && NW * KW >= 128;  // the launcher's form for more than 64 keys
+  static_assert(!MULTI || (64 / KW) * NW * KW >= SELF_MAXS, "one lane per key of every pass");
+  __shared__ int htoks[MULTI ? NW * 64 : 1];
+  int tk[KW], tvl = 0;
+  auto stash_tvl = [&] {
+    if constexpr (MULTI) htoks[wu * 64 + lane] = tvl;
+  };
+  auto hist_tok = [&](int h, int t) { return t == 0 ? qr.tok0 : min(max(h, 0), qr.V - 1); };
+  if constexpr (TAB) {
+    const int tmax = max(step - 1, 0);
+    const int* hr = qr.hist + (size_t)r * qr.hist_ld;
+    if constexpr (MULTI) tvl = hr[max(min((lane / KW) * NW * KW + wu * KW + lane % KW, tmax) - 1, 0)];
+#pragma unroll
+    for (int u = 0; u < KW; ++u) {
+      const int t = min(wu * KW + u, tmax);
+      tk[u] = hist_tok(hr[max(t - 1, 0)], t);
+    }
+  }
   auto load_pass = [&](int base) {
+    if constexpr (TAB) {
+      const int t0 = base + wu * KW, tmax = max(step - 1, 0);
+#pragma unroll
+      for (int u = 0; u < KW; ++u) {
+        const int t = min(t0 + u, tmax);  // wave-uniform
+        int tok = tk[u];
+        if constexpr (MULTI)
+          if (base > 0)
+            tok = hist_tok(__builtin_amdgcn_readfirstlane(htoks[wu * 64 + base / (NW * KW) * KW + u]), t);
+        // the k | v part of the table row (row-major, q | k | v): a scalar base plus the lane's offset
+        const float* row = qkv + ((size_t)(t * qr.V + tok) * 3 + 1) * ND_D + lane * 4;
+        k[u] = ld4(row);
+        v[u] = ld4(row + ND_D);
+      }
+      return;
+    }
     // Q24: the wave index from an SGPR, so each key's row address is a scalar base plus the lane's constant
     // offsets (its three loads per key otherwise held two 64-bit vector addresses per key in flight and
     // spilled at KW = 16); the fp32 forms keep the vector form, whose schedule has no drain
@@ -944,13 +994,14 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
       }
     }
   };
-  // the first pass's cache loads go out before the row's q | k | v, whose
+  // the first pass's history loads go out before the row's q | k | v, whose
   // address (table mode) waits on the row's token
-  // HEAD: wave 0 runs the head before its own cache loads (its registers are
-  // then free of the keys: no spill); the other waves first load the step's
-  // V candidate table rows (every token the head can pick) for LDS, then
-  // their cache loads, so the row's q | k | v is an LDS read once the token
-  // is known (not a global round trip after the barrier)
+  // HEAD: wave 0 runs the head before its own history loads (its registers are
+  // then free of the keys: no spill; their tokens are in SGPRs already); the
+  // other waves first load the step's V candidate table rows (every token the
+  // head can pick) for LDS, then their history loads, so the row's q | k | v
+  // is an LDS read once the token is known (not a global round trip after the
+  // barrier)
   f32x4 qv, kme, vme;
   if constexpr (HEAD) {
     __shared__ float hlp[ND_MAXV];
@@ -959,6 +1010,7 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
     if (wu == 0) {
       const int b = greedy_head_row(hd, r, step - 1, lane, hlp);
       if (lane == 0) htok = b;
+      stash_tvl();  // (arrived during the head)
       load_pass(0);
     } else {
       // V x 192 float4 pieces over (NW - 1) x 64 threads, clamped (straight-line:
@@ -978,6 +1030,7 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
         const int e = min(t0 + i * (NW - 1) * 64, n4 - 1);
         st4(tabs + 4 * e, tv[i]);
       }
+      stash_tvl();  // (older than the candidate rows just stored)
     }
     lds_barrier();  // LDS only: the cache loads stay in flight
     const float* trow = tabs + htok * (3 * ND_D);
@@ -993,6 +1046,7 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
     qv = ld4(qr0) / ND_SQRT_DH;
     kme = ld4(qr0 + qstep);
     vme = ld4(qr0 + 2 * qstep);
+    stash_tvl();  // (the oldest load in flight)
   }
   if constexpr (Q24) {  // the step's own key as every later step will read it back
     kme = q24_raw(kme);
@@ -1037,7 +1091,7 @@ dec_self_attention_kernel(const float* __restrict__ qkv, float* __restrict__ cac
       online_update<1, KW>(sc, vf, m, l, acc);
     }
   }
-  if (wave == 0) {
+  if (!TAB && wave == 0) {  // (TAB: every later step reads this key from the table)
     if constexpr (Q24) {
       uint8_t* mine = reinterpret_cast<uint8_t*>(cache) + ((size_t)r * S + step) * SELF_Q24_ROW;
       *reinterpret_cast<u32x3*>(mine + 12 * lane) = u32x3{__float_as_uint(kme.x), __float_as_uint(kme.y),
@@ -1235,9 +1289,13 @@ hipError_t launch_dec_self_attention(const float* qkv, float* cache, const int* 
     return hipGetLastError();
   }
   if (qr.tok && (qr.V < 1 || qr.tok0 < 0 || qr.tok0 >= qr.V)) return hipErrorInvalidValue;
+  // table history: greedy rows on the row-major table; keys up to step - 1 need hist[r][0 .. step - 2]
+  const bool tab = qr.hist != nullptr;
+  if (tab && (!qr.tok || !qr.rm || anc || skip || clist || rpc != 1 || q24 || qr.hist_ld < 1 || qr.hist_ld < step - 1))
+    return hipErrorInvalidValue;
   if (head) {
-    if (!qr.tok || anc || skip || rpc != 1 || step < 1 || head->V != qr.V || head->V > SELF_TABV ||
-        head->S > max_steps)
+    if (!tab || step < 1 || head->V != qr.V || head->V > SELF_TABV || head->S > max_steps ||
+        head->out_tokens != qr.hist || head->S != qr.hist_ld)
       return hipErrorInvalidValue;
     const hipError_t e = check_greedy_head(*head);
     if (e != hipSuccess) return e;
@@ -1249,23 +1307,25 @@ hipError_t launch_dec_self_attention(const float* qkv, float* cache, const int* 
   const int grid = clist ? ccap * skip_rpc : R;
   if (step >= max_steps || step >= SELF_MAXS) return hipErrorInvalidValue;
   const int n = step + 1;
-#define ND_SELF3(NW, KW, A, HD, Q)                                                                                \
-  hipLaunchKernelGGL((dec_self_attention_kernel<NW, KW, A, HD, Q>), dim3(grid), dim3(NW * 64), 0, s, qkv, cache,   \
+#define ND_SELF3(NW, KW, A, HD, Q, TB)                                                                              \
+  hipLaunchKernelGGL((dec_self_attention_kernel<NW, KW, A, HD, Q, TB>), dim3(grid), dim3(NW * 64), 0, s, qkv, cache, \
                      anc, anc_ld, step, max_steps, out, rpc, skip, skip_rpc, qr, hd, clist)
-#define ND_SELF2(NW, KW, A, HD)       \
-  do {                                \
-    if (q24)                          \
-      ND_SELF3(NW, KW, A, HD, true);  \
-    else                              \
-      ND_SELF3(NW, KW, A, HD, false); \
+#define ND_SELF2(NW, KW, A)                  \
+  do {                                       \
+    if (q24)                                 \
+      ND_SELF3(NW, KW, A, false, true, false);  \
+    else                                     \
+      ND_SELF3(NW, KW, A, false, false, false); \
   } while (0)
-#define ND_SELF(NW, KW)                \
-  if (anc)                             \
-    ND_SELF2(NW, KW, true, false);     \
-  else if (head)                       \
-    ND_SELF2(NW, KW, false, true);     \
-  else                                 \
-    ND_SELF2(NW, KW, false, false)
+#define ND_SELF(NW, KW)                              \
+  if (anc)                                           \
+    ND_SELF2(NW, KW, true);                          \
+  else if (head)                                     \
+    ND_SELF3(NW, KW, false, true, false, true);      \
+  else if (tab)                                      \
+    ND_SELF3(NW, KW, false, false, false, true);     \
+  else                                               \
+    ND_SELF2(NW, KW, false)
   // 4 waves of up to 16 keys per row up to 64 keys (beam rows: configs[3]
   // pooled 75.62 -> 74.59 ms, one call 94.28 -> 93.60 ms; greedy rows pooled
   // 16.75 / 16.84 -> 16.72 / 16.70 ms), then 8 waves of 16 keys (the 16-wave

@@ -118,10 +118,6 @@ static int alloc_workspaces(nd_ctx* c) {
   WS(c->cache, Ld * R * S * 2 * D);
   WS(c->tok, R);
   if (cfg.self_attn_type != ND_SELF_AVERAGE) {
-    const size_t QR = (S * (size_t)c->V + 15) / 16 * 16;
-    WS(c->qtab_x, QR * D);
-    WS(c->qtab_part, QR * ND_PART_LD * 2);
-    WS(c->qtab, QR * 3 * D);
     WS(c->rtok, R);
   }
   WS(c->gtok, B * S);
@@ -272,12 +268,15 @@ static hipError_t enqueue_ctxkv(nd_ctx* c, int B, int T, hipStream_t s, bool q24
   return G(c->x, D, c->m.ctxkv_w, N, D, c->m.ctxkv_b, c->ctxkv, N, M).h3(c).q24(img, plane).run(s);
 }
 
-// Layer 0 of a scaled-dot decoder reads q | k | v from the per-call table
-// QKV0[step][token] (kernels.hpp, QkvRows; c->qtab) instead of running its QKV
-// GEMM every step.  Average-attention decoders have no table (alloc_workspaces)
-// and keep the per-step GEMM.  With the table, the greedy head is fused into
-// the next step's layer-0 self-attention.
-static bool head_fused(const nd_ctx* c) { return c->qtab && c->V <= 8; }  // SELF_TABV
+// Layer 0 of a scaled-dot decoder reads q | k | v from the model's table
+// QKV0[step][token] (kernels.hpp, QkvRows; Model.qtab, built by nd_finalize in
+// the call's product mode) instead of running its QKV GEMM every step.
+// Average-attention decoders have no table and keep the per-step GEMM.  With
+// the table, the greedy head is fused into the next step's layer-0
+// self-attention, and a greedy row's layer-0 history is read from the table
+// too (QkvRows.hist): greedy calls do not touch layer 0's region of the cache.
+static const float* qkv_table(const nd_ctx* c) { return c->m.qtab[c->exact ? 1 : 0]; }
+static bool head_fused(const nd_ctx* c) { return qkv_table(c) && c->V <= 8; }  // SELF_TABV
 
 static nd::NextEmbed next_embed(nd_ctx* c) {
   nd::NextEmbed ne;
@@ -285,28 +284,8 @@ static nd::NextEmbed next_embed(nd_ctx* c) {
   ne.pe = c->cfg.position_encoding ? c->m.pe : nullptr;
   ne.x = c->dx;
   ne.part = c->dx_part;
-  ne.tok = c->qtab ? c->rtok : nullptr;
+  ne.tok = qkv_table(c) ? c->rtok : nullptr;
   return ne;
-}
-
-// QKV0[s][v] = LN(emb[v] (* 16 + pe[s])) W_qkv + b for the S steps of the
-// call: the layer-0 projection of every input a step can see (V of them),
-// through the same split-fp16 GEMM the step would run (decoder/transformer.py:
-// 76-78, the embedding as onmt/modules/embeddings.py:189-207)
-static hipError_t enqueue_qkv_table(nd_ctx* c, int S, hipStream_t s) {
-  if (!c->qtab) return hipSuccess;
-  if (S < 1 || S > c->cfg.max_steps) return hipErrorInvalidValue;
-  const int D = c->D, rows = (S * c->V + 15) / 16 * 16;
-  LCHK(nd::launch_dec_embed_table(c->m.emb, c->cfg.position_encoding ? c->m.pe : nullptr, c->V, S, c->qtab_x,
-                                  c->qtab_part, rows, s));
-  const DecLayer& L = c->m.dec[0];
-  // row-major: the self-attention reads one table row per workgroup (QkvRows.rm)
-  return G(c->qtab_x, D, L.pwqkv, 3 * D, D, L.nbqkv, c->qtab, 3 * D, rows)
-      .p16()
-      .h3(c)
-      .ln(c->qtab_part, 1)
-      .c_rowmajor(true)
-      .run(s);
 }
 
 // Step-0 decoder input (later steps' inputs are written by the search
@@ -391,9 +370,11 @@ static int dec_ffn_splits(const nd_ctx* c, int R) {
 
 // done: per chunk, nonzero = finished (--fast beam; null otherwise): its rows'
 // tiles and attention workgroups exit without work
+// gtok_ld: greedy calls (one row per chunk, no ancestry): the leading dimension of c->gtok, the call's
+// max_len; layer 0 then reads its history from the table by the row's tokens there (0: the cache)
 static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, const int* anc, int anc_ld,
                                    hipStream_t s, const int* done = nullptr, const nd::GreedyHead* head = nullptr,
-                                   const int* clist = nullptr, int ccap = 0) {
+                                   const int* clist = nullptr, int ccap = 0, int gtok_ld = 0) {
   const int R = C * rpc, D = c->D, F = c->F, S = c->cfg.max_steps;
   const int Ld = (int)c->m.dec.size();
   const bool mb = use_memory_bank(c, rpc);
@@ -429,14 +410,18 @@ static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, c
       LCHK(nd::launch_aan_gate(c->ag, c->axn, c->aa, c->dx, c->dq1, c->dq1_part, R, s));
       pnq = 1;
     } else {
-      if (i == 0 && c->qtab) {  // the row's q | k | v from the call's table
+      if (i == 0 && qkv_table(c)) {  // the row's q | k | v from the model's table
         nd::QkvRows qr;
         qr.tok = c->rtok;
         qr.V = c->V;
         qr.tok0 = c->cfg.bos_idx;
-        qr.rm = 1;  // the table is row-major (enqueue_qkv_table)
-        LCHK(nd::launch_dec_self_attention(c->qtab, cache, anc, anc_ld, step, S, c->datt, R, s, rpc, done, qr, head,
-                                           clist, ccap, sq24));
+        qr.rm = 1;  // the table is row-major (model.hip build_qkv_tables)
+        if (gtok_ld > 0 && rpc == 1 && !anc && !done && !clist) {  // greedy rows: the history too
+          qr.hist = c->gtok;
+          qr.hist_ld = gtok_ld;
+        }
+        LCHK(nd::launch_dec_self_attention(qkv_table(c), cache, anc, anc_ld, step, S, c->datt, R, s, rpc, done, qr,
+                                           head, clist, ccap, sq24));
       } else {
         // greedy rows (one workgroup each): q | k | v row-major; beam keeps P16 (its M = 5120 GEMMs
         // take the LDS-tiled route, which writes P16)
@@ -515,7 +500,6 @@ static hipError_t enqueue_greedy(nd_ctx* c, int B, int T, int S, int min_len, bo
   LCHK(enqueue_encode(c, B, T, s));
   LCHK(enqueue_memory(c, B, T, 1, s));
   LCHK(nd::launch_fill_i32(c->tok, c->cfg.bos_idx, B, s));
-  LCHK(enqueue_qkv_table(c, S, s));
   LCHK(enqueue_first_embed(c, B, s));
   const nd::NextEmbed ne = next_embed(c);
   // step k's head runs inside step k + 1's layer-0 self-attention (table
@@ -525,7 +509,7 @@ static hipError_t enqueue_greedy(nd_ctx* c, int B, int T, int S, int min_len, bo
                                                  c->cfg.eos_idx, c->tok, c->gtok, c->gscore,
                                                  logp ? c->glogp : nullptr, ne, smp);
   for (int step = 0; step < S; ++step) {
-    LCHK(enqueue_dec_step(c, B, 1, T, step, nullptr, 0, s, nullptr, fuse && step > 0 ? &hd : nullptr));
+    LCHK(enqueue_dec_step(c, B, 1, T, step, nullptr, 0, s, nullptr, fuse && step > 0 ? &hd : nullptr, nullptr, 0, S));
     if (!fuse || step == S - 1)
       LCHK(nd::launch_dec_greedy_head(c->dx, c->m.dec_ln_g, c->m.dec_ln_b, c->m.gen_w, c->m.gen_b, c->V, step, S, min_len,
                                       c->cfg.eos_idx, c->tok, c->gtok, c->gscore, logp ? c->glogp : nullptr, ne, B,
@@ -864,7 +848,6 @@ static int translate_segmented(nd_ctx* c, const BeamIo& io, GraphKey key, bool t
       LCHK(enqueue_encode(c, B, T, s));
       LCHK(enqueue_memory(c, B, T, beam, s));  // K/V per layer (memory bank at beam 1)
       LCHK(init(s));
-      LCHK(enqueue_qkv_table(c, max_len, s));
       LCHK(enqueue_first_embed(c, B * beam, s));
       LCHK(nd::launch_fill_i32(c->steps_done, max_len, 1, s));
       return hipSuccess;

@@ -148,6 +148,15 @@ struct Model {
   std::map<const float*, std::pair<uint16_t*, float>> split;
   // row-major split images of the P16 step weights (large-M route), keyed by the P16 weight
   std::map<const float*, std::pair<uint16_t*, float>> split_rm;
+  // decoder layer 0's QKV table (kernels.hpp QkvRows; scaled-dot decoders): row step * V + token holds
+  // q | k | v of that input, [round16(qtab_steps * V), 768] row-major, for every step a context may run
+  // (qtab_steps = the owner's max_steps; a call of fewer steps reads a prefix).  It depends on the weights
+  // alone, so nd_finalize builds it once in each product mode a call can run in: [0] through the split-fp16
+  // step GEMM, [1] in exact fp32 (nd_set_exact_fp32 flips between them at run time)
+  float* qtab[2] = {nullptr, nullptr};
+  int qtab_steps = 0;
+  // the table's input rows and their statistics: used while nd_finalize builds it, kept for the next nd_finalize
+  float *qtab_x = nullptr, *qtab_part = nullptr;
 };
 
 struct nd_ctx {
@@ -226,9 +235,7 @@ struct nd_ctx {
   float *dx = nullptr, *dq1 = nullptr, *dmid = nullptr, *dcq = nullptr, *datt = nullptr, *dqkv = nullptr,
         *dhid = nullptr, *cache = nullptr;
   int *tok = nullptr, *gtok = nullptr;
-  // layer-0 QKV table (QkvRows): input rows, their statistics, the table
-  // [round16(max_steps * V), 768] P16, and each row's token of the step
-  float *qtab_x = nullptr, *qtab_part = nullptr, *qtab = nullptr;
+  // each row's token of the step: its row of the layer-0 QKV table (Model.qtab)
   int* rtok = nullptr;
   float *gscore = nullptr, *glogp = nullptr;
   nd::BeamState bs{};

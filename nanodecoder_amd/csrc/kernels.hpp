@@ -189,10 +189,11 @@ hipError_t launch_dec_ffn(const float* y, const uint16_t* w1h, float w1s, const 
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* out, int rows, hipStream_t s);
 
 // ---- decoder -------------------------------------------------------------
-// Layer 0's self-attention reads its row's q | k | v from a per-call table
-// QKV0[step][token] (P16 [S * V, 768]; launch_dec_embed_table + one GEMM)
-// instead of a per-step GEMM: its input LN(emb[tok] * 16 + pe[step]) takes
-// only V values per step.  tok == nullptr: the per-step qkv matrix.
+// Layer 0's self-attention reads its row's q | k | v from the model's table
+// QKV0[step][token] ([S * V, 768]; launch_dec_embed_table + one GEMM, built
+// once at finalize) instead of a per-step GEMM: its input LN(emb[tok] * 16 +
+// pe[step]) takes only V values per step.  tok == nullptr: the per-step qkv
+// matrix.
 struct QkvRows {
   const int* tok = nullptr;  // row -> token of this step (steps > 0)
   int V = 0;
@@ -201,6 +202,13 @@ struct QkvRows {
   // instead of P16: a workgroup reads ONE row, which in P16 is 16 B of every
   // 128 B line (GemmArgs.c_rm)
   int rm = 0;
+  // Table history (greedy rows: one row per chunk, no ancestry, no skip list,
+  // fp32, row-major table): hist[r * hist_ld + t] is row r's token picked at
+  // step t (the greedy head's out_tokens), so key t < step of row r is the
+  // k | v part of table row t * V + (t == 0 ? tok0 : hist[r][t - 1]) and the
+  // kernel neither reads nor writes the cache.  nullptr: the cache.
+  const int* hist = nullptr;
+  int hist_ld = 0;
 };
 // rows s * V + v (s < S, v < V) of the layer-0 QKV table's input, P16, with
 // one row-statistics partial per row; rows S * V .. rows_alloc - 1 zero
@@ -212,7 +220,8 @@ hipError_t launch_dec_embed(const int* tok, const float* emb, const float* pe, i
 // self attention: writes k,v of this step into cache[slot=r][step], attends
 // over the row's history cache[anc[r][t]][t] (anc == nullptr: identity).
 // skip (nullable): per chunk (row / rpc), nonzero = finished, its rows do nothing.
-// head (greedy, table mode, step > 0, no anc / skip): the workgroup of row r first
+// qr.hist (table history, QkvRows): the history comes from the table, the cache is not touched.
+// head (greedy, table history, step > 0): the workgroup of row r first
 // runs the previous step's greedy head for r (its token is this step's input),
 // so the standalone head kernel runs only after the last step
 struct GreedyHead;

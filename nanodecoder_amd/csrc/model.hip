@@ -462,6 +462,46 @@ static int derive_memory_bank_weights(nd_ctx* c) {
   return rc;
 }
 
+// Decoder layer 0's QKV table (Model.qtab): QKV0[s][v] = LN(emb[v] (* 16 + pe[s])) W_qkv + b for every
+// step s < max_steps and token v, the layer-0 projection of every input a step can see, through the same
+// GEMM the step would run (decoder/transformer.py:76-78, the embedding as
+// onmt/modules/embeddings.py:189-207): once on the split-fp16 weight image, once in exact fp32.  Row-major:
+// the self-attention reads whole rows (QkvRows.rm).  Every buffer, the input rows and their statistics
+// included, is allocated once and kept: freeing device memory here (hipMalloc / hipFree of the two scratch
+// buffers) made a split-K context's third and later graph launches return wrong tokens on MI355X.
+static int build_qkv_tables(nd_ctx* c) {
+  if (c->cfg.self_attn_type == ND_SELF_AVERAGE) return ND_OK;
+  const int D = c->D, S = c->cfg.max_steps;
+  const size_t rows = ((size_t)S * c->V + 15) / 16 * 16;
+  Model& m = c->m;
+  for (auto& t : m.qtab)
+    if (!t && dalloc(c, &t, rows * 3 * D) != hipSuccess) return fail(ND_ERR_HIP, "hipMalloc layer-0 QKV table");
+  if (!m.qtab_x && dalloc(c, &m.qtab_x, rows * D) != hipSuccess) return fail(ND_ERR_HIP, "hipMalloc layer-0 QKV table");
+  if (!m.qtab_part && dalloc(c, &m.qtab_part, rows * ND_PART_LD * 2) != hipSuccess)
+    return fail(ND_ERR_HIP, "hipMalloc layer-0 QKV table");
+  m.qtab_steps = S;
+  const bool exact = c->exact;
+  hipError_t e = hipMemsetAsync(m.qtab_x, 0, rows * D * sizeof(float), c->es);
+  if (e == hipSuccess) e = hipMemsetAsync(m.qtab_part, 0, rows * ND_PART_LD * 2 * sizeof(float), c->es);
+  if (e == hipSuccess)
+    e = nd::launch_dec_embed_table(m.emb, c->cfg.position_encoding ? m.pe : nullptr, c->V, S, m.qtab_x, m.qtab_part,
+                                   (int)rows, c->es);
+  const DecLayer& L = m.dec[0];
+  for (int ex = 0; ex < 2 && e == hipSuccess; ++ex) {
+    c->exact = ex != 0;  // G::h3 picks the weight image by it
+    e = G(m.qtab_x, D, L.pwqkv, 3 * D, D, L.nbqkv, m.qtab[ex], 3 * D, (int)rows)
+            .p16()
+            .h3(c)
+            .ln(m.qtab_part, 1)
+            .c_rowmajor(true)
+            .run(c->es);
+  }
+  c->exact = exact;
+  if (e == hipSuccess) e = hipStreamSynchronize(c->es);
+  if (e != hipSuccess) return fail(ND_ERR_HIP, std::string("layer-0 QKV table: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
 int nd_finalize(nd_ctx* c) {
   if (!c) return fail(ND_ERR_ARG, "null ctx");
   std::string missing;
@@ -596,6 +636,7 @@ int nd_finalize(nd_ctx* c) {
   {
     int rc = derive_bank_dim_scales(c);
     if (!rc) rc = derive_memory_bank_weights(c);
+    if (!rc) rc = build_qkv_tables(c);
     if (rc) return rc;
   }
   drop_graphs(c);
@@ -615,6 +656,8 @@ int nd_share_weights(nd_ctx* c, const nd_ctx* src) {
       a.vocab != b.vocab || a.rnn_hidden != b.rnn_hidden || a.position_encoding != b.position_encoding ||
       a.pad_idx != b.pad_idx || a.bos_idx != b.bos_idx || a.eos_idx != b.eos_idx || a.device != b.device)
     return fail(ND_ERR_ARG, "nd_share_weights: the model configurations differ");
+  // the position table and the layer-0 QKV table hold the source's max_steps steps
+  if (a.max_steps > b.max_steps) return fail(ND_ERR_ARG, "nd_share_weights: max_steps exceeds the source context's");
   // every weight pointer and every image nd_finalize derived (struct Model; nothing in it is a workspace).
   // The context's own raw weight buffers from nd_create stay allocated and are never read (a few tens of MB
   // at d_model 256): the derived images -- the split-fp16 and P16 forms, the memory-bank products -- are

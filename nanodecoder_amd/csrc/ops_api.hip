@@ -240,6 +240,24 @@ int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* a
   return ND_OK;
 }
 
+int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int32_t V, const int32_t* tok,
+                                   int32_t tok0, const int32_t* hist, int32_t hist_ld, float* cache, int32_t step,
+                                   int32_t max_steps, float* out, int32_t R, void* stream) {
+  if (!table || !tok || !hist || !out || R < 1 || V < 1 || step < 0 || step >= table_steps)
+    return fail(ND_ERR_ARG, "dec_self_attention_table: bad arguments");
+  nd::QkvRows qr;
+  qr.tok = tok;
+  qr.V = V;
+  qr.tok0 = tok0;
+  qr.rm = 1;
+  qr.hist = hist;
+  qr.hist_ld = hist_ld;
+  hipError_t e = nd::launch_dec_self_attention(table, cache, nullptr, 0, step, max_steps, out, R, (hipStream_t)stream, 1,
+                                               nullptr, qr);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_table: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
 int nd_op_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int32_t* span, float pad_val,
                             float* out, int32_t C, int32_t rpc, int32_t T, int32_t ldT, int32_t grid, void* stream) {
   if (int rc = ensure_attributes()) return rc;

@@ -721,6 +721,23 @@ def op_dec_self_attention_q24(qkv, cache, step, anc=None, rpc=1, done=None):
     return unpack_p16(out, R)
 
 
+def op_dec_self_attention_table(table, V, tok, tok0, hist, step, cache=None, max_steps=None):
+    """The greedy rows' layer-0 self-attention on the QKV table (nd_op_dec_self_attention_table): table
+    [steps * V, 768] row-major, tok int32 [R] each row's token of this step, hist int32 [R, ld] the tokens
+    picked at earlier steps, cache (optional, [R, S, 512]) left untouched; returns out [R, 256] row-major."""
+    R = tok.shape[0]
+    steps = table.shape[0] // V
+    S = max_steps if max_steps is not None else (cache.shape[1] if cache is not None else steps)
+    if int(tok.min()) < 0 or int(tok.max()) >= V or int(hist.min()) < 0 or int(hist.max()) >= V:
+        raise ValueError("token out of range [0, V)")
+    out = torch.empty((R + 15) // 16 * 16, 256, dtype=torch.float32, device=table.device)
+    s = ctypes.c_void_p(torch.cuda.current_stream(table.device).cuda_stream)
+    _lib.check(_lib.lib().nd_op_dec_self_attention_table(_ptr(table), steps, V, _ptr(tok), tok0, _ptr(hist),
+                                                         hist.shape[1], _ptr(cache), step, S, _ptr(out), R, s),
+               "nd_op_dec_self_attention_table")
+    return unpack_p16(out, R)
+
+
 def op_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, rpc, packed=False):
     """q [C*rpc, 256] row-major (or P16-packed with packed=True); returns out
     in the same convention."""
