@@ -199,6 +199,23 @@ int nd_translate_beam_classic_ex(nd_ctx* ctx, const float* d_signal, const int32
                                  int32_t* d_tokens, float* d_scores, int32_t* d_lens, int32_t* d_steps, float* d_attn,
                                  void* stream);
 
+/* Teacher-forced scoring: replaces Translator._score_target (translate/translator.py:928-941): one
+ * causally masked decoder pass over every position of every target, captured in one hipGraph.
+ *   d_gold     [B, L] i32: the gold row of each chunk, tgt[1:] in the reference's terms:
+ *              its tokens followed by EOS, then pad_idx
+ *   d_gold_len [B] i32 in [1, L]: tokens counted, EOS included
+ *   d_score    [B] f32: sum over i < gold_len of logp[i][gold[i]]
+ *   d_tok_logp nullable [B, L] f32: the summands (0 at i >= gold_len)
+ *   d_logp     nullable [B, L, V] f32: every position's log-probs (rows i >= gold_len unspecified)
+ * L <= max_steps, B <= max_batch, T <= max_src_len (ND_ERR_ARG otherwise); an ND_SELF_AVERAGE decoder is
+ * refused with ND_ERR_ARG (teacher-forced average attention is a cumulative mean, not built).  Token ids
+ * outside [0, vocab) are clamped, never read out of bounds; the caller validates them.  The [B * L, .]
+ * workspaces (and, on a context created with max_beam 1, the per-layer context K/V) are allocated by the
+ * first call.  Honours nd_set_graphs, nd_set_exact_fp32 and nd_take_overflow like the translate calls. */
+int nd_score_targets(nd_ctx* ctx, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                     const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
+                     float* d_score, float* d_tok_logp, float* d_logp, void* stream);
+
 /* Signal front end (utils/labelop.py:194-243, extract_fast5_raw): R raw
  * reads concatenated in d_raw (float64, read r at d_offsets[r] ..
  * d_offsets[r+1]) normalised per read into d_out (float32, same offsets).
@@ -594,6 +611,16 @@ int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int
                                  const float* signal, const int32_t* span, float pad_val, float* out, int32_t C,
                                  int32_t rpc, int32_t T, const int32_t* clist, int32_t ccap, int32_t nsplit,
                                  float* part, const int32_t* done, void* stream);
+
+/* The scoring pass's attention (score.hip tf_attention_kernel), fp32, 8 heads of 32: Lq query rows per
+ * chunk (row c * Lq + i of q, pitch ldq floats) over the chunk's Lk key rows (row c * Lk + t of kv, pitch
+ * ldkv; K at column koff, V at column voff); out [B * Lq, 256] row-major.  causal != 0: keys j <= i
+ * (Lq == Lk; signal and span unused, may be null).  causal == 0: keys t < span[c], those with
+ * signal[c * Lk + t] == pad_val filled with -1e18 (multi_headed_attn.py:142-177), as
+ * nd_op_dec_ctx_attention. */
+int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
+                       const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
+                       int32_t Lk, int32_t causal, void* stream);
 
 #ifdef __cplusplus
 }

@@ -54,6 +54,8 @@ SIGNATURES = {
     "nd_translate_beam_classic": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _I, _P, _P, _P, _P, _P]),
     "nd_translate_beam_classic_ex": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, ctypes.POINTER(NdClassicOpts), _I,
                                           _I, _P, _P, _P, _P, _P, _P]),
+    "nd_score_targets": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "nd_op_tf_attention": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
     "nd_normalize_reads": (_I, [_P, _P, _I, _I, _P, _P]),
     "nd_window_reads": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "nd_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),

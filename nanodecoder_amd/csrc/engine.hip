@@ -1000,6 +1000,111 @@ int nd_translate_beam_classic_ex(nd_ctx* c, const float* d_signal, const int32_t
                            d_tokens, d_scores, d_lens, d_steps, d_attn, stream);
 }
 
+// ------------------------------------------------------- teacher-forced scoring
+// The scoring call's workspaces, made by the first call (a context that never scores pays nothing): the
+// per-layer context K/V when the context has none (alloc_ctx_kv, as nd_set_ctx_path(1) does) and the
+// [max_batch * max_steps, .] decoder rows.
+static int alloc_score_ws(nd_ctx* c) {
+  int rc = alloc_ctx_kv(c);
+  if (rc != ND_OK) return rc;
+  if (c->tf_score) return ND_OK;  // allocated last
+  const auto& cfg = c->cfg;
+  const size_t B = cfg.max_batch, S = cfg.max_steps, D = c->D, F = c->F;
+  const size_t M = (B * S + 255) / 256 * 256;  // whole GEMM row tiles
+  hipError_t e;
+#define WST(ptr, n)                                       \
+  if ((e = dalloc(c, &(ptr), (size_t)(n))) != hipSuccess) \
+    return fail(ND_ERR_HIP, std::string("hipMalloc scoring workspace " #ptr ": ") + hipGetErrorString(e));
+  WST(c->tf_x, M * D);
+  WST(c->tf_q1, M * D);
+  WST(c->tf_mid, M * D);
+  WST(c->tf_cq, M * D);
+  WST(c->tf_att, M * D);
+  // q | k | v, then the FFN hidden: the encoder's `big` (free once the context K/V are projected) when it
+  // holds max_batch * max_steps rows
+  if (cfg.max_steps <= cfg.max_src_len) {
+    c->tf_big = c->big;
+  } else {
+    WST(c->tf_big, M * std::max(F, 3 * D));
+  }
+  WST(c->tf_x_part, M * ND_PART_LD * 2);
+  WST(c->tf_q1_part, M * ND_PART_LD * 2);
+  WST(c->tf_mid_part, M * ND_PART_LD * 2);
+  WST(c->tf_gold, B * S);
+  WST(c->tf_gold_len, B);
+  WST(c->tf_tok_logp, B * S);
+  WST(c->tf_logp, B * S * (size_t)c->V);
+  WST(c->tf_score, B);
+#undef WST
+  return ND_OK;
+}
+
+// Encoder, fp32 context K/V of every layer, then the decoder over the M = B * L target rows at once
+// (decoder/transformer.py:53-95 with step = None): the row-major GEMMs of the encoder side (split-fp16
+// images of the decoder's fp32 weights, or fp32 MFMA in exact mode: the same G calls) around the two
+// attentions of score.hip; the FFN is the two GEMMs (its hidden in tf_big), in both product modes.
+static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, bool want_logp, hipStream_t s) {
+  const Model& m = c->m;
+  const int M = B * L, D = c->D, F = c->F, Ld = (int)m.dec.size();
+  const float pad = (float)c->cfg.pad_idx;
+  LCHK(enqueue_encode(c, B, T, s));
+  LCHK(enqueue_ctxkv(c, B, T, s, false));
+  LCHK(nd::launch_tf_embed(c->tf_gold, c->cfg.bos_idx, c->V, m.emb, c->cfg.position_encoding ? m.pe : nullptr, c->tf_x,
+                           c->tf_x_part, B, L, s));
+  int pnx = 1, pnq = 0, pnm = 0;
+  for (int i = 0; i < Ld; ++i) {
+    const DecLayer& Y = m.dec[i];
+    LCHK(G(c->tf_x, D, Y.nwqkv, 3 * D, D, Y.nbqkv, c->tf_big, 3 * D, M).h3(c).ln(c->tf_x_part, pnx).run(s));
+    LCHK(nd::launch_tf_attention(c->tf_big, 3 * D, c->tf_big, 3 * D, D, 2 * D, nullptr, nullptr, 0.f, c->tf_att, B, L, L,
+                                 true, s));
+    LCHK(G(c->tf_att, D, Y.wo, D, D, Y.bo, c->tf_q1, D, M).h3(c).res(c->tf_x, D).stats(c->tf_q1_part).run(s, &pnq));
+    LCHK(G(c->tf_q1, D, Y.ncwq, D, D, Y.ncbq, c->tf_cq, D, M).h3(c).ln(c->tf_q1_part, pnq).run(s));
+    LCHK(nd::launch_tf_attention(c->tf_cq, D, c->ctxkv, Ld * 2 * D, i * 2 * D, i * 2 * D + D, c->sig, c->span, pad,
+                                 c->tf_att, B, L, T, false, s));
+    LCHK(G(c->tf_att, D, Y.cwo, D, D, Y.cbo, c->tf_mid, D, M).h3(c).res(c->tf_q1, D).stats(c->tf_mid_part).run(s, &pnm));
+    LCHK(G(c->tf_mid, D, Y.nw1, F, D, Y.nb1, c->tf_big, F, M).h3(c).ln(c->tf_mid_part, pnm).relu().run(s));
+    LCHK(G(c->tf_big, F, Y.w2, D, F, Y.b2, c->tf_x, D, M).h3(c).res(c->tf_mid, D).stats(c->tf_x_part).run(s, &pnx));
+  }
+  return nd::launch_score_head(c->tf_x, m.dec_ln_g, m.dec_ln_b, m.gen_w, m.gen_b, c->V, c->tf_gold, c->tf_gold_len, B, L,
+                               c->tf_score, want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s);
+}
+
+int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                     const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L, float* d_score,
+                     float* d_tok_logp, float* d_logp, void* stream) {
+  // every argument check comes before the first HIP call
+  if (!c) return fail(ND_ERR_ARG, "null ctx");
+  if (c->cfg.self_attn_type == ND_SELF_AVERAGE)
+    return fail(ND_ERR_ARG, "nd_score_targets: average-attention decoders are not supported (teacher-forced average "
+                            "attention is a cumulative mean, a kernel this library does not have)");
+  if (L < 1 || L > c->cfg.max_steps) return fail(ND_ERR_ARG, "nd_score_targets: L out of range [1, max_steps]");
+  int rc = check_call(c, B, T, L);
+  if (rc) return rc;
+  if (!d_signal || !d_len || !d_span || !d_gold || !d_gold_len || !d_score) return fail(ND_ERR_ARG, "null buffer");
+  HIPCHK(hipSetDevice(c->cfg.device));
+  if ((rc = alloc_score_ws(c))) return rc;
+  hipStream_t cs = (hipStream_t)stream;
+  if ((rc = stage_inputs(c, d_signal, d_len, d_span, B, T, cs))) return rc;
+  HIPCHK(hipMemcpyAsync(c->tf_gold, d_gold, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
+  HIPCHK(hipMemcpyAsync(c->tf_gold_len, d_gold_len, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
+  const bool tl = d_tok_logp != nullptr, lp = d_logp != nullptr;
+  GraphKey key;
+  key.mode = 3;
+  key.B = B;
+  key.T = T;
+  key.S = L;
+  key.logp = (tl ? 1 : 0) | (lp ? 2 : 0);
+  {
+    const CallFlags flags(c, false);
+    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_score(c, B, T, L, tl, lp, s); });
+  }
+  if (rc) return rc;
+  HIPCHK(hipMemcpyAsync(d_score, c->tf_score, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
+  if (tl) HIPCHK(hipMemcpyAsync(d_tok_logp, c->tf_tok_logp, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
+  if (lp) HIPCHK(hipMemcpyAsync(d_logp, c->tf_logp, (size_t)B * L * c->V * 4, hipMemcpyDeviceToDevice, c->es));
+  return release_to(c, cs);
+}
+
 int nd_encode(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span, int32_t B, int32_t T,
               float* d_memory, void* stream) {
   int rc = check_call(c, B, T, 1);

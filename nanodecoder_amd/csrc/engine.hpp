@@ -95,10 +95,10 @@ struct NanoLayer {
 
 // What a captured graph depends on.  Callers fill the fields by name; every field takes part in the order.
 struct GraphKey {
-  int mode = 0;  // 0 greedy / sampling, 1 --fast beam, 2 classic beam
+  int mode = 0;  // 0 greedy / sampling, 1 --fast beam, 2 classic beam, 3 teacher-forced scoring (S = L)
   int B = 0, T = 0, S = 0, min_len = 0, beam = 1, n_best = 1;
   int seg = 0;   // beam: first step of the segment, -1 = the prologue (encoder, memory, init)
-  int logp = 0;  // greedy: per-step log-probabilities kept
+  int logp = 0;  // greedy: per-step log-probabilities kept; scoring: bit 0 tok_logp, bit 1 logp kept
   float alpha = 0.f;
   int stamp = 0;  // kernel stamps on (set by run_graph from the ctx)
   // attention capture and the classic Beam's options
@@ -246,6 +246,14 @@ struct nd_ctx {
   // -attn_debug / coverage: [decoder rows][max_steps][max_src_len] head-0 context scores -> probabilities
   float* attn_raw = nullptr;
   int* h_alive = nullptr;  // pinned
+  // teacher-forced scoring (nd_score_targets), made on first use: the [max_batch * max_steps, .] row-major
+  // decoder rows x / q1 / mid / cq / att with their row statistics, q | k | v and the FFN hidden (tf_big: the
+  // encoder's `big` when max_steps <= max_src_len, the encoder being done with it), the staged gold rows
+  // and the results
+  float *tf_x = nullptr, *tf_q1 = nullptr, *tf_mid = nullptr, *tf_cq = nullptr, *tf_att = nullptr, *tf_big = nullptr;
+  float *tf_x_part = nullptr, *tf_q1_part = nullptr, *tf_mid_part = nullptr;
+  int *tf_gold = nullptr, *tf_gold_len = nullptr;
+  float *tf_score = nullptr, *tf_tok_logp = nullptr, *tf_logp = nullptr;
 
   hipStream_t es = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;

@@ -411,4 +411,23 @@ hipError_t launch_attn_step_softmax(float* a, size_t ld, const int* span, int R,
 hipError_t launch_beam_attn_gather(const BeamState& st, int C, int n_best, int S, int max_len, int T, float* out,
                                    hipStream_t s);
 
+// ---- teacher-forced scoring (score.hip) ------------------------------------
+// x[c*L + i][:] = emb[i == 0 ? bos : gold[c][i-1]] (* 16 + pe[i] with position encoding; the token clamped
+// into [0, V)), row-major, and the row's statistics in one partial (part, ND_PART_LD slots per row)
+hipError_t launch_tf_embed(const int* gold, int bos, int V, const float* emb, const float* pe, float* x, float* part,
+                           int B, int L, hipStream_t s);
+// fp32 attention of Lq query rows per chunk (row c*Lq + i of q, pitch ldq, head h at column 32 h) over the
+// chunk's Lk key rows (row c*Lk + t of kv, pitch ldkv; K at column koff, V at voff): out [B*Lq, 256].
+// causal: keys j <= i (Lq == Lk; signal, span unused).  Otherwise keys t < span[c], those with
+// signal[c*Lk + t] == pad_val filled with ND_MASK_FILL (launch_dec_ctx_attention's masks).
+hipError_t launch_tf_attention(const float* q, int ldq, const float* kv, int ldkv, int koff, int voff,
+                               const float* signal, const int* span, float pad_val, float* out, int B, int Lq, int Lk,
+                               bool causal, hipStream_t s);
+// per row c*L + i of x (row-major): LN_dec -> generator -> log_softmax; tok_logp[c][i] (nullable) =
+// logp[gold[c][i]] for i < gold_len[c], else 0; score[c] = their sum in a fixed order; logp (nullable)
+// [B, L, V] every row's log-probabilities.  L <= 512, V <= 32.
+hipError_t launch_score_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
+                             int V, const int* gold, const int* gold_len, int B, int L, float* score, float* tok_logp,
+                             float* logp, hipStream_t s);
+
 }  // namespace nd

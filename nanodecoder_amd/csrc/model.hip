@@ -629,6 +629,17 @@ int nd_finalize(nd_ctx* c) {
       }
     }
     HIPCHK(mk(c->cfg.encoder_type == ND_ENC_TRANSFORMER ? c->m.nctxkv_w : c->m.ctxkv_w, L2, D));
+    // teacher-forced scoring (engine.hip enqueue_score) runs the decoder's fp32 row-major weights over
+    // B * L rows on the same GEMMs
+    if (c->cfg.self_attn_type != ND_SELF_AVERAGE)
+      for (auto& L : c->m.dec) {
+        HIPCHK(mk(L.nwqkv, 3 * D, D));
+        HIPCHK(mk(L.wo, D, D));
+        HIPCHK(mk(L.ncwq, D, D));
+        HIPCHK(mk(L.cwo, D, D));
+        HIPCHK(mk(L.nw1, F, D));
+        HIPCHK(mk(L.w2, D, F));
+      }
     for (size_t l = 1; l < c->m.nano.size(); ++l) HIPCHK(mk(c->m.nano[l].wih, 8 * c->H, 2 * c->H));
     if (c->m.nano_W) HIPCHK(mk(c->m.nano_W, D, 2 * c->H));
     HIPCHK(hipStreamSynchronize(c->es));

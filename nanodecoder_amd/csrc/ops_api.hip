@@ -333,6 +333,15 @@ int nd_op_dec_ctx_attention(const float* q, const float* kv, int32_t ld, int32_t
   return ND_OK;
 }
 
+int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
+                       const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
+                       int32_t Lk, int32_t causal, void* stream) {
+  hipError_t e = nd::launch_tf_attention(q, ldq, kv, ldkv, koff, voff, signal, span, pad_val, out, B, Lq, Lk,
+                                         causal != 0, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("tf_attention: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
 int nd_op_ctx_pack_q24(const float* kv, int32_t ld, int32_t layers, void* out, const int32_t* span, int32_t B,
                        int32_t T, void* stream) {
   if (!kv || !out || !span) return fail(ND_ERR_ARG, "ctx_pack_q24: bad arguments");

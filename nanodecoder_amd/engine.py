@@ -281,6 +281,31 @@ class Engine:
             out["attn"] = att
         return out
 
+    def score_targets(self, signal, lengths, spans=None, gold=None, gold_len=None, return_tok_logp: bool = False,
+                      return_logp: bool = False):
+        """Teacher-forced scoring (nd_score_targets; Translator._score_target, translator.py:928-941): one
+        decoder pass over every position of every target.  gold [B, L] int32: each chunk's tokens followed
+        by EOS, then pad_idx; gold_len [B] in [1, L]: tokens counted, EOS included.  Returns dict(scores [B]
+        f32 = sum over i < gold_len of logp[i][gold[i]], tok_logp [B, L] or None: the summands (0 at
+        i >= gold_len), logp [B, L, V] or None (rows i >= gold_len unspecified), overflow)."""
+        if self.cfg.self_attn_type == "average":
+            raise NotImplementedError("score_targets: average-attention decoders are not supported")
+        signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
+        if gold is None or gold_len is None:
+            raise ValueError("score_targets needs gold and gold_len")
+        gold = torch.as_tensor(gold).to(self.device, torch.int32, non_blocking=True).contiguous()
+        gold_len = torch.as_tensor(gold_len).to(self.device, torch.int32, non_blocking=True).contiguous()
+        if gold.dim() != 2 or gold.shape[0] != B or gold_len.shape != (B,):
+            raise ValueError("gold must be [B, L] and gold_len [B]")
+        L = gold.shape[1]
+        sc = torch.empty(B, dtype=torch.float32, device=self.device)
+        tl = torch.empty(B, L, dtype=torch.float32, device=self.device) if return_tok_logp else None
+        lp = torch.empty(B, L, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logp else None
+        _lib.check(self._L.nd_score_targets(self._h, _ptr(signal), _ptr(lengths), _ptr(spans), _ptr(gold),
+                                            _ptr(gold_len), B, T, L, _ptr(sc), _ptr(tl), _ptr(lp), self._stream()),
+                   "nd_score_targets")
+        return dict(scores=sc, tok_logp=tl, logp=lp, overflow=self._take_overflow())
+
     def encode(self, signal, lengths, spans=None):
         """Memory bank [B, T, d] of the encoder (rows >= span unspecified)."""
         signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
@@ -401,6 +426,12 @@ class EnginePool:
 
     def translate_beam_classic(self, signal, lengths, spans=None, **kw):
         return self._call("translate_beam_classic", signal, lengths, spans, **kw)
+
+    def score_targets(self, signal, lengths, spans=None, **kw):
+        r = self._call("score_targets", signal, lengths, spans, **kw)
+        # the gold rows stay referenced like the other inputs (see _call)
+        self._held[r["lane"]] = r["inputs"] = r["inputs"] + (kw.get("gold"), kw.get("gold_len"))
+        return r
 
     def encode(self, signal, lengths, spans=None):
         """Engine.encode on the next lane's context, joined to the current
@@ -749,6 +780,20 @@ def op_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, rpc, packed=Fal
     _lib.check(_lib.lib().nd_op_dec_ctx_attention(_ptr(qp), _ptr(kv), ld, koff, _ptr(signal), _ptr(span), float(pad_val),
                                                   _ptr(out), C, rpc, T, s), "nd_op_dec_ctx_attention")
     return out if packed else unpack_p16(out, R)
+
+
+def op_tf_attention(q, kv, B, Lq, Lk, koff, voff, causal, signal=None, span=None, pad_val=0.0):
+    """The scoring pass's attention (nd_op_tf_attention): q [B*Lq, ldq] and kv [B*Lk, ldkv] row-major (K at
+    column koff, V at voff; q and kv may be one q | k | v buffer), causal (keys j <= i, Lq == Lk) or over
+    keys t < span[c] with signal [B, Lk] == pad_val masked; returns out [B*Lq, 256]."""
+    out = torch.empty(B * Lq, 256, dtype=torch.float32, device=q.device)
+    if span is not None:
+        span = span.to(torch.int32)
+    s = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+    _lib.check(_lib.lib().nd_op_tf_attention(_ptr(q), q.shape[1], _ptr(kv), kv.shape[1], koff, voff, _ptr(signal),
+                                             _ptr(span), float(pad_val), _ptr(out), B, Lq, Lk, int(causal), s),
+               "nd_op_tf_attention")
+    return out
 
 
 CTXQ_ROW = 1600  # bytes per (key row, layer) of the 24-bit context K/V image (kernels.hpp)

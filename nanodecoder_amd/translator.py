@@ -138,6 +138,7 @@ class Translator(object):
                 engine = Engine(cfg, weights, **kw)
         self.engine = engine
         self._pinned, self._pin_i = None, 0
+        self.last_gold_scores = None  # per-chunk gold scores of the last translate(src, tgt=...)
 
     def _check_supported(self):
         if self.beam_size == 1:
@@ -384,15 +385,112 @@ class Translator(object):
             words.append(w)
         return words
 
+    # --------------------------------------------------------------- gold scoring
+    def _gold_ids(self, target) -> List[int]:
+        """One target as token ids without EOS: a token string ("A C G T"; words outside the vocabulary
+        become <unk>, as torchtext maps them) or a sequence of ids.  ValueError for an id outside the
+        vocabulary, for pad / BOS / EOS inside the sequence, and for more tokens than max_steps - 1."""
+        cfg = self.cfg
+        if isinstance(target, str):
+            ids = [cfg.itos.index(w) if w in cfg.itos else cfg.unk_idx for w in target.split()]
+        else:
+            ids = [int(t) for t in np.asarray(target).reshape(-1).tolist()]
+        for t in ids:
+            if t < 0 or t >= cfg.vocab:
+                raise ValueError(f"target token id {t} outside the vocabulary [0, {cfg.vocab})")
+            if t in (cfg.pad_idx, cfg.bos_idx, cfg.eos_idx):
+                raise ValueError(f"target holds the special token {cfg.itos[t]!r}: pass the bases only "
+                                 "(BOS and EOS are added here)")
+        if len(ids) > self.engine.max_steps - 1:
+            raise ValueError(f"target of {len(ids)} tokens is longer than max_steps - 1 = "
+                             f"{self.engine.max_steps - 1}")
+        return ids
+
+    def score(self, chunks, targets, batch_size):
+        """Teacher-forced scores of given target sequences (Translator._score_target,
+        translate/translator.py:928-941): per chunk (score, tok_logp list), score = the sum of the target's
+        token log-probabilities, EOS (appended here) included, tok_logp = the summands.  ``targets``: one
+        token string or id sequence per chunk (see _gold_ids).  Each chunk keeps the span of its reference
+        batch (consecutive ``batch_size`` chunks), exactly as stream_reads assigns it."""
+        if batch_size is None:
+            raise ValueError("batch_size must be set")
+        chunks = [parse_chunk(c) for c in chunks]
+        if len(chunks) != len(targets):
+            raise ValueError("one target per chunk")
+        ids = [self._gold_ids(t) for t in targets]
+        if self.cfg.self_attn_type == "average":
+            raise NotImplementedError("scoring targets is not supported for average-attention decoders")
+        spans = []
+        for b0 in range(0, len(chunks), batch_size):
+            part = chunks[b0: b0 + batch_size]
+            spans += [max(len(c) for c in part)] * len(part)
+        out, cap = [], self.engine.max_batch
+        for b0 in range(0, len(chunks), cap):
+            out += self._score_batch(chunks[b0: b0 + cap], spans[b0: b0 + cap], ids[b0: b0 + cap])
+        return out
+
+    def _score_batch(self, chunks, spans, ids, exact: bool = False):
+        """One engine batch of score(): stage, call, collect on the host."""
+        n = len(chunks)
+        lens = np.array([len(c) for c in chunks], np.int32)
+        if (lens < 1).any():
+            raise ValueError("empty signal chunk")
+        spans = np.asarray(spans, np.int32)
+        if spans.max() > self.engine.max_src_len:
+            raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
+        T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
+        B = _bucket(n, self.engine.max_batch)
+        # target rows padded to a multiple of 8 positions (one captured graph per (B, T, L); the padding
+        # positions add exactly 0)
+        L = min(self.engine.max_steps, (max(len(t) for t in ids) + 1 + 7) // 8 * 8)
+        sig, ln, sp, dev_in = self._stage(B, T)
+        for i, c in enumerate(chunks):
+            sig[i, : len(c)] = c
+        ln[:n], sp[:n] = lens, spans
+        if dev_in is not None:
+            sig, ln, sp = dev_in
+        gold = np.full((B, L), self.cfg.pad_idx, np.int32)
+        gold_len = np.ones(B, np.int32)
+        gold[:, 0] = self.cfg.eos_idx  # the engine's padding rows score a lone EOS
+        for i, t in enumerate(ids):
+            gold[i, : len(t)] = t
+            gold[i, len(t)] = self.cfg.eos_idx
+            gold_len[i] = len(t) + 1
+        r = self.engine.score_targets(sig, ln, sp, gold=torch.from_numpy(gold), gold_len=torch.from_numpy(gold_len),
+                                      return_tok_logp=True)
+        if "event" in r:
+            r["event"].synchronize()
+        ov = r.get("overflow")
+        if ov is not None and int(ov.cpu().reshape(-1)[0]) != 0 and not exact:
+            # split-fp16 range guard: the batch again with every product in exact fp32 (see _rerun_exact)
+            self.engine.set_exact_fp32(True)
+            try:
+                return self._score_batch(chunks, spans, ids, exact=True)
+            finally:
+                self.engine.set_exact_fp32(False)
+        sc, tl = r["scores"].cpu().numpy(), r["tok_logp"].cpu().numpy()
+        return [(float(sc[i]), tl[i, : gold_len[i]].tolist()) for i in range(n)]
+
     def translate(self, src, tgt=None, src_dir=None, batch_size=None, attn_debug=False):
         """translate/translator.py:181-369.  Returns (all_scores,
-        all_predictions): per chunk, n_best scores and n_best strings."""
+        all_predictions): per chunk, n_best scores and n_best strings.  With ``tgt`` (one target per chunk,
+        see score) the gold scores are computed too (Translator._score_target): kept per chunk on
+        ``last_gold_scores`` and, with -verbose, logged as GOLD / GOLD SCORE after PRED SCORE
+        (translate/translation.py:147-150)."""
         assert src is not None
         if batch_size is None:
             raise ValueError("batch_size must be set")
         chunks = [parse_chunk(c) for c in src]
-        res = self.translate_reads([chunks], batch_size=batch_size, attn_debug=attn_debug)[0]
-        return res
+        if tgt is None:
+            return self.translate_reads([chunks], batch_size=batch_size, attn_debug=attn_debug)[0]
+        tgt = list(tgt)
+        gold = self.score(chunks, tgt, batch_size)
+        self.last_gold_scores = [g[0] for g in gold]
+        sents = [t if isinstance(t, str) else " ".join(self.cfg.itos[i] for i in self._gold_ids(t)) for t in tgt]
+        results = [None]
+        for ri, res in self.stream_reads([chunks], batch_size, attn_debug):
+            results[ri] = res
+        return self._report(results, attn_debug, gold=list(zip(sents, self.last_gold_scores)))[0]
 
     def _write_attn(self, chunk: np.ndarray, sent: List[str], attn: np.ndarray):
         """translate/translator.py:285-336: the source samples and the
@@ -482,10 +580,11 @@ class Translator(object):
             results[ri] = res
         return self._report(results, False)
 
-    def _report(self, results, attn_debug: bool):
+    def _report(self, results, attn_debug: bool, gold=None):
         """Per read (all_scores, all_predictions) from per-chunk results, with
         the reference's verbose / -dump_beam / report_score side outputs
-        (translate/translator.py:255-369)."""
+        (translate/translator.py:255-369).  gold (translate with tgt): per chunk
+        in order (gold sentence, gold score), logged after PRED SCORE."""
         ret = []
         counter = 0
         pred_score_total, pred_words_total = 0.0, 0
@@ -505,6 +604,9 @@ class Translator(object):
                     msg = "\nSENT {}: {}\n".format(counter, None) + \
                           "PRED {}: {}\n".format(counter, " ".join(sents[0])) + \
                           "PRED SCORE: {:.4f}\n".format(scores[0])
+                    if gold is not None:  # translation.py:147-150
+                        msg += "GOLD {}: {}\n".format(counter, gold[counter - 1][0]) + \
+                               "GOLD SCORE: {:.4f}\n".format(gold[counter - 1][1])
                     if len(sents) > 1:
                         msg += "\nBEST HYP:\n" + "".join("[{:.4f}] {}\n".format(sc, s)
                                                          for sc, s in zip(scores, sents))
