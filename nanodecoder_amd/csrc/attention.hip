@@ -1246,98 +1246,67 @@ dec_self_attention_beam_kernel(const float* __restrict__ qkv, float* __restrict_
   merge_waves<RPC, NW>(accs, ms, ls, m, l, acc, wave, lane, tid, out, c * RPC);
 }
 
-// the chunk-per-workgroup form for rpc beam rows (ancestry, no fused head)
-static bool use_self_beam(const int* anc, int rpc, const GreedyHead* head) { return anc && rpc >= 2 && !head; }
+// The forms of dec_self_attention_kernel, as the bits of its template switches: the six the kernel's
+// static_asserts allow, each at the four (NW, KW) shapes.
+enum SelfForm { SELF_PLAIN = 0, SELF_ANC = 1, SELF_PLAIN_Q24 = 4, SELF_ANC_Q24 = 5, SELF_TAB = 8, SELF_HEAD = 10 };
 
-hipError_t launch_dec_self_attention(const float* qkv, float* cache, const int* anc, int anc_ld, int step,
-                                     int max_steps, float* out, int R, hipStream_t s, int rpc, const int* skip,
-                                     const QkvRows& qr, const GreedyHead* head, const int* clist, int ccap,
-                                     bool q24) {
-  if (use_self_beam(anc, rpc, head) && R % rpc == 0) {
-    if (qr.tok && (qr.V < 1 || qr.tok0 < 0 || qr.tok0 >= qr.V)) return hipErrorInvalidValue;
-    if (clist && (ccap < 1 || (long)ccap * rpc > R)) return hipErrorInvalidValue;
-    if (step >= max_steps || step >= SELF_MAXS) return hipErrorInvalidValue;
-    const int grid = clist ? ccap : R / rpc;
-    const bool lng = step >= 4 * 64;  // keys past the first slot table (4 waves x 64 lanes)
-    switch (rpc) {
-#define ND_SELFB2(RP, Q, L)                                                                                       \
-  hipLaunchKernelGGL((dec_self_attention_beam_kernel<RP, 4, Q, L>), dim3(grid), dim3(4 * 64), 0, s, qkv, cache,    \
-                     anc, anc_ld, step, max_steps, out, skip, qr, clist)
-#define ND_SELFB(RP)                    \
-  case RP:                              \
-    if (q24 && !lng)                    \
-      ND_SELFB2(RP, true, false);       \
-    else if (q24)                       \
-      ND_SELFB2(RP, true, true);        \
-    else if (!lng)                      \
-      ND_SELFB2(RP, false, false);      \
-    else                                \
-      ND_SELFB2(RP, false, true);       \
-    break;
-      ND_SELFB(2)
-      ND_SELFB(3)
-      ND_SELFB(4)
-      ND_SELFB(5)
-      ND_SELFB(6)
-      ND_SELFB(7)
-      ND_SELFB(8)
-#undef ND_SELFB
-#undef ND_SELFB2
-      default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
+hipError_t launch_dec_self_attention(const SelfAttnArgs& a, hipStream_t s) {
+  const QkvRows& qr = a.qr;
+  const RowSet& rs = a.rows;
+  const int R = a.R, step = a.step;
   if (qr.tok && (qr.V < 1 || qr.tok0 < 0 || qr.tok0 >= qr.V)) return hipErrorInvalidValue;
+  if (rs.clist && (rs.ccap < 1 || (long)rs.ccap * rs.rpc > R || a.head)) return hipErrorInvalidValue;
+  if (step >= a.max_steps || step >= SELF_MAXS) return hipErrorInvalidValue;
+  // the chunk-per-workgroup form for rpc beam rows (ancestry, no fused head)
+  if (a.anc && rs.rpc >= 2 && !a.head && R % rs.rpc == 0) {
+    const int grid = rs.clist ? rs.ccap : R / rs.rpc;
+    const bool lng = step >= 4 * 64;  // keys past the first slot table (4 waves x 64 lanes)
+    const bool ok = pick_form<8, 7, 6, 5, 4, 3, 2>(rs.rpc, [&](auto RP) {
+      pick_form<1, 0, 3, 2>(2 * a.q24 + lng, [&](auto QL) {
+        constexpr int ql = decltype(QL)::value;
+        hipLaunchKernelGGL((dec_self_attention_beam_kernel<decltype(RP)::value, 4, (ql & 2) != 0, (ql & 1) != 0>),
+                           dim3(grid), dim3(4 * 64), 0, s, a.qkv, a.cache, a.anc, a.anc_ld, step, a.max_steps, a.out,
+                           rs.done, qr, rs.clist);
+      });
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+  }
   // table history: greedy rows on the row-major table; keys up to step - 1 need hist[r][0 .. step - 2]
   const bool tab = qr.hist != nullptr;
-  if (tab && (!qr.tok || !qr.rm || anc || skip || clist || rpc != 1 || q24 || qr.hist_ld < 1 || qr.hist_ld < step - 1))
+  if (tab && (!qr.tok || !qr.rm || a.anc || rs.done || rs.clist || rs.rpc != 1 || a.q24 || qr.hist_ld < 1 ||
+              qr.hist_ld < step - 1))
     return hipErrorInvalidValue;
-  if (head) {
-    if (!tab || step < 1 || head->V != qr.V || head->V > SELF_TABV || head->S > max_steps ||
-        head->out_tokens != qr.hist || head->S != qr.hist_ld)
+  if (a.head) {
+    if (!tab || step < 1 || a.head->V != qr.V || a.head->V > SELF_TABV || a.head->S > a.max_steps ||
+        a.head->out_tokens != qr.hist || a.head->S != qr.hist_ld)
       return hipErrorInvalidValue;
-    const hipError_t e = check_greedy_head(*head);
+    const hipError_t e = check_greedy_head(*a.head);
     if (e != hipSuccess) return e;
   }
-  const GreedyHead hd = head ? *head : GreedyHead();
-  const int skip_rpc = rpc;
-  if (rpc < 2 || R % (8 * rpc)) rpc = 1;
-  if (clist && (ccap < 1 || (long)ccap * skip_rpc > R || head)) return hipErrorInvalidValue;
-  const int grid = clist ? ccap * skip_rpc : R;
-  if (step >= max_steps || step >= SELF_MAXS) return hipErrorInvalidValue;
+  const GreedyHead hd = a.head ? *a.head : GreedyHead();
+  const int skip_rpc = rs.rpc;
+  const int rpc = (rs.rpc < 2 || R % (8 * rs.rpc)) ? 1 : rs.rpc;
+  const int grid = rs.clist ? rs.ccap * skip_rpc : R;
   const int n = step + 1;
-#define ND_SELF3(NW, KW, A, HD, Q, TB)                                                                              \
-  hipLaunchKernelGGL((dec_self_attention_kernel<NW, KW, A, HD, Q, TB>), dim3(grid), dim3(NW * 64), 0, s, qkv, cache, \
-                     anc, anc_ld, step, max_steps, out, rpc, skip, skip_rpc, qr, hd, clist)
-#define ND_SELF2(NW, KW, A)                  \
-  do {                                       \
-    if (q24)                                 \
-      ND_SELF3(NW, KW, A, false, true, false);  \
-    else                                     \
-      ND_SELF3(NW, KW, A, false, false, false); \
-  } while (0)
-#define ND_SELF(NW, KW)                              \
-  if (anc)                                           \
-    ND_SELF2(NW, KW, true);                          \
-  else if (head)                                     \
-    ND_SELF3(NW, KW, false, true, false, true);      \
-  else if (tab)                                      \
-    ND_SELF3(NW, KW, false, false, false, true);     \
-  else                                               \
-    ND_SELF2(NW, KW, false)
+  const int form = a.anc ? (a.q24 ? SELF_ANC_Q24 : SELF_ANC)
+                   : a.head ? SELF_HEAD
+                   : tab ? SELF_TAB
+                         : (a.q24 ? SELF_PLAIN_Q24 : SELF_PLAIN);
   // 4 waves of up to 16 keys per row up to 64 keys (beam rows: configs[3]
   // pooled 75.62 -> 74.59 ms, one call 94.28 -> 93.60 ms; greedy rows pooled
   // 16.75 / 16.84 -> 16.72 / 16.70 ms), then 8 waves of 16 keys (the 16-wave
   // forms fill a CU's whole register file and shut other pool lanes out:
   // pooled 17.85 -> 17.73 ms per call); round 3-4 same-box A/B pairs
-  if (n <= 16) ND_SELF(4, 4);
-  else if (n <= 32) ND_SELF(4, 8);
-  else if (n <= 64) ND_SELF(4, 16);
-  else ND_SELF(8, 16);  // two passes beyond 128 keys
-#undef ND_SELF
-#undef ND_SELF2
-#undef ND_SELF3
+  const int kw = n <= 16 ? 4 : n <= 32 ? 8 : 16, nw = n <= 64 ? 4 : 8;  // two passes beyond 128 keys
+  pick_form<8 * 16, 4 * 16, 4 * 8, 4 * 4>(nw * kw, [&](auto WK) {
+    constexpr int NW = decltype(WK)::value == 8 * 16 ? 8 : 4, KW = decltype(WK)::value / NW;
+    pick_form<SELF_PLAIN, SELF_PLAIN_Q24, SELF_TAB, SELF_HEAD, SELF_ANC, SELF_ANC_Q24>(form, [&](auto FM) {
+      constexpr int f = decltype(FM)::value;
+      hipLaunchKernelGGL((dec_self_attention_kernel<NW, KW, (f & 1) != 0, (f & 2) != 0, (f & 4) != 0, (f & 8) != 0>),
+                         dim3(grid), dim3(NW * 64), 0, s, a.qkv, a.cache, a.anc, a.anc_ld, step, a.max_steps, a.out,
+                         rpc, rs.done, skip_rpc, qr, hd, rs.clist);
+    });
+  });
   return hipGetLastError();
 }
 
@@ -1719,50 +1688,42 @@ hipError_t launch_ctx_pack_q24(const float* kv, int ld, int Ld, uint8_t* out, co
 
 static size_t ctx_lds_bytes(int rpc) { return (size_t)CTX_NW * rpc * (ND_D + 2 * ND_H) * sizeof(float); }
 
-hipError_t launch_dec_ctx_attention(const float* q, const void* kv, int ld, int koff, const float* signal,
-                                    const int* span, float pad_val, float* out, int C, int rpc, int T,
-                                    hipStream_t s, unsigned long long* stamp, float* attn_dbg, size_t dbg_stride,
-                                    const int* skip, bool q24, const int* clist, int ccap, int nsplit, float* part) {
-  if (rpc < 1 || rpc > CTX_MAXR || T > 512) return hipErrorInvalidValue;
-  if (clist && (ccap < 1 || ccap > C)) return hipErrorInvalidValue;
-  if (!clist || !part || attn_dbg) nsplit = 1;  // the split form runs over a chunk list (the -attn_debug form whole)
+// The forms of the context attention: f(kernel, a null pointer of its K/V type) for rpc rows per chunk on the
+// fp32 or the 24-bit K/V; false: no such form.
+template <typename F>
+static bool ctx_form(int rpc, bool q24, F&& f) {
+  return pick_form<8, 7, 6, 5, 4, 3, 2, 1>(rpc, [&](auto R) {
+    if (q24)
+      f(dec_ctx_q24_kernel<decltype(R)::value>, static_cast<const uint8_t*>(nullptr));
+    else
+      f(dec_ctx_attention_kernel<decltype(R)::value>, static_cast<const float*>(nullptr));
+  });
+}
+
+hipError_t launch_dec_ctx_attention(const CtxAttnArgs& a, hipStream_t s) {
+  const RowSet& rs = a.rows;
+  const int rpc = rs.rpc;
+  if (rpc < 1 || rpc > CTX_MAXR || a.T > 512) return hipErrorInvalidValue;
+  if (rs.clist && (rs.ccap < 1 || rs.ccap > rs.C)) return hipErrorInvalidValue;
+  // the split form runs over a chunk list (the -attn_debug form whole)
+  const int nsplit = (!rs.clist || !a.part || a.tap.dbg) ? 1 : a.nsplit;
   if (nsplit < 1 || nsplit > 64) return hipErrorInvalidValue;
-  float* const pout = nsplit > 1 ? part : nullptr;
-  const int grid = clist ? ccap * nsplit : C;
-  const size_t lds = q24 ? cq_lds_bytes(rpc) : ctx_lds_bytes(rpc);
-  switch (rpc) {
-#define ND_CTX_CASE(R)                                                                                            \
-  case R:                                                                                                         \
-    if (q24)                                                                                                      \
-      hipLaunchKernelGGL((dec_ctx_q24_kernel<R>), dim3(grid), dim3(CTX_NW * 64), lds, s, q,                       \
-                         static_cast<const uint8_t*>(kv), ld, koff, signal, span, pad_val, out, T, stamp,         \
-                         attn_dbg, dbg_stride, skip, clist, nsplit, pout);                                        \
-    else                                                                                                          \
-      hipLaunchKernelGGL((dec_ctx_attention_kernel<R>), dim3(grid), dim3(CTX_NW * 64), lds, s, q,                 \
-                         static_cast<const float*>(kv), ld, koff, signal, span, pad_val, out, T, stamp, attn_dbg, \
-                         dbg_stride, skip, clist, nsplit, pout);                                                  \
-    break;
-    ND_CTX_CASE(1)
-    ND_CTX_CASE(2)
-    ND_CTX_CASE(3)
-    ND_CTX_CASE(4)
-    ND_CTX_CASE(5)
-    ND_CTX_CASE(6)
-    ND_CTX_CASE(7)
-    ND_CTX_CASE(8)
-#undef ND_CTX_CASE
-  }
+  float* const pout = nsplit > 1 ? a.part : nullptr;
+  const int grid = rs.clist ? rs.ccap * nsplit : rs.C;
+  const size_t lds = a.q24 ? cq_lds_bytes(rpc) : ctx_lds_bytes(rpc);
+  ctx_form(rpc, a.q24, [&](auto kern, auto* kv) {
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(CTX_NW * 64), lds, s, a.q, static_cast<decltype(kv)>(a.kv), a.ld, a.koff,
+                       a.mask.signal, a.mask.span, a.mask.pad_val, a.out, a.T, a.tap.stamp, a.tap.dbg, a.tap.dbg_stride,
+                       rs.done, rs.clist, nsplit, pout);
+  });
   if (nsplit > 1) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(ctx_split_merge_kernel, dim3(ccap * rpc), dim3(ND_D), 0, s, part, clist, skip, nsplit, rpc, out);
+    hipLaunchKernelGGL(ctx_split_merge_kernel, dim3(rs.ccap * rpc), dim3(ND_D), 0, s, a.part, rs.clist, rs.done, nsplit,
+                       rpc, a.out);
   }
   return hipGetLastError();
 }
-
-}  // namespace nd
-
-namespace nd {
 
 __global__ void fill_i32_kernel(int* p, int v, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
@@ -1802,28 +1763,16 @@ hipError_t launch_alive_list(const int* done, int C, int* list, int cap, int* ov
 }
 
 hipError_t init_kernel_attributes() {
-  const void* fns[] = {
-      (const void*)dec_ctx_attention_kernel<1>, (const void*)dec_ctx_attention_kernel<2>,
-      (const void*)dec_ctx_attention_kernel<3>, (const void*)dec_ctx_attention_kernel<4>,
-      (const void*)dec_ctx_attention_kernel<5>, (const void*)dec_ctx_attention_kernel<6>,
-      (const void*)dec_ctx_attention_kernel<7>, (const void*)dec_ctx_attention_kernel<8>,
-      (const void*)dec_ctx_q24_kernel<1>,              (const void*)dec_ctx_q24_kernel<2>,
-      (const void*)dec_ctx_q24_kernel<3>,              (const void*)dec_ctx_q24_kernel<4>,
-      (const void*)dec_ctx_q24_kernel<5>,              (const void*)dec_ctx_q24_kernel<6>,
-      (const void*)dec_ctx_q24_kernel<7>,              (const void*)dec_ctx_q24_kernel<8>};
-  for (const void* f : fns) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-  }
-  {
-    hipError_t e = init_mem_attributes();
-    if (e != hipSuccess) return e;
-  }
-  {
-    hipError_t e = init_bank8_attributes();
-    if (e != hipSuccess) return e;
-  }
-  return init_gemm_attributes();
+  hipError_t e = hipSuccess;
+  for (int rpc = 1; rpc <= CTX_MAXR; ++rpc)
+    for (int q24 = 0; q24 < 2; ++q24)
+      ctx_form(rpc, q24 != 0, [&](auto kern, auto*) {
+        if (e == hipSuccess)
+          e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      });
+  if (e == hipSuccess) e = init_mem_attributes();
+  if (e == hipSuccess) e = init_bank8_attributes();
+  return e == hipSuccess ? init_gemm_attributes() : e;
 }
 
 }  // namespace nd

@@ -571,54 +571,36 @@ static int bank_cached(int C) { return C / 4; }
 // rows past T zero with scale 0, and they are masked: the blocks past them need not be streamed)
 static int bank8_kpw(int T) { return std::min(B8_KPW, (T + 127) / 128); }
 
-hipError_t launch_dec_bank_d8(const float* qp, const void* bank, const float* kscale, const int* kemax,
-                              const float* signal, const int* span, float pad_val, float* out, int C, int T,
-                              hipStream_t s, unsigned long long* stamp, float* attn_dbg, size_t dbg_stride, int* ovf,
-                              bool nt, int grid) {
-  if (T < 1 || T > 512 || C < 1 || grid < 0 || !bank || !kscale || !kemax) return hipErrorInvalidValue;
-  const int G = grid > 0 ? std::min(C, grid) : C;
-  const int kpw = bank8_kpw(T);
-#define ND_BANK8_GO(N, W, K)                                                                                      \
-  hipLaunchKernelGGL((dec_bank_d8_kernel<N, W, K>), dim3(G), dim3(B8_NW * 64), B8_LDS, s, qp,                    \
-                     reinterpret_cast<const i32x4*>(bank), kscale, kemax, signal, span, pad_val, out, T, C, stamp,  \
-                     attn_dbg, dbg_stride, ovf, bank_cached(C))
-#define ND_BANK8_K(N, W)         \
-  do {                           \
-    if (kpw == 4)                \
-      ND_BANK8_GO(N, W, 4);      \
-    else if (kpw == 3)           \
-      ND_BANK8_GO(N, W, 3);      \
-    else if (kpw == 2)           \
-      ND_BANK8_GO(N, W, 2);      \
-    else                         \
-      ND_BANK8_GO(N, W, 1);      \
-  } while (0)
-  if (G < C) {
-    if (nt)
-      ND_BANK8_K(true, true);
-    else
-      ND_BANK8_K(false, true);
-  } else if (nt) {
-    ND_BANK8_K(true, false);
-  } else {
-    ND_BANK8_K(false, false);
-  }
-#undef ND_BANK8_K
-#undef ND_BANK8_GO
+// The forms of the kernel: non-temporal bank loads, workgroups that walk several chunks, key blocks per wave
+template <typename F>
+static void bank8_form(bool nt, bool walk, int kpw, F&& f) {
+  pick_form<0, 2, 1, 3>(2 * nt + walk, [&](auto NW) {
+    pick_form<1, 2, 3, 4>(kpw, [&](auto K) {
+      constexpr int nw = decltype(NW)::value;
+      f(dec_bank_d8_kernel<(nw & 2) != 0, (nw & 1) != 0, decltype(K)::value>);
+    });
+  });
+}
+
+hipError_t launch_dec_bank_d8(const BankD8Args& a, hipStream_t s) {
+  const int C = a.C, T = a.T;
+  if (T < 1 || T > 512 || C < 1 || a.grid < 0 || !a.bank || !a.kscale || !a.kemax) return hipErrorInvalidValue;
+  const int G = a.grid > 0 ? std::min(C, a.grid) : C;
+  bank8_form(a.nt, G < C, bank8_kpw(T), [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(G), dim3(B8_NW * 64), B8_LDS, s, a.qp, reinterpret_cast<const i32x4*>(a.bank),
+                       a.kscale, a.kemax, a.mask.signal, a.mask.span, a.mask.pad_val, a.out, T, C, a.tap.stamp,
+                       a.tap.dbg, a.tap.dbg_stride, a.ovf, bank_cached(C));
+  });
   return hipGetLastError();
 }
 
 hipError_t init_bank8_attributes() {
-#define ND_BANK8_FNS(K)                                                                                           \
-  (const void*)dec_bank_d8_kernel<false, false, K>, (const void*)dec_bank_d8_kernel<true, false, K>,              \
-      (const void*)dec_bank_d8_kernel<false, true, K>, (const void*)dec_bank_d8_kernel<true, true, K>
-  const void* fns[] = {ND_BANK8_FNS(4), ND_BANK8_FNS(3), ND_BANK8_FNS(2), ND_BANK8_FNS(1)};
-#undef ND_BANK8_FNS
-  for (const void* f : fns) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, B8_LDS);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 4 * B8_KPW; ++i)
+    bank8_form((i & 2) != 0, (i & 1) != 0, 1 + i / 4, [&](auto kern) {
+      if (e == hipSuccess) e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, B8_LDS);
+    });
+  return e;
 }
 
 }  // namespace nd

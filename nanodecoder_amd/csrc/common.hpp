@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #define ND_D 256         // d_model (compiled constant)
 #define ND_DH 32         // head dim
 #define ND_H 8           // heads
@@ -201,6 +203,16 @@ __device__ __forceinline__ float absmax4(f32x4 v) {
 }
 __device__ __forceinline__ void flag_overflow(int* ovf, float amax) {
   if (amax >= ND_F16_LIMIT && ovf != nullptr) ovf[0] = 1;
+}
+
+// Host side: a runtime value picks a template instantiation.  Calls f(std::integral_constant<int, V>) for the
+// first V of Vs equal to v; false when none is.  A kernel family writes its forms once as a function that maps
+// the runtime choice to a kernel pointer through this, and both its launcher and its hipFuncSetAttribute loop
+// (over the choices) call that function.  hipcc emits the kernels a list instantiates last value first: the
+// lists are written in the order that keeps each code object's kernels where they were (same addresses).
+template <int... Vs, typename F>
+inline bool pick_form(int v, F&& f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
 }
 
 // Launch-duration stamps (bench roofline, measured inside the timed graph):

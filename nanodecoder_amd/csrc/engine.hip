@@ -368,14 +368,23 @@ static int dec_ffn_splits(const nd_ctx* c, int R) {
   return std::max(1, std::min({8, 160 / rb, F / 32}));
 }
 
-// done: per chunk, nonzero = finished (--fast beam; null otherwise): its rows'
-// tiles and attention workgroups exit without work
-// gtok_ld: greedy calls (one row per chunk, no ancestry): the leading dimension of c->gtok, the call's
-// max_len; layer 0 then reads its history from the table by the row's tokens there (0: the cache)
-static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, const int* anc, int anc_ld,
-                                   hipStream_t s, const int* done = nullptr, const nd::GreedyHead* head = nullptr,
-                                   const int* clist = nullptr, int ccap = 0, int gtok_ld = 0) {
-  const int R = C * rpc, D = c->D, F = c->F, S = c->cfg.max_steps;
+// What the self-attention of a step reads besides the step's rows: the beam's cache slot ancestry, or, for
+// greedy rows (one row per chunk, no ancestry), the tokens picked so far, c->gtok with leading dimension
+// gtok_ld = the call's max_len (0: the cache), by which layer 0 reads its history from the table; and the
+// previous step's greedy head, fused into layer 0
+struct StepHist {
+  const int* anc = nullptr;
+  int anc_ld = 0;
+  int gtok_ld = 0;
+  const nd::GreedyHead* head = nullptr;
+};
+
+// rows: C chunks of rpc rows; rows.done (--fast beam; null otherwise): the finished chunks' tiles and
+// attention workgroups exit without work
+static hipError_t enqueue_dec_step(nd_ctx* c, const nd::RowSet& rows, int T, int step, const StepHist& h,
+                                   hipStream_t s) {
+  const int C = rows.C, rpc = rows.rpc, R = C * rpc, D = c->D, F = c->F, S = c->cfg.max_steps;
+  const int* const done = rows.done;
   const int Ld = (int)c->m.dec.size();
   const bool mb = use_memory_bank(c, rpc);
   int pnx = 1, pnq = 0, pnm = 0;
@@ -383,6 +392,7 @@ static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, c
   auto dg = [&](const float* A, int lda, const float* W, int N, int K, const float* bias, float* out, int ldc) {
     return G(A, lda, W, N, K, bias, out, ldc, R).p16().h3(c).skip(done, rpc).small_m(c->beam_tail).splitk(c);
   };
+  const nd::SrcMask mask{.signal = c->sig, .span = c->span, .pad_val = (float)c->cfg.pad_idx};
   for (int i = 0; i < Ld; ++i) {
     DecLayer& L = c->m.dec[i];
     // the self-attention history: beam rows keep 24-bit rows (1600 B per key, attention.hip
@@ -390,18 +400,18 @@ static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, c
     // fp32 k | v (2 KB).  Same box, two reps (profiles/r05_self_q24_ab.txt): configs[3] pooled
     // 67.71 / 67.78 -> 67.28 / 67.17 ms; greedy configs[1] pooled 15.55 / 15.53 -> 15.70 / 15.74 (the
     // row's own history is 100 keys at most: the dequantise costs more than the bytes it saves)
-    const bool sq24 = anc && !c->exact && c->cfg.self_attn_type != ND_SELF_AVERAGE;
+    const bool sq24 = h.anc && !c->exact && c->cfg.self_attn_type != ND_SELF_AVERAGE;
     float* cache = sq24 ? reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(c->cache) + (size_t)i * R * S * CTXQ_ROW)
                         : c->cache + (size_t)i * R * S * 2 * D;
-    unsigned long long* stamp = c->kstamp_on ? c->kstamp + 2 * ((size_t)step * Ld + i) : nullptr;
-    // -attn_debug (greedy): the last layer's head-0 context scores, [B][S][T]
-    float* dbg = (c->attn_on && i == Ld - 1) ? c->attn_raw + (size_t)step * T : nullptr;
-    const size_t dbg_stride = (size_t)S * T;
+    // kernel stamps; -attn_debug (greedy): the last layer's head-0 context scores, [B][S][T]
+    const nd::AttnTap tap{.stamp = c->kstamp_on ? c->kstamp + 2 * ((size_t)step * Ld + i) : nullptr,
+                          .dbg = (c->attn_on && i == Ld - 1) ? c->attn_raw + (size_t)step * T : nullptr,
+                          .dbg_stride = (size_t)S * T};
     // decoder/transformer.py:53-95
     // all step activations are P16-packed (kernels.hpp)
     if (c->cfg.self_attn_type == ND_SELF_AVERAGE) {
       // average_attn.py:55-106 + the layer residual (decoder/transformer.py:82-86)
-      LCHK(nd::launch_aan_prep(c->dx, L.ln1_g, L.ln1_b, cache, anc, anc_ld, step, S, c->axn, c->aavg, c->aavg_part,
+      LCHK(nd::launch_aan_prep(c->dx, L.ln1_g, L.ln1_b, cache, h.anc, h.anc_ld, step, S, c->axn, c->aavg, c->aavg_part,
                                R, s));
       LCHK(dg(c->aavg, D, L.paw1, D, D, L.nab1, c->ah, D).ln(c->aavg_part, 1).relu().run(s));
       LCHK(dg(c->ah, D, L.paw2, D, D, L.ab2, c->aa, D).res(c->aavg, D).run(s));
@@ -410,27 +420,26 @@ static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, c
       LCHK(nd::launch_aan_gate(c->ag, c->axn, c->aa, c->dx, c->dq1, c->dq1_part, R, s));
       pnq = 1;
     } else {
+      nd::SelfAttnArgs sa{.qkv = c->dqkv, .cache = cache, .anc = h.anc, .anc_ld = h.anc_ld, .step = step,
+                          .max_steps = S, .out = c->datt, .R = R, .rows = rows, .q24 = sq24};
       if (i == 0 && qkv_table(c)) {  // the row's q | k | v from the model's table
-        nd::QkvRows qr;
-        qr.tok = c->rtok;
-        qr.V = c->V;
-        qr.tok0 = c->cfg.bos_idx;
-        qr.rm = 1;  // the table is row-major (model.hip build_qkv_tables)
-        if (gtok_ld > 0 && rpc == 1 && !anc && !done && !clist) {  // greedy rows: the history too
-          qr.hist = c->gtok;
-          qr.hist_ld = gtok_ld;
+        sa.qkv = qkv_table(c);
+        sa.qr.tok = c->rtok;
+        sa.qr.V = c->V;
+        sa.qr.tok0 = c->cfg.bos_idx;
+        sa.qr.rm = 1;  // the table is row-major (model.hip build_qkv_tables)
+        if (h.gtok_ld > 0 && rpc == 1 && !h.anc && !done && !rows.clist) {  // greedy rows: the history too
+          sa.qr.hist = c->gtok;
+          sa.qr.hist_ld = h.gtok_ld;
         }
-        LCHK(nd::launch_dec_self_attention(qkv_table(c), cache, anc, anc_ld, step, S, c->datt, R, s, rpc, done, qr,
-                                           head, clist, ccap, sq24));
+        sa.head = h.head;
       } else {
         // greedy rows (one workgroup each): q | k | v row-major; beam keeps P16 (its M = 5120 GEMMs
         // take the LDS-tiled route, which writes P16)
-        nd::QkvRows q12;
-        q12.rm = (rpc == 1 && !anc && !done) ? 1 : 0;
-        LCHK(dg(c->dx, D, L.pwqkv, 3 * D, D, L.nbqkv, c->dqkv, 3 * D).ln(c->dx_part, pnx).c_rowmajor(q12.rm).run(s));
-        LCHK(nd::launch_dec_self_attention(c->dqkv, cache, anc, anc_ld, step, S, c->datt, R, s, rpc, done, q12, nullptr,
-                                           clist, ccap, sq24));
+        sa.qr.rm = (rpc == 1 && !h.anc && !done) ? 1 : 0;
+        LCHK(dg(c->dx, D, L.pwqkv, 3 * D, D, L.nbqkv, c->dqkv, 3 * D).ln(c->dx_part, pnx).c_rowmajor(sa.qr.rm).run(s));
       }
+      LCHK(nd::launch_dec_self_attention(sa, s));
       LCHK(dg(c->datt, D, L.pwo, D, D, L.bo, c->dq1, D).res(c->dx, D).stats(c->dq1_part).run(s, &pnq));
     }
     if (mb) {  // memory-bank form (attention.hip)
@@ -438,22 +447,25 @@ static hipError_t enqueue_dec_step(nd_ctx* c, int C, int rpc, int T, int step, c
       // q' row-major for the digit-bank kernel (one row per chunk), P16 for the fp32 one
       LCHK(dg(c->dq1, D, L.pwqk, HD, D, L.bqk, c->dqk, HD).ln(c->dq1_part, pnq).c_rowmajor(c->bank_d8).run(s));
       if (c->bank_d8)
-        LCHK(nd::launch_dec_bank_d8(c->dqk, c->mem_p, c->bank_ks, c->bank_em, c->sig, c->span, (float)c->cfg.pad_idx,
-                                    c->dU, C, T, s, stamp, dbg, dbg_stride, c->ovf, c->bank_nt, c->bank_grid));
+        LCHK(nd::launch_dec_bank_d8({.qp = c->dqk, .bank = c->mem_p, .kscale = c->bank_ks, .kemax = c->bank_em,
+                                     .mask = mask, .out = c->dU, .C = C, .T = T, .tap = tap, .ovf = c->ovf,
+                                     .nt = c->bank_nt, .grid = c->bank_grid}, s));
       else
-        LCHK(nd::launch_dec_mem_attention(c->dqk, c->mem, c->sig, c->span, (float)c->cfg.pad_idx, c->dU, C, rpc, T,
-                                          T, s, stamp, dbg, dbg_stride, c->bank_grid));
+        LCHK(nd::launch_dec_mem_attention({.qp = c->dqk, .mem = c->mem, .mask = mask, .out = c->dU, .C = C, .rpc = rpc,
+                                           .T = T, .ldT = T, .tap = tap, .grid = c->bank_grid}, s));
       LCHK(dg(c->dU, HD, L.pwvo, D, HD, L.bvo, c->dmid, D).res(c->dq1, D).stats(c->dmid_part).run(s, &pnm));
     } else {
       LCHK(dg(c->dq1, D, L.pcwq, D, D, L.ncbq, c->dcq, D).ln(c->dq1_part, pnq).run(s));
-      if (c->ctx_q24)
-        LCHK(nd::launch_dec_ctx_attention(c->dcq, c->ctxq + (size_t)i * C * T * CTXQ_ROW, CTXQ_ROW, 0, c->sig, c->span,
-                                          (float)c->cfg.pad_idx, c->datt, C, rpc, T, s, stamp, dbg, dbg_stride, done,
-                                          true, clist, ccap, ctx_split(), c->ctx_part));
-      else
-        LCHK(nd::launch_dec_ctx_attention(c->dcq, c->ctxkv, Ld * 2 * D, i * 2 * D, c->sig, c->span,
-                                          (float)c->cfg.pad_idx, c->datt, C, rpc, T, s, stamp, dbg, dbg_stride, done,
-                                          false, clist, ccap, ctx_split(), c->ctx_part));
+      // beam rows read layer i's plane of the 24-bit image (ld, koff in bytes), or its columns of the fp32 K/V
+      nd::CtxAttnArgs ca{.q = c->dcq, .kv = c->ctxkv, .ld = Ld * 2 * D, .koff = i * 2 * D, .q24 = c->ctx_q24, .T = T,
+                         .out = c->datt, .mask = mask, .rows = rows, .tap = tap, .nsplit = ctx_split(),
+                         .part = c->ctx_part};
+      if (c->ctx_q24) {
+        ca.kv = c->ctxq + (size_t)i * C * T * CTXQ_ROW;
+        ca.ld = CTXQ_ROW;
+        ca.koff = 0;
+      }
+      LCHK(nd::launch_dec_ctx_attention(ca, s));
       LCHK(dg(c->datt, D, L.pcwo, D, D, L.cbo, c->dmid, D).res(c->dq1, D).stats(c->dmid_part).run(s, &pnm));
     }
     if (const int ns = dec_ffn_splits(c, R)) {  // beam rows: the fused block, hidden on chip (ffn.hip)
@@ -494,26 +506,24 @@ static hipError_t enqueue_memory(nd_ctx* c, int B, int T, int rpc, hipStream_t s
   return nd::launch_memory_pack(c->x, c->m.bank_ln_g, c->m.bank_ln_b, c->mem_p, B, T, T, s);
 }
 
-static hipError_t enqueue_greedy(nd_ctx* c, int B, int T, int S, int min_len, bool logp, hipStream_t s,
-                                 const nd::Sampling& smp = nd::Sampling()) {
+static hipError_t enqueue_greedy(nd_ctx* c, int B, int T, int S, int min_len, bool logp, const nd::Sampling& smp,
+                                 hipStream_t s) {
   if (c->kstamp_on) LCHK(nd::launch_stamp_reset(c->kstamp, (int)c->m.dec.size() * c->cfg.max_steps, s));
   LCHK(enqueue_encode(c, B, T, s));
   LCHK(enqueue_memory(c, B, T, 1, s));
   LCHK(nd::launch_fill_i32(c->tok, c->cfg.bos_idx, B, s));
   LCHK(enqueue_first_embed(c, B, s));
-  const nd::NextEmbed ne = next_embed(c);
   // step k's head runs inside step k + 1's layer-0 self-attention (table
   // mode); only the last step's head is a launch of its own
   const bool fuse = head_fused(c);
-  const nd::GreedyHead hd = nd::make_greedy_head(c->dx, c->m.dec_ln_g, c->m.dec_ln_b, c->m.gen_w, c->m.gen_b, c->V, S, min_len,
-                                                 c->cfg.eos_idx, c->tok, c->gtok, c->gscore,
-                                                 logp ? c->glogp : nullptr, ne, smp);
+  const nd::GreedyHead hd{.x = c->dx, .ln_g = c->m.dec_ln_g, .ln_b = c->m.dec_ln_b, .gw = c->m.gen_w, .gb = c->m.gen_b,
+                          .V = c->V, .S = S, .min_len = min_len, .eos = c->cfg.eos_idx, .tok = c->tok,
+                          .out_tokens = c->gtok, .score = c->gscore, .logp_dump = logp ? c->glogp : nullptr,
+                          .ne = next_embed(c), .smp = smp};
+  const nd::RowSet rows{.C = B, .rpc = 1};
   for (int step = 0; step < S; ++step) {
-    LCHK(enqueue_dec_step(c, B, 1, T, step, nullptr, 0, s, nullptr, fuse && step > 0 ? &hd : nullptr, nullptr, 0, S));
-    if (!fuse || step == S - 1)
-      LCHK(nd::launch_dec_greedy_head(c->dx, c->m.dec_ln_g, c->m.dec_ln_b, c->m.gen_w, c->m.gen_b, c->V, step, S, min_len,
-                                      c->cfg.eos_idx, c->tok, c->gtok, c->gscore, logp ? c->glogp : nullptr, ne, B,
-                                      s, smp));
+    LCHK(enqueue_dec_step(c, rows, T, step, {.gtok_ld = S, .head = fuse && step > 0 ? &hd : nullptr}, s));
+    if (!fuse || step == S - 1) LCHK(nd::launch_dec_greedy_head(hd, step, B, s));
   }
   if (c->attn_on) LCHK(nd::launch_attn_rows_softmax(c->attn_raw, c->span, B, c->cfg.max_steps, T, s));
   return hipSuccess;
@@ -535,24 +545,28 @@ static hipError_t enqueue_attn_step(nd_ctx* c, int C, int rpc, int T, int step, 
   return nd::launch_attn_step_softmax(c->attn_raw + (size_t)step * T, S * T, c->span, C * rpc, rpc, T, s);
 }
 
+// the output head over the decoder rows x
+static nd::Generator generator(const nd_ctx* c, const float* x) {
+  return {.x = x, .ln_g = c->m.dec_ln_g, .ln_b = c->m.dec_ln_b, .gw = c->m.gen_w, .gb = c->m.gen_b, .V = c->V};
+}
+
 static hipError_t enqueue_beam_steps(nd_ctx* c, int B, int T, int beam, int n_best, float alpha, int S, int min_len,
                                      int s0, int s1, hipStream_t s) {
   const nd::BeamState st = beam_state(c);
+  nd::BeamCall bc{.rows = {.C = B, .rpc = beam, .done = c->bs.done}, .n_best = n_best, .S = S, .min_len = min_len,
+                  .eos = c->cfg.eos_idx};
   // the tail (at most a sixteenth of the chunks alive, translate_beam): the attention and beam-step launches
   // run over the segment's alive chunks only (a list built at its start), not B chunks that exit at once
-  const int ccap = (B + 15) / 16;
-  const int* clist = nullptr;
   if (c->beam_tail) {
-    LCHK(nd::launch_alive_list(c->bs.done, B, c->clist, ccap, c->ovf, s));
-    clist = c->clist;
+    bc.rows.clist = c->clist;
+    bc.rows.ccap = (B + 15) / 16;
+    LCHK(nd::launch_alive_list(c->bs.done, B, c->clist, bc.rows.ccap, c->ovf, s));
   }
   for (int step = s0; step < s1; ++step) {
-    const int cur = step & 1;
-    LCHK(enqueue_dec_step(c, B, beam, T, step, c->bs.anc[cur], S, s, c->bs.done, nullptr, clist, ccap));
+    LCHK(enqueue_dec_step(c, bc.rows, T, step, {.anc = c->bs.anc[step & 1], .anc_ld = S}, s));
     LCHK(enqueue_attn_step(c, B, beam, T, step, s));
     const float lenpen = (float)std::pow((5.0 + (step + 1)) / 6.0, (double)alpha);
-    LCHK(nd::launch_beam_step(next_embed(c), c->dx, c->m.dec_ln_g, c->m.dec_ln_b, c->m.gen_w, c->m.gen_b, c->V, st, B, beam,
-                              n_best, step, S, min_len, c->cfg.eos_idx, lenpen, s, clist, ccap));
+    LCHK(nd::launch_beam_step(next_embed(c), generator(c, c->dx), st, bc, step, lenpen, s));
   }
   return hipSuccess;
 }
@@ -560,11 +574,12 @@ static hipError_t enqueue_beam_steps(nd_ctx* c, int B, int T, int beam, int n_be
 static hipError_t enqueue_classic_steps(nd_ctx* c, int B, int T, int beam, int n_best, const nd::ClassicOpts& o, int S,
                                         int min_len, int s0, int s1, hipStream_t s) {
   const nd::BeamState st = beam_state(c);
+  const nd::BeamCall bc{.rows = {.C = B, .rpc = beam}, .n_best = n_best, .S = S, .min_len = min_len,
+                        .eos = c->cfg.eos_idx};
   for (int step = s0; step < s1; ++step) {
-    LCHK(enqueue_dec_step(c, B, beam, T, step, c->bs.anc[step & 1], S, s));
+    LCHK(enqueue_dec_step(c, bc.rows, T, step, {.anc = c->bs.anc[step & 1], .anc_ld = S}, s));
     LCHK(enqueue_attn_step(c, B, beam, T, step, s));
-    LCHK(nd::launch_beam_classic_step(next_embed(c), c->dx, c->m.dec_ln_g, c->m.dec_ln_b, c->m.gen_w, c->m.gen_b, c->V, st,
-                                      B, beam, n_best, step, S, min_len, c->cfg.eos_idx, o, s));
+    LCHK(nd::launch_beam_classic_step(next_embed(c), generator(c, c->dx), st, bc, step, o, s));
   }
   return hipSuccess;
 }
@@ -767,7 +782,7 @@ static int translate_greedy(nd_ctx* c, const float* d_signal, const int32_t* d_l
   {
     const CallFlags flags(c, d_attn != nullptr);
     set_memory_view(c, T, 1);
-    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_greedy(c, B, T, max_len, min_len, lp, s, smp); });
+    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_greedy(c, B, T, max_len, min_len, lp, smp, s); });
   }
   if (rc) return rc;
   if (c->timing) HIPCHK(hipEventRecord(c->ev_b, c->es));
@@ -905,7 +920,7 @@ static int translate_beam(nd_ctx* c, const float* d_signal, const int32_t* d_len
   key.attn = d_attn ? 1 : 0;
   return translate_segmented(
       c, io, key, true,
-      [&](hipStream_t s) { return nd::launch_beam_init(c->bs, B, beam, n_best, max_len, c->cfg.bos_idx, s); },
+      [&](hipStream_t s) { return nd::launch_beam_init(c->bs, B, beam, c->cfg.bos_idx, s); },
       [&](int s0, int s1, hipStream_t s) {
         return enqueue_beam_steps(c, B, T, beam, n_best, alpha, max_len, min_len, s0, s1, s);
       },
@@ -1055,18 +1070,19 @@ static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, b
   for (int i = 0; i < Ld; ++i) {
     const DecLayer& Y = m.dec[i];
     LCHK(G(c->tf_x, D, Y.nwqkv, 3 * D, D, Y.nbqkv, c->tf_big, 3 * D, M).h3(c).ln(c->tf_x_part, pnx).run(s));
-    LCHK(nd::launch_tf_attention(c->tf_big, 3 * D, c->tf_big, 3 * D, D, 2 * D, nullptr, nullptr, 0.f, c->tf_att, B, L, L,
-                                 true, s));
+    LCHK(nd::launch_tf_attention({.q = c->tf_big, .ldq = 3 * D, .kv = c->tf_big, .ldkv = 3 * D, .koff = D, .voff = 2 * D,
+                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = L, .causal = true}, s));
     LCHK(G(c->tf_att, D, Y.wo, D, D, Y.bo, c->tf_q1, D, M).h3(c).res(c->tf_x, D).stats(c->tf_q1_part).run(s, &pnq));
     LCHK(G(c->tf_q1, D, Y.ncwq, D, D, Y.ncbq, c->tf_cq, D, M).h3(c).ln(c->tf_q1_part, pnq).run(s));
-    LCHK(nd::launch_tf_attention(c->tf_cq, D, c->ctxkv, Ld * 2 * D, i * 2 * D, i * 2 * D + D, c->sig, c->span, pad,
-                                 c->tf_att, B, L, T, false, s));
+    LCHK(nd::launch_tf_attention({.q = c->tf_cq, .ldq = D, .kv = c->ctxkv, .ldkv = Ld * 2 * D, .koff = i * 2 * D,
+                                  .voff = i * 2 * D + D, .mask = {.signal = c->sig, .span = c->span, .pad_val = pad},
+                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = T}, s));
     LCHK(G(c->tf_att, D, Y.cwo, D, D, Y.cbo, c->tf_mid, D, M).h3(c).res(c->tf_q1, D).stats(c->tf_mid_part).run(s, &pnm));
     LCHK(G(c->tf_mid, D, Y.nw1, F, D, Y.nb1, c->tf_big, F, M).h3(c).ln(c->tf_mid_part, pnm).relu().run(s));
     LCHK(G(c->tf_big, F, Y.w2, D, F, Y.b2, c->tf_x, D, M).h3(c).res(c->tf_mid, D).stats(c->tf_x_part).run(s, &pnx));
   }
-  return nd::launch_score_head(c->tf_x, m.dec_ln_g, m.dec_ln_b, m.gen_w, m.gen_b, c->V, c->tf_gold, c->tf_gold_len, B, L,
-                               c->tf_score, want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s);
+  return nd::launch_score_head(generator(c, c->tf_x), c->tf_gold, c->tf_gold_len, B, L, c->tf_score,
+                               want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s);
 }
 
 int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,

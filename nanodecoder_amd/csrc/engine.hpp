@@ -18,11 +18,6 @@
 #include "common.hpp"
 #include "kernels.hpp"
 
-namespace nd {
-hipError_t init_kernel_attributes();
-hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t s);
-}  // namespace nd
-
 // nd_last_error's text: one thread-local string for the whole library (defined in engine.hip)
 extern thread_local std::string g_err;
 

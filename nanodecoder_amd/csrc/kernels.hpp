@@ -214,35 +214,72 @@ struct QkvRows {
 // one row-statistics partial per row; rows S * V .. rows_alloc - 1 zero
 hipError_t launch_dec_embed_table(const float* emb, const float* pe, int V, int S, float* x, float* part, int rows_alloc,
                                   hipStream_t s);
-struct DecStepArgs;
 hipError_t launch_dec_embed(const int* tok, const float* emb, const float* pe, int step, float* x, float* part,
                             int R, hipStream_t s);
+hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t s);
+// raises the dynamic-LDS limit of every form of the decoder attentions and the GEMMs (once per process)
+hipError_t init_kernel_attributes();
+
+// Launch arguments of the decoder-step kernels: host-only aggregates filled by field name; the launchers
+// unpack them into the kernels' argument lists.  Three bundles recur:
+// the source-side key mask: keys t < span[c], those with signal[c*T + t] == pad_val filled with ND_MASK_FILL
+struct SrcMask {
+  const float* signal = nullptr;
+  const int* span = nullptr;
+  float pad_val = 0.f;
+};
+// the chunks and rows a launch covers: rows r = c * rpc + j of the chunks c < C
+struct RowSet {
+  int C = 0;
+  int rpc = 1;
+  const int* done = nullptr;   // --fast beam: per chunk, nonzero = finished, its rows do nothing
+  // --fast beam tail: the launch runs the chunks listed here only (ccap entries, -1 = none);
+  // launch_alive_list builds the list from the done flags
+  const int* clist = nullptr;
+  int ccap = 0;
+};
+// kernel stamps (common.hpp stamp_begin) and the -attn_debug capture of the head-0 scores
+struct AttnTap {
+  unsigned long long* stamp = nullptr;
+  float* dbg = nullptr;
+  size_t dbg_stride = 0;
+};
 // self attention: writes k,v of this step into cache[slot=r][step], attends
 // over the row's history cache[anc[r][t]][t] (anc == nullptr: identity).
-// skip (nullable): per chunk (row / rpc), nonzero = finished, its rows do nothing.
 // qr.hist (table history, QkvRows): the history comes from the table, the cache is not touched.
-// head (greedy, table history, step > 0): the workgroup of row r first
-// runs the previous step's greedy head for r (its token is this step's input),
-// so the standalone head kernel runs only after the last step
 struct GreedyHead;
-hipError_t launch_dec_self_attention(const float* qkv, float* cache, const int* anc, int anc_ld, int step,
-                                     int max_steps, float* out, int R, hipStream_t s, int rpc = 1,
-                                     const int* skip = nullptr, const QkvRows& qr = QkvRows(),
-                                     const GreedyHead* head = nullptr, const int* clist = nullptr, int ccap = 0,
-                                     bool q24 = false);
-// q24: the cache holds 1600-B 24-bit rows (attention.hip SELF_Q24_ROW) instead of [512] floats
+struct SelfAttnArgs {
+  const float* qkv = nullptr;
+  float* cache = nullptr;
+  const int* anc = nullptr;
+  int anc_ld = 0, step = 0, max_steps = 0;
+  float* out = nullptr;
+  int R = 0;    // rows of qkv and out
+  RowSet rows;  // rpc, done and the chunk list (C unused: R says it)
+  QkvRows qr;
+  // greedy, table history, step > 0: the workgroup of row r first runs the previous step's greedy head
+  // for r (its token is this step's input), so the standalone head kernel runs only after the last step
+  const GreedyHead* head = nullptr;
+  bool q24 = false;  // the cache holds 1600-B 24-bit rows (attention.hip SELF_Q24_ROW) instead of [512] floats
+};
+hipError_t launch_dec_self_attention(const SelfAttnArgs& a, hipStream_t s);
 // context attention: rows r = c*rpc + j attend over ctxkv rows of chunk c
-// (K at kv[(c*T+t)*ld + koff], V at +256), mask signal == pad_val, keys < span.
-// q24: kv is the 24-bit image of launch_ctx_pack_q24 (ld, koff in bytes).
-hipError_t launch_dec_ctx_attention(const float* q, const void* kv, int ld, int koff, const float* signal,
-                                    const int* span, float pad_val, float* out, int C, int rpc, int T,
-                                    hipStream_t s, unsigned long long* stamp = nullptr, float* attn_dbg = nullptr,
-                                    size_t dbg_stride = 0, const int* skip = nullptr, bool q24 = false,
-                                    const int* clist = nullptr, int ccap = 0, int nsplit = 1, float* part = nullptr);
-// part: nsplit > 1 (with clist): scratch of ccap * nsplit * rpc * (256 + 16) floats
-// --fast beam tail: clist (nullable) lists the chunks the self / context
-// attention and the beam step run (ccap entries, -1 = none); launch_alive_list
-// builds it from the done flags (*ovf = 1 when more than cap are alive)
+// (K at kv[(c*T+t)*ld + koff], V at +256)
+struct CtxAttnArgs {
+  const float* q = nullptr;
+  const void* kv = nullptr;
+  int ld = 0, koff = 0;
+  bool q24 = false;  // kv is the 24-bit image of launch_ctx_pack_q24 (ld, koff in bytes)
+  int T = 0;
+  float* out = nullptr;
+  SrcMask mask;
+  RowSet rows;
+  AttnTap tap;
+  int nsplit = 1;         // workgroups per listed chunk (rows.clist; the -attn_debug form runs whole)
+  float* part = nullptr;  // nsplit > 1: scratch of ccap * nsplit * rpc * (256 + 16) floats
+};
+hipError_t launch_dec_ctx_attention(const CtxAttnArgs& a, hipStream_t s);
+// RowSet.clist from the done flags (*ovf = 1 when more than cap are alive)
 hipError_t launch_alive_list(const int* done, int C, int* list, int cap, int* ovf, hipStream_t s);
 // 24-bit context K/V (beam rows): per (key row, layer) CTXQ_ROW bytes = k's 256
 // integers (3 bytes each, lane i's 12 bytes = dims 4i..4i+3) | v's | per head
@@ -271,10 +308,16 @@ struct NextEmbed {
 // space), mem = row-major memory bank [C * ldT, 256] (chunk c's position t at
 // row c*ldT + t, t < T <= ldT); out = U [C, 8*256] P16 (head h's
 // softmax-weighted memory sum).
-hipError_t launch_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int* span,
-                                    float pad_val, float* out, int C, int rpc, int T, int ldT, hipStream_t s,
-                                    unsigned long long* stamp = nullptr, float* attn_dbg = nullptr,
-                                    size_t dbg_stride = 0, int grid = 0);
+struct MemAttnArgs {
+  const float* qp = nullptr;
+  const float* mem = nullptr;
+  SrcMask mask;
+  float* out = nullptr;
+  int C = 0, rpc = 1, T = 0, ldT = 0;
+  AttnTap tap;
+  int grid = 0;  // workgroups at most (they walk the chunks); 0 = one per chunk
+};
+hipError_t launch_dec_mem_attention(const MemAttnArgs& a, hipStream_t s);
 // -attn_debug: raw head-0 score rows [B*S][T] (keys < span[c]) -> probabilities
 hipError_t launch_attn_rows_softmax(float* a, const int* span, int B, int S, int T, hipStream_t s);
 // stamp pairs (earliest start, latest end) <- (UINT64_MAX, 0)
@@ -290,10 +333,20 @@ hipError_t init_mem_attributes();
 // bytes), per-row scales kscale [B * 512], per-chunk biased max exponent kemax [B]
 hipError_t launch_bank_pack_d8(const float* x, const float* ln_g, const float* ln_b, void* bank, float* kscale,
                                int* kemax, const int* span, int B, int T, int* ovf, hipStream_t s);
-hipError_t launch_dec_bank_d8(const float* qp, const void* bank, const float* kscale, const int* kemax,
-                              const float* signal, const int* span, float pad_val, float* out, int C, int T,
-                              hipStream_t s, unsigned long long* stamp, float* attn_dbg, size_t dbg_stride, int* ovf,
-                              bool nt = false, int grid = 0);
+struct BankD8Args {
+  const float* qp = nullptr;  // [C, 8*256] row-major
+  const void* bank = nullptr;
+  const float* kscale = nullptr;
+  const int* kemax = nullptr;
+  SrcMask mask;
+  float* out = nullptr;
+  int C = 0, T = 0;
+  AttnTap tap;
+  int* ovf = nullptr;
+  bool nt = false;  // stream the bank with non-temporal loads
+  int grid = 0;     // as MemAttnArgs.grid
+};
+hipError_t launch_dec_bank_d8(const BankD8Args& a, hipStream_t s);
 hipError_t init_bank8_attributes();
 // signal front end (frontend.hip): per-read normalisation (method 0 none, 1
 // median/MAD, 2 median/std; fp64 math, float32 out) of reads concatenated at
@@ -322,7 +375,7 @@ struct Sampling {
 // generator -> log_softmax -> argmax (or a sample) for a row, its token into
 // tok / out_tokens[row][step], score, optional logp dump [R][S][V], and the
 // next step's embedded input (ne).  Run by greedy_head_kernel, or by the
-// layer-0 self-attention of the next step (launch_dec_self_attention's head).
+// layer-0 self-attention of the next step (SelfAttnArgs.head).
 struct GreedyHead {
   const float* x = nullptr;
   const float* ln_g = nullptr;
@@ -337,17 +390,9 @@ struct GreedyHead {
   NextEmbed ne;
   Sampling smp;
 };
-GreedyHead make_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                            int V, int S, int min_len, int eos, int* tok, int* out_tokens, float* score,
-                            float* logp_dump, const NextEmbed& ne, const Sampling& smp);
 hipError_t check_greedy_head(const GreedyHead& h);
-// greedy head: LN_dec -> generator -> log_softmax -> argmax (or a sample);
-// writes token (next input + output [R, S] at column step), score, optional
-// logp dump, and the next step's embedded input (ne).
-hipError_t launch_dec_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw,
-                                  const float* gb, int V, int step, int S, int min_len, int eos, int* tok,
-                                  int* out_tokens, float* score, float* logp_dump, const NextEmbed& ne, int R,
-                                  hipStream_t s, const Sampling& smp = Sampling());
+// the standalone head of R rows: their token into column step of out_tokens
+hipError_t launch_dec_greedy_head(const GreedyHead& h, int step, int R, hipStream_t s);
 
 struct BeamState {
   float* cum;        // [C, beam] topk_log_probs
@@ -389,18 +434,29 @@ struct ClassicOpts {
   int ngram;       // -block_ngram_repeat (0: off)
   unsigned excl;   // -ignore_when_blocking token ids as a bit mask
 };
-hipError_t launch_beam_init(const BeamState& st, int C, int beam, int n_best, int S, int bos, hipStream_t s);
-hipError_t launch_beam_step(const NextEmbed& ne, const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                            int V, const BeamState& st, int C, int beam, int n_best, int step, int S, int min_len,
-                            int eos, float lenpen, hipStream_t s, const int* clist = nullptr, int ccap = 0);
+// the output head's weights and input rows (host-only): LN_dec (ln_g, ln_b) -> generator (gw, gb) over V tokens
+struct Generator {
+  const float* x = nullptr;
+  const float* ln_g = nullptr;
+  const float* ln_b = nullptr;
+  const float* gw = nullptr;
+  const float* gb = nullptr;
+  int V = 0;
+};
+// one search call: rows.C chunks of rows.rpc = beam_size rows (the tail's chunk list: the --fast beam only)
+struct BeamCall {
+  RowSet rows;
+  int n_best = 1, S = 0, min_len = 0, eos = 0;
+};
+hipError_t launch_beam_init(const BeamState& st, int C, int beam, int bos, hipStream_t s);
+hipError_t launch_beam_step(const NextEmbed& ne, const Generator& g, const BeamState& st, const BeamCall& b, int step,
+                            float lenpen, hipStream_t s);
 hipError_t launch_beam_finish(const BeamState& st, int C, int n_best, int S, int* tokens, float* scores, int* lens,
                               hipStream_t s);
 // classic Beam: length_penalty 0 none, 1 wu, 2 avg (onmt/translate/penalties.py)
 hipError_t launch_beam_classic_init(const BeamState& st, const int* group, int C, int beam, int bos, hipStream_t s);
-hipError_t launch_beam_classic_step(const NextEmbed& ne, const float* x, const float* ln_g, const float* ln_b,
-                                    const float* gw, const float* gb, int V, const BeamState& st, int C, int beam,
-                                    int n_best, int step, int S, int min_len, int eos, const ClassicOpts& o,
-                                    hipStream_t s);
+hipError_t launch_beam_classic_step(const NextEmbed& ne, const Generator& g, const BeamState& st, const BeamCall& b,
+                                    int step, const ClassicOpts& o, hipStream_t s);
 hipError_t launch_beam_classic_finish(const BeamState& st, int C, int beam, int n_best, int S, const ClassicOpts& o,
                                       int* tokens, float* scores, int* lens, hipStream_t s);
 // per-step softmax of the captured head-0 scores of R rows (row r belongs to
@@ -418,16 +474,22 @@ hipError_t launch_tf_embed(const int* gold, int bos, int V, const float* emb, co
                            int B, int L, hipStream_t s);
 // fp32 attention of Lq query rows per chunk (row c*Lq + i of q, pitch ldq, head h at column 32 h) over the
 // chunk's Lk key rows (row c*Lk + t of kv, pitch ldkv; K at column koff, V at voff): out [B*Lq, 256].
-// causal: keys j <= i (Lq == Lk; signal, span unused).  Otherwise keys t < span[c], those with
-// signal[c*Lk + t] == pad_val filled with ND_MASK_FILL (launch_dec_ctx_attention's masks).
-hipError_t launch_tf_attention(const float* q, int ldq, const float* kv, int ldkv, int koff, int voff,
-                               const float* signal, const int* span, float pad_val, float* out, int B, int Lq, int Lk,
-                               bool causal, hipStream_t s);
-// per row c*L + i of x (row-major): LN_dec -> generator -> log_softmax; tok_logp[c][i] (nullable) =
+// causal: keys j <= i (Lq == Lk; mask unused).  Otherwise the context attention's mask over Lk keys.
+struct TfAttnArgs {
+  const float* q = nullptr;
+  int ldq = 0;
+  const float* kv = nullptr;
+  int ldkv = 0, koff = 0, voff = 0;
+  SrcMask mask;
+  float* out = nullptr;
+  int B = 0, Lq = 0, Lk = 0;
+  bool causal = false;
+};
+hipError_t launch_tf_attention(const TfAttnArgs& a, hipStream_t s);
+// per row c*L + i of g.x (row-major): LN_dec -> generator -> log_softmax; tok_logp[c][i] (nullable) =
 // logp[gold[c][i]] for i < gold_len[c], else 0; score[c] = their sum in a fixed order; logp (nullable)
 // [B, L, V] every row's log-probabilities.  L <= 512, V <= 32.
-hipError_t launch_score_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                             int V, const int* gold, const int* gold_len, int B, int L, float* score, float* tok_logp,
-                             float* logp, hipStream_t s);
+hipError_t launch_score_head(const Generator& g, const int* gold, const int* gold_len, int B, int L, float* score,
+                             float* tok_logp, float* logp, hipStream_t s);
 
 }  // namespace nd

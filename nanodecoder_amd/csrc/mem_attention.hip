@@ -369,27 +369,26 @@ static constexpr size_t mem_lds_bytes() { return (size_t)MB_LDS_FLOATS * sizeof(
 static_assert(MB_LDS_FLOATS * 4 <= 160 * 1024, "LDS");
 static_assert(MB_NW * 512 * 4 <= MB_U, "merge slots overlap the q' image");
 
-hipError_t launch_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int* span,
-                                    float pad_val, float* out, int C, int rpc, int T, int ldT, hipStream_t s,
-                                    unsigned long long* stamp, float* attn_dbg, size_t dbg_stride, int grid) {
-  if (rpc != 1 || T < 1 || T > 512 || ldT < T || C < 1 || grid < 0) return hipErrorInvalidValue;
+// The forms of the kernel: the tile count as a compile-time constant for chunks of 257..512 samples (the
+// 512-sample chunks of every bench batch; the reference authors' production runs use 300);
+// shorter ones take the runtime count (form 0)
+template <typename F>
+static void mem_form(int tiles, F&& f) {
+  pick_form<0, 5, 6, 7, 8>(tiles >= 5 ? tiles : 0, [&](auto N) { f(dec_mem_attention_kernel<decltype(N)::value>); });
+}
+
+hipError_t launch_dec_mem_attention(const MemAttnArgs& a, hipStream_t s) {
+  const int C = a.C, T = a.T;
+  if (a.rpc != 1 || T < 1 || T > 512 || a.ldT < T || C < 1 || a.grid < 0) return hipErrorInvalidValue;
+  int grid = a.grid;
 #ifdef MB_NO_WALK  // timing variant only (tools/build_variant.sh): one workgroup per chunk always
   grid = 0;
 #endif
   const int G = grid > 0 ? std::min(C, grid) : C;
-  // the tile count as a compile-time constant for chunks of 257..512 samples (the 512-sample chunks of every bench
-  // batch; the reference authors' production runs use 300); shorter ones take the runtime count
-#define ND_MEM_GO(N)                                                                                              \
-  hipLaunchKernelGGL((dec_mem_attention_kernel<N>), dim3(G), dim3(MB_NW * 64), mem_lds_bytes(), s, qp, mem, signal, \
-                     span, pad_val, out, T, ldT, stamp, attn_dbg, dbg_stride, C)
-  switch ((T + MB_TILE - 1) / MB_TILE) {
-    case 8: ND_MEM_GO(8); break;
-    case 7: ND_MEM_GO(7); break;
-    case 6: ND_MEM_GO(6); break;
-    case 5: ND_MEM_GO(5); break;
-    default: ND_MEM_GO(0); break;
-  }
-#undef ND_MEM_GO
+  mem_form((T + MB_TILE - 1) / MB_TILE, [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(G), dim3(MB_NW * 64), mem_lds_bytes(), s, a.qp, a.mem, a.mask.signal, a.mask.span,
+                       a.mask.pad_val, a.out, T, a.ldT, a.tap.stamp, a.tap.dbg, a.tap.dbg_stride, C);
+  });
   return hipGetLastError();
 }
 
@@ -460,14 +459,13 @@ hipError_t launch_stamp_reset(unsigned long long* stamps, int pairs, hipStream_t
 }
 
 hipError_t init_mem_attributes() {
-  const void* fns[] = {(const void*)dec_mem_attention_kernel<0>, (const void*)dec_mem_attention_kernel<5>,
-                       (const void*)dec_mem_attention_kernel<6>, (const void*)dec_mem_attention_kernel<7>,
-                       (const void*)dec_mem_attention_kernel<8>};
-  for (const void* f : fns) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mem_lds_bytes());
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  hipError_t e = hipSuccess;
+  for (int tiles = 0; tiles <= 512 / MB_TILE; ++tiles)
+    mem_form(tiles, [&](auto kern) {
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)mem_lds_bytes());
+    });
+  return e;
 }
 
 }  // namespace nd

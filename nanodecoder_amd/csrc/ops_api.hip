@@ -212,7 +212,8 @@ int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* sp
 
 int nd_op_dec_self_attention(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
                              int32_t max_steps, float* out, int32_t R, void* stream) {
-  hipError_t e = nd::launch_dec_self_attention(qkv, cache, anc, anc_ld, step, max_steps, out, R, (hipStream_t)stream);
+  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
+                                                .max_steps = max_steps, .out = out, .R = R}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -222,8 +223,9 @@ int nd_op_dec_self_attention_beam(const float* qkv, float* cache, const int32_t*
                                   void* stream) {
   if (!qkv || !cache || !anc || !out || rpc < 2 || rpc > 8 || R % rpc)
     return fail(ND_ERR_ARG, "dec_self_attention_beam: bad arguments");
-  hipError_t e = nd::launch_dec_self_attention(qkv, cache, anc, anc_ld, step, max_steps, out, R, (hipStream_t)stream,
-                                               rpc, done);
+  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
+                                                .max_steps = max_steps, .out = out, .R = R,
+                                                .rows = {.C = R / rpc, .rpc = rpc, .done = done}}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_beam: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -233,9 +235,10 @@ int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* a
                                  void* stream) {
   if (!qkv || !cache || !out || rpc < 1 || rpc > 8 || R % rpc || (rpc > 1 && !anc))
     return fail(ND_ERR_ARG, "dec_self_attention_q24: bad arguments");
-  hipError_t e = nd::launch_dec_self_attention(qkv, static_cast<float*>(cache), anc, anc_ld, step, max_steps, out, R,
-                                               (hipStream_t)stream, rpc, done, nd::QkvRows(), nullptr, nullptr, 0,
-                                               true);
+  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = static_cast<float*>(cache), .anc = anc,
+                                                .anc_ld = anc_ld, .step = step, .max_steps = max_steps, .out = out,
+                                                .R = R, .rows = {.C = R / rpc, .rpc = rpc, .done = done}, .q24 = true},
+                                               (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_q24: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -245,15 +248,9 @@ int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int3
                                    int32_t max_steps, float* out, int32_t R, void* stream) {
   if (!table || !tok || !hist || !out || R < 1 || V < 1 || step < 0 || step >= table_steps)
     return fail(ND_ERR_ARG, "dec_self_attention_table: bad arguments");
-  nd::QkvRows qr;
-  qr.tok = tok;
-  qr.V = V;
-  qr.tok0 = tok0;
-  qr.rm = 1;
-  qr.hist = hist;
-  qr.hist_ld = hist_ld;
-  hipError_t e = nd::launch_dec_self_attention(table, cache, nullptr, 0, step, max_steps, out, R, (hipStream_t)stream, 1,
-                                               nullptr, qr);
+  const nd::QkvRows qr{.tok = tok, .V = V, .tok0 = tok0, .rm = 1, .hist = hist, .hist_ld = hist_ld};
+  hipError_t e = nd::launch_dec_self_attention({.qkv = table, .cache = cache, .step = step, .max_steps = max_steps,
+                                                .out = out, .R = R, .rows = {.C = R}, .qr = qr}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_table: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -261,8 +258,8 @@ int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int3
 int nd_op_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int32_t* span, float pad_val,
                             float* out, int32_t C, int32_t rpc, int32_t T, int32_t ldT, int32_t grid, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  hipError_t e = nd::launch_dec_mem_attention(qp, mem, signal, span, pad_val, out, C, rpc, T, ldT, (hipStream_t)stream,
-                                              nullptr, nullptr, 0, grid);
+  hipError_t e = nd::launch_dec_mem_attention({.qp = qp, .mem = mem, .mask = {signal, span, pad_val}, .out = out, .C = C,
+                                               .rpc = rpc, .T = T, .ldT = ldT, .grid = grid}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_mem_attention: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -317,8 +314,9 @@ int nd_op_dec_bank_d8(const float* qp, const void* bank, const float* kscale, co
   if (int rc = ensure_attributes()) return rc;
   if (!qp || !bank || !kscale || !kemax || !signal || !span || !out || grid < 0)
     return fail(ND_ERR_ARG, "dec_bank_d8: bad arguments");
-  hipError_t e = nd::launch_dec_bank_d8(qp, bank, kscale, kemax, signal, span, pad_val, out, C, T,
-                                        (hipStream_t)stream, nullptr, nullptr, 0, ovf, false, grid);
+  hipError_t e = nd::launch_dec_bank_d8({.qp = qp, .bank = bank, .kscale = kscale, .kemax = kemax,
+                                         .mask = {signal, span, pad_val}, .out = out, .C = C, .T = T, .ovf = ovf,
+                                         .grid = grid}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_bank_d8: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -327,7 +325,8 @@ int nd_op_dec_ctx_attention(const float* q, const float* kv, int32_t ld, int32_t
                             const int32_t* span, float pad_val, float* out, int32_t C, int32_t rpc, int32_t T,
                             void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  hipError_t e = nd::launch_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, out, C, rpc, T,
+  hipError_t e = nd::launch_dec_ctx_attention({.q = q, .kv = kv, .ld = ld, .koff = koff, .T = T, .out = out,
+                                               .mask = {signal, span, pad_val}, .rows = {.C = C, .rpc = rpc}},
                                               (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention: ") + hipGetErrorString(e));
   return ND_OK;
@@ -336,8 +335,9 @@ int nd_op_dec_ctx_attention(const float* q, const float* kv, int32_t ld, int32_t
 int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
                        const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
                        int32_t Lk, int32_t causal, void* stream) {
-  hipError_t e = nd::launch_tf_attention(q, ldq, kv, ldkv, koff, voff, signal, span, pad_val, out, B, Lq, Lk,
-                                         causal != 0, (hipStream_t)stream);
+  hipError_t e = nd::launch_tf_attention({.q = q, .ldq = ldq, .kv = kv, .ldkv = ldkv, .koff = koff, .voff = voff,
+                                          .mask = {signal, span, pad_val}, .out = out, .B = B, .Lq = Lq, .Lk = Lk,
+                                          .causal = causal != 0}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("tf_attention: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -357,9 +357,10 @@ int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int
   if (int rc = ensure_attributes()) return rc;
   if (!q || !kv || !signal || !span || !out || !clist || (nsplit > 1 && !part))
     return fail(ND_ERR_ARG, "dec_ctx_attention_list: bad arguments");
-  hipError_t e = nd::launch_dec_ctx_attention(q, kv, ld, koff, signal, span, pad_val, out, C, rpc, T,
-                                              (hipStream_t)stream, nullptr, nullptr, 0, done, q24 != 0, clist, ccap,
-                                              nsplit, part);
+  hipError_t e = nd::launch_dec_ctx_attention(
+      {.q = q, .kv = kv, .ld = ld, .koff = koff, .q24 = q24 != 0, .T = T, .out = out, .mask = {signal, span, pad_val},
+       .rows = {.C = C, .rpc = rpc, .done = done, .clist = clist, .ccap = ccap}, .nsplit = nsplit, .part = part},
+      (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_list: ") + hipGetErrorString(e));
   return ND_OK;
 }
@@ -378,8 +379,9 @@ int nd_op_dec_ctx_attention_q24(const float* q, const void* kvq, int32_t layers,
   if (!q || !kvq || !signal || !span || !out || layer < 0 || layer >= layers)
     return fail(ND_ERR_ARG, "dec_ctx_attention_q24: bad arguments");
   const uint8_t* plane = static_cast<const uint8_t*>(kvq) + (size_t)layer * C * T * CTXQ_ROW;
-  hipError_t e = nd::launch_dec_ctx_attention(q, plane, CTXQ_ROW, 0, signal, span, pad_val, out, C, rpc, T,
-                                              (hipStream_t)stream, nullptr, nullptr, 0, nullptr, true);
+  hipError_t e = nd::launch_dec_ctx_attention({.q = q, .kv = plane, .ld = CTXQ_ROW, .koff = 0, .q24 = true, .T = T,
+                                               .out = out, .mask = {signal, span, pad_val},
+                                               .rows = {.C = C, .rpc = rpc}}, (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_q24: ") + hipGetErrorString(e));
   return ND_OK;
 }

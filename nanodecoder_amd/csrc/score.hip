@@ -207,21 +207,22 @@ tf_attention_kernel(const float* __restrict__ q, int ldq, const float* __restric
   }
 }
 
-hipError_t launch_tf_attention(const float* q, int ldq, const float* kv, int ldkv, int koff, int voff,
-                               const float* signal, const int* span, float pad_val, float* out, int B, int Lq, int Lk,
-                               bool causal, hipStream_t s) {
-  if (!q || !kv || !out || B < 1 || B > 65535 || Lq < 1 || Lk < 1) return hipErrorInvalidValue;
-  if (ldq < ND_D || ldkv < ND_D || (ldq | ldkv | koff | voff) % 4 || koff < 0 || voff < 0 || koff + ND_D > ldkv ||
-      voff + ND_D > ldkv)
+hipError_t launch_tf_attention(const TfAttnArgs& a, hipStream_t s) {
+  const SrcMask& m = a.mask;
+  if (!a.q || !a.kv || !a.out || a.B < 1 || a.B > 65535 || a.Lq < 1 || a.Lk < 1) return hipErrorInvalidValue;
+  if (a.ldq < ND_D || a.ldkv < ND_D || (a.ldq | a.ldkv | a.koff | a.voff) % 4 || a.koff < 0 || a.voff < 0 ||
+      a.koff + ND_D > a.ldkv || a.voff + ND_D > a.ldkv)
     return hipErrorInvalidValue;
-  if (causal ? Lq != Lk : (!signal || !span)) return hipErrorInvalidValue;
-  const dim3 grid(ND_H, (Lq + TF_NW * 32 - 1) / (TF_NW * 32), B), block(TF_NW * 64);
-  if (causal)
-    hipLaunchKernelGGL(tf_attention_kernel<true>, grid, block, 0, s, q, ldq, kv, ldkv, koff, voff, signal, span, pad_val,
-                       out, Lq, Lk);
+  if (a.causal ? a.Lq != a.Lk : (!m.signal || !m.span)) return hipErrorInvalidValue;
+  const dim3 grid(ND_H, (a.Lq + TF_NW * 32 - 1) / (TF_NW * 32), a.B), block(TF_NW * 64);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, grid, block, 0, s, a.q, a.ldq, a.kv, a.ldkv, a.koff, a.voff, m.signal, m.span, m.pad_val,
+                       a.out, a.Lq, a.Lk);
+  };
+  if (a.causal)
+    go(tf_attention_kernel<true>);
   else
-    hipLaunchKernelGGL(tf_attention_kernel<false>, grid, block, 0, s, q, ldq, kv, ldkv, koff, voff, signal, span,
-                       pad_val, out, Lq, Lk);
+    go(tf_attention_kernel<false>);
   return hipGetLastError();
 }
 
@@ -315,12 +316,11 @@ score_head_kernel(const float* __restrict__ x, const float* __restrict__ ln_g, c
   }
 }
 
-hipError_t launch_score_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                             int V, const int* gold, const int* gold_len, int B, int L, float* score, float* tok_logp,
-                             float* logp, hipStream_t s) {
-  if (B < 1 || L < 1 || L > TF_MAXL || V < 1 || V > ND_MAXV || !score) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(score_head_kernel, dim3(B), dim3(TF_HW * 64), 0, s, x, ln_g, ln_b, gw, gb, V, gold, gold_len, L,
-                     score, tok_logp, logp);
+hipError_t launch_score_head(const Generator& g, const int* gold, const int* gold_len, int B, int L, float* score,
+                             float* tok_logp, float* logp, hipStream_t s) {
+  if (B < 1 || L < 1 || L > TF_MAXL || g.V < 1 || g.V > ND_MAXV || !score) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(score_head_kernel, dim3(B), dim3(TF_HW * 64), 0, s, g.x, g.ln_g, g.ln_b, g.gw, g.gb, g.V, gold,
+                     gold_len, L, score, tok_logp, logp);
   return hipGetLastError();
 }
 

@@ -18,40 +18,13 @@ __global__ void __launch_bounds__(256) greedy_head_kernel(GreedyHead h, int step
   greedy_head_row(h, r, step, lane, lps[w]);
 }
 
-GreedyHead make_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                            int V, int S, int min_len, int eos, int* tok, int* out_tokens, float* score,
-                            float* logp_dump, const NextEmbed& ne, const Sampling& smp) {
-  GreedyHead h;
-  h.x = x;
-  h.ln_g = ln_g;
-  h.ln_b = ln_b;
-  h.gw = gw;
-  h.gb = gb;
-  h.V = V;
-  h.S = S;
-  h.min_len = min_len;
-  h.eos = eos;
-  h.tok = tok;
-  h.out_tokens = out_tokens;
-  h.score = score;
-  h.logp_dump = logp_dump;
-  h.ne = ne;
-  h.smp = smp;
-  return h;
-}
-
 hipError_t check_greedy_head(const GreedyHead& h) {
   if (h.V > ND_MAXV || h.V < 1 || !h.ne.emb || !h.ne.x || !h.ne.part) return hipErrorInvalidValue;
   if (h.smp.seed && (h.smp.temp == 0.f || h.smp.topk == 1 || h.smp.topk > h.V)) return hipErrorInvalidValue;
   return hipSuccess;
 }
 
-hipError_t launch_dec_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw,
-                                  const float* gb, int V, int step, int S, int min_len, int eos, int* tok,
-                                  int* out_tokens, float* score, float* logp_dump, const NextEmbed& ne, int R,
-                                  hipStream_t s, const Sampling& smp) {
-  const GreedyHead h = make_greedy_head(x, ln_g, ln_b, gw, gb, V, S, min_len, eos, tok, out_tokens, score, logp_dump,
-                                        ne, smp);
+hipError_t launch_dec_greedy_head(const GreedyHead& h, int step, int R, hipStream_t s) {
   const hipError_t e = check_greedy_head(h);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(greedy_head_kernel, dim3((R + 3) / 4), dim3(256), 0, s, h, step, R);
@@ -76,9 +49,7 @@ beam_init_kernel(BeamState st, int C, int beam, int bos) {
   if (c == 0) *st.n_alive = C;
 }
 
-hipError_t launch_beam_init(const BeamState& st, int C, int beam, int n_best, int S, int bos, hipStream_t s) {
-  (void)n_best;
-  (void)S;
+hipError_t launch_beam_init(const BeamState& st, int C, int beam, int bos, hipStream_t s) {
   hipLaunchKernelGGL(beam_init_kernel, dim3((C + 63) / 64), dim3(64), 0, s, st, C, beam, bos);
   return hipGetLastError();
 }
@@ -205,13 +176,14 @@ beam_step_kernel(NextEmbed ne, const float* __restrict__ x, const float* __restr
   }
 }
 
-hipError_t launch_beam_step(const NextEmbed& ne, const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
-                            int V, const BeamState& st, int C, int beam, int n_best, int step, int S, int min_len,
-                            int eos, float lenpen, hipStream_t s, const int* clist, int ccap) {
+hipError_t launch_beam_step(const NextEmbed& ne, const Generator& g, const BeamState& st, const BeamCall& b, int step,
+                            float lenpen, hipStream_t s) {
+  const int beam = b.rows.rpc, C = b.rows.C, V = g.V, ccap = b.rows.ccap;
+  const int* clist = b.rows.clist;
   if (beam > BEAM_MAX || beam * V > 256 || V > ND_MAXV || !ne.emb || !ne.x || !ne.part) return hipErrorInvalidValue;
   if (clist && (ccap < 1 || ccap > C)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(beam_step_kernel, dim3(clist ? ccap : C), dim3(256), 0, s, ne, x, ln_g, ln_b, gw, gb, V, st, beam,
-                     n_best, step, S, min_len, eos, lenpen, clist);
+  hipLaunchKernelGGL(beam_step_kernel, dim3(clist ? ccap : C), dim3(256), 0, s, ne, g.x, g.ln_g, g.ln_b, g.gw, g.gb, V,
+                     st, beam, b.n_best, step, b.S, b.min_len, b.eos, lenpen, clist);
   return hipGetLastError();
 }
 
@@ -491,16 +463,16 @@ beam_classic_step_kernel(NextEmbed ne, const float* __restrict__ x, const float*
   }
 }
 
-hipError_t launch_beam_classic_step(const NextEmbed& ne, const float* x, const float* ln_g, const float* ln_b,
-                                    const float* gw, const float* gb, int V, const BeamState& st, int C, int beam,
-                                    int n_best, int step, int S, int min_len, int eos, const ClassicOpts& o,
-                                    hipStream_t s) {
+hipError_t launch_beam_classic_step(const NextEmbed& ne, const Generator& g, const BeamState& st, const BeamCall& b,
+                                    int step, const ClassicOpts& o, hipStream_t s) {
+  const int beam = b.rows.rpc, V = g.V, S = b.S;
+  if (b.rows.done || b.rows.clist) return hipErrorInvalidValue;  // the --fast beam's
   if (beam > BEAM_MAX || beam * V > 256 || V > ND_MAXV || V < beam || !ne.emb || !ne.x || !ne.part)
     return hipErrorInvalidValue;
   if (o.cov_kind != 0 && (!st.attn || !st.cut || !st.cov[0] || !st.cov[1])) return hipErrorInvalidValue;
   if (o.ngram < 0 || o.ngram > S || (o.ngram > 0 && (!st.blk[0] || !st.blk[1]))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(beam_classic_step_kernel, dim3(C), dim3(256), 0, s, ne, x, ln_g, ln_b, gw, gb, V, st, beam,
-                     n_best, step, S, min_len, eos, o);
+  hipLaunchKernelGGL(beam_classic_step_kernel, dim3(b.rows.C), dim3(256), 0, s, ne, g.x, g.ln_g, g.ln_b, g.gw, g.gb, V,
+                     st, beam, b.n_best, step, S, b.min_len, b.eos, o);
   return hipGetLastError();
 }
 
