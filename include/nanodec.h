@@ -233,6 +233,37 @@ int nd_normalize_reads(const double* d_raw, const int64_t* d_offsets, int32_t R,
 int nd_window_reads(const float* d_sig, const int64_t* d_offsets, const int32_t* d_read, const int32_t* d_start,
                     const int32_t* d_len, int32_t C, int32_t T, float* d_signal, void* stream);
 
+/* Read assembly (utils/labelop.py:310-352, add_count / simple_assembly with
+ * flag_intersection, and the argmax + index2base of translate.py:84-87) for a
+ * group of R reads in one call.  d_bases [total_bases] u8: every chunk's best
+ * hypothesis as ASCII with the spaces removed, concatenated; chunk c is
+ * d_chunk_off[c] .. d_chunk_off[c+1] (C + 1 offsets, empty chunks allowed and
+ * skipped as the reference drops them), read r owns the consecutive chunks
+ * d_read_off[r] .. d_read_off[r+1] (R + 1 offsets).  Consecutive non-empty
+ * chunks are aligned by their longest common substring (the longest, then the
+ * earliest in the first chunk, then the earliest in the second; no shared
+ * character: displacement la - lb), exactly difflib's longest matching block
+ * while the second chunk has fewer than 200 chars; the chunks vote per column
+ * and class (A C G T M, case folded) and the column's call is the class with
+ * the most votes, the lowest on a tie.
+ *   d_seq     [total_bases] u8: read r's bases start at byte
+ *             d_chunk_off[d_read_off[r]] (a consensus is never longer than the
+ *             sum of its chunks); bytes past a read's length are 0
+ *   d_seq_len [R] i32: bases of read r, or -1 when d_status[r] != 0
+ *   d_status  [R] i32: 0 = assembled.  Bit 0: some chunk has 200 or more
+ *             chars (difflib's autojunk heuristic starts there and changes the
+ *             block found; that regime is not reproduced).  Bit 1: some char's
+ *             upper case is not one of A C G T M.  The caller assembles such a
+ *             read on the host.
+ * d_work holds nd_assemble_reads_work_bytes(C, total_bases) bytes.  Null
+ * buffers, negative sizes, total_bases >= 2^31 or a smaller work_bytes return
+ * ND_ERR_ARG before any HIP call; R == 0 returns ND_OK at once.  Everything is
+ * enqueued on `stream`: no allocation, no synchronisation.  No context needed. */
+int64_t nd_assemble_reads_work_bytes(int32_t C, int64_t total_bases);
+int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R,
+                      int32_t C, int64_t total_bases, uint8_t* d_seq, int32_t* d_seq_len, int32_t* d_status,
+                      void* d_work, int64_t work_bytes, void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

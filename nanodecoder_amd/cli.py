@@ -110,10 +110,12 @@ def _extract(args):
         return ["!" + prefix, repr(e)]
 
 
-def write_output(opt, file_src, all_predictions, time_translate):
-    """translate.py:81-98."""
+def write_output(opt, file_src, all_predictions, time_translate, sequence=None):
+    """translate.py:81-98.  ``sequence``: the read already assembled
+    (-assembly gpu); None assembles it here."""
     try:
-        c_bpread = frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
+        c_bpread = sequence if sequence is not None else \
+            frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
         name = file_src.split(".txt")[0]
         with open(os.path.join(opt.save_data, "result", name + ".fasta"), "w") as f:
             f.writelines(">%s\n%s" % (name, c_bpread))
@@ -127,9 +129,13 @@ def write_output(opt, file_src, all_predictions, time_translate):
         print("!!!error!!!data src: " + file_src.split(".txt")[0])
 
 
+ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled / of them on the host, this run
+
+
 def main(opt=None):
     opt = opt or parse_translate_opts()
     logger = init_logger(opt.log_file)
+    ASSEMBLY_STATS.update(reads=0, fallback=0)
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
         os.makedirs(os.path.join(opt.save_data, sub), exist_ok=True)
     from .translator import build_translator
@@ -160,6 +166,9 @@ def main(opt=None):
         if pending:
             n_done += _run_group(opt, translator, pending, gpu_fe)
     logger.info("translated %d reads in %.1f s" % (n_done, time.time() - t_start))
+    if getattr(opt, "assembly", "cpu") == "gpu":
+        logger.info("-assembly gpu: %d of %d reads were assembled on the host (fallback: a chunk of 200 or more "
+                    "bases, or text outside ACGTM)" % (ASSEMBLY_STATS["fallback"], ASSEMBLY_STATS["reads"]))
     return n_done
 
 
@@ -192,8 +201,19 @@ def _translate_group(opt, translator, group, raw=False):
         return 0
     dt = time.time() - t0
     total = max(1, sum(len(preds) for _, preds in outs))
-    for g, (_, preds) in zip(group, outs):
-        write_output(opt, g[0], preds, dt * len(preds) / total)
+    seqs = [None] * len(outs)
+    if getattr(opt, "assembly", "cpu") == "gpu":
+        # the whole group in one device call; a read left None (its host fallback raised) is assembled
+        # again by write_output, which reports that read's error as -assembly cpu does
+        try:
+            seqs = frontend.assemble_reads([preds for _, preds in outs], opt.src_seq_length, opt.src_seq_stride,
+                                           device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True)
+        except Exception as e:
+            for g in group:
+                print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
+            return 0
+    for g, (_, preds), seq in zip(group, outs, seqs):
+        write_output(opt, g[0], preds, dt * len(preds) / total, sequence=seq)
     return len(group)
 
 

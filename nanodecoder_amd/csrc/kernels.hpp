@@ -355,6 +355,15 @@ hipError_t launch_read_normalize(const double* raw, const long long* off, int R,
                                  hipStream_t s);
 hipError_t launch_read_window(const float* sig, const long long* off, const int* rd, const int* start,
                               const int* len, int C, int T, float* out, hipStream_t s);
+// read assembly (assembly.hip): the overlap consensus of utils/labelop.py:310-352 for R reads whose chunk
+// strings (ASCII, spaces removed) are concatenated in bases[total]: chunk c = chunk_off[c] .. chunk_off[c+1],
+// read r = chunks read_off[r] .. read_off[r+1].  Read r's bases go to seq at chunk_off[read_off[r]], their
+// count to seq_len[r]; status[r] != 0 (bit 0: a chunk of 200 or more chars, bit 1: a char outside ACGTM) means
+// the read was not assembled (seq_len[r] = -1).  work holds assemble_work_bytes(C, total) bytes
+size_t assemble_work_bytes(int C, long long total);
+hipError_t launch_assemble_reads(const unsigned char* bases, const int* chunk_off, const int* read_off, int R, int C,
+                                 int total, unsigned char* seq, int* seq_len, int* status, void* work,
+                                 hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

@@ -1,5 +1,5 @@
-// libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads): single
-// launches on the caller's stream, with no context.  The nd_op_* calls exist for the op-level tests.
+// libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
+// nd_assemble_reads): launches on the caller's stream, with no context.  The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
 static hipError_t gemm(const float* A, int lda, const float* W, int N, int K, const float* bias, float* C, int ldc,
@@ -289,6 +289,29 @@ int nd_window_reads(const float* d_sig, const int64_t* d_offsets, const int32_t*
   hipError_t e = nd::launch_read_window(d_sig, (const long long*)d_offsets, d_read, d_start, d_len, C, T, d_signal,
                                         (hipStream_t)stream);
   if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("window_reads: ") + hipGetErrorString(e));
+  return ND_OK;
+}
+
+int64_t nd_assemble_reads_work_bytes(int32_t C, int64_t total_bases) {
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases) : -1;
+}
+
+int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R,
+                      int32_t C, int64_t total_bases, uint8_t* d_seq, int32_t* d_seq_len, int32_t* d_status,
+                      void* d_work, int64_t work_bytes, void* stream) {
+  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "assemble_reads: R, C and total_bases must be >= 0 and total_bases < 2^31");
+  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "assemble_reads: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_assemble_reads_work_bytes asks for");
+  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
+      (total_bases > 0 && (!d_bases || !d_seq)))
+    return fail(ND_ERR_ARG, "assemble_reads: null buffer");
+  if (R == 0) return ND_OK;
+  hipError_t e = nd::launch_assemble_reads(d_bases, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq, d_seq_len,
+                                           d_status, d_work, (hipStream_t)stream);
+  if (e != hipSuccess) return fail(ND_ERR_HIP, std::string("assemble_reads: ") + hipGetErrorString(e));
   return ND_OK;
 }
 

@@ -200,3 +200,113 @@ def assemble_read(all_predictions, src_seq_length: int, src_seq_stride: int) -> 
     if src_seq_stride < src_seq_length:
         return index2base(np.argmax(simple_assembly(all_predictions), axis=0))
     return simple_assembly(all_predictions, flag_intersection=False)
+
+
+# ---------------------------------------------------------------- assembly on the device (-assembly gpu)
+ASM_STATUS_LONG = 1   # include/nanodec.h nd_assemble_reads: a chunk of 200 or more chars (difflib autojunk)
+ASM_STATUS_CHAR = 2   # a char whose upper case is not in BASE_KEYS
+
+
+def pack_assembly_input(reads):
+    """The input of nd_assemble_reads for a group of reads (each the
+    all_predictions assemble_read takes): every chunk's x[0] with the spaces
+    removed, as ASCII bytes, concatenated.  Returns (bases uint8 [total],
+    chunk_off int32 [C + 1], read_off int32 [R + 1], host): read r owns chunks
+    read_off[r] .. read_off[r+1], one per prediction, empty ones included.
+    ``host`` lists the reads kept back for assemble_read: text that is not
+    ASCII, and a hypothesis of nothing but spaces (simple_assembly drops ""
+    before it removes the spaces, so that one stays in its chunk list as an
+    empty string).  Such a read is packed with no chunks."""
+    lens, parts, host = [], [], []
+    read_off = np.zeros(len(reads) + 1, np.int64)
+    for r, preds in enumerate(reads):
+        strs = [x[0].replace(" ", "") for x in preds]
+        try:
+            if any(s == "" and x[0] != "" for s, x in zip(strs, preds)):
+                raise ValueError("a hypothesis of spaces")
+            raw = "".join(strs).encode("ascii")
+        except ValueError:  # UnicodeEncodeError is one
+            host.append(r)
+            read_off[r + 1] = read_off[r]
+            continue
+        parts.append(raw)
+        lens.extend(len(s) for s in strs)
+        read_off[r + 1] = read_off[r] + len(strs)
+    chunk_off = np.zeros(len(lens) + 1, np.int64)
+    chunk_off[1:] = np.cumsum(np.asarray(lens, np.int64))
+    if chunk_off[-1] >= 2 ** 31:
+        raise ValueError("more than 2^31 - 1 bases in one assembly group")
+    bases = np.frombuffer(bytearray(b"").join(parts), np.uint8)  # a bytearray: writable, as torch.from_numpy wants
+    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
+
+
+def _assemble_device(bases, chunk_off, read_off, device):
+    """One nd_assemble_reads call on the CURRENT stream of ``device``:
+    (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    R, C, total = len(read_off) - 1, len(chunk_off) - 1, int(bases.size)
+    L = _lib.lib()
+    work_bytes = int(L.nd_assemble_reads_work_bytes(C, total))
+    with torch.cuda.device(dev):
+        off_d = _pinned(np.concatenate([chunk_off, read_off])).to(dev, non_blocking=True)
+        bases_d = _pinned(bases).to(dev, non_blocking=True)
+        seq_d = torch.empty(total, dtype=torch.uint8, device=dev)
+        out_d = torch.empty(2, R, dtype=torch.int32, device=dev)  # seq_len, status
+        work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        _lib.check(L.nd_assemble_reads(p(bases_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d), p(out_d[0]),
+                                       p(out_d[1]), p(work_d), work_bytes, stream), "nd_assemble_reads")
+        out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
+        seq = seq_d.cpu().numpy()
+    return seq, out[0], out[1]
+
+
+def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None, stats=None,
+                   defer_errors: bool = False):
+    """assemble_read for a group of reads: one string per read.
+
+    ``device=None``, or ``src_seq_stride >= src_seq_length`` (translate.py's
+    concatenation branch: nothing to align), is exactly
+    ``[assemble_read(p, ...) for p in reads]``.  Otherwise the whole group is
+    assembled by one nd_assemble_reads call (assembly.hip) on the current
+    torch stream of ``device``, and every read the device does not assemble
+    (a chunk of 200 or more chars, a char outside BASE_KEYS, text
+    pack_assembly_input kept back) goes through assemble_read on the host,
+    which raises for it whatever it raises.  That fallback is per read and
+    counted: ``stats`` (a dict) gets its "reads" and "fallback" entries
+    increased by the reads of this call and by those assembled on the host.
+    ``defer_errors``: a read whose host assembly raises yields None instead
+    (the caller assembles it again where it handles that read's errors)."""
+    reads = list(reads)
+    if device is None or src_seq_stride >= src_seq_length:
+        return [assemble_read(p, src_seq_length, src_seq_stride) for p in reads]
+    bases, chunk_off, read_off, host = pack_assembly_input(reads)
+    R = len(reads)
+    out = [""] * R  # no bases at all: every device read is ""
+    todo = set(host)
+    if bases.size:
+        seq, seq_len, status = _assemble_device(bases, chunk_off, read_off, device)
+        raw = seq.tobytes()
+        start = chunk_off[read_off[:-1]]
+        for r in range(R):
+            if status[r] != 0:
+                todo.add(r)
+            elif seq_len[r] > 0:
+                out[r] = raw[start[r]: start[r] + seq_len[r]].decode("ascii")
+    if stats is not None:
+        stats["reads"] = stats.get("reads", 0) + R
+        stats["fallback"] = stats.get("fallback", 0) + len(todo)
+    for r in sorted(todo):
+        try:
+            out[r] = assemble_read(reads[r], src_seq_length, src_seq_stride)
+        except Exception:
+            if not defer_errors:
+                raise
+            out[r] = None
+    return out

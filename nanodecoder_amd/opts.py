@@ -73,6 +73,10 @@ def translate_parser() -> argparse.ArgumentParser:
     _add(g, "seed", type=int, default=-1, help="random sampling seed (-1: fresh entropy per run)")
     _add(g, "frontend", default="cpu", choices=["cpu", "gpu"],
          help="gpu: normalise and window the reads on the GPU (frontend.hip) instead of in the worker pool")
+    _add(g, "assembly", default="cpu", choices=["cpu", "gpu"],
+         help="gpu: assemble each group's overlapping chunks into reads on the GPU (assembly.hip; the same "
+              "bytes; a read it does not cover is assembled on the host and counted in the log) instead of "
+              "read by read in Python")
     return p
 
 
