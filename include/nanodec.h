@@ -356,8 +356,8 @@ const char* nd_version(void);
  * which kernels a workload of a given size runs (gemm.hip launch_gemm_p16 /
  * launch_gemm pick the kernel from M, N, K). */
 #define ND_ROUTE_P16_SMALL 0   /* gemm_p16_kernel<1,4,64>  (K = 256, few row blocks) */
-#define ND_ROUTE_P16_N64 1     /* gemm_p16_kernel<4,2,128> (K = 256) */
-#define ND_ROUTE_P16_LN128 2   /* gemm_p16_kernel<8,1,256> (K = 256, LN prologue) */
+#define ND_ROUTE_P16_N64 1     /* retired, always 0: no shape reached its kernel (the index is kept) */
+#define ND_ROUTE_P16_LN128 2   /* retired, always 0 (likewise) */
 #define ND_ROUTE_P16S_2X4 3    /* gemm_p16s_kernel<2,4>    (K = 256, LDS-staged, 32-row blocks) */
 #define ND_ROUTE_P16S_2X2 4    /* gemm_p16s_kernel<2,2> */
 #define ND_ROUTE_P16_LONGK 5   /* gemm_p16_kernel<1,8,*>   (K = 512 / 1024 / 2048) */

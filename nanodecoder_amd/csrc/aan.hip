@@ -77,12 +77,10 @@ aan_gate_kernel(const float* __restrict__ g, const float* __restrict__ xn, const
   }
 }
 
-hipError_t launch_aan_prep(const float* x, const float* ln_g, const float* ln_b, float* hist, const int* anc,
-                           int anc_ld, int step, int max_steps, float* xn, float* avg, float* avg_part, int R,
-                           hipStream_t s) {
-  if (step < 0 || step >= max_steps) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(aan_prep_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, ln_g, ln_b, hist, anc, anc_ld, step,
-                     max_steps, xn, avg, avg_part, R);
+hipError_t launch_aan_prep(const AanPrepArgs& a, hipStream_t s) {
+  if (a.step < 0 || a.step >= a.max_steps) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(aan_prep_kernel, dim3((a.R + 3) / 4), dim3(256), 0, s, a.x, a.ln_g, a.ln_b, a.hist, a.anc,
+                     a.anc_ld, a.step, a.max_steps, a.xn, a.avg, a.avg_part, a.R);
   return hipGetLastError();
 }
 

@@ -519,14 +519,14 @@ static int enc_attn_grid() {
   return n;
 }
 
-hipError_t launch_enc_attention(const float* qkv, const float* signal, const int* span, float* out, int B, int T,
-                                hipStream_t s, bool exact, int* ovf) {
-  if (T > ENC_MAXT || T <= 0) return hipErrorInvalidValue;
-  if (exact)
-    hipLaunchKernelGGL(enc_attention_kernel, dim3(ND_H, B), dim3(1024), 0, s, qkv, signal, span, out, T);
+hipError_t launch_enc_attention(const EncAttnArgs& a, hipStream_t s) {
+  if (a.T > ENC_MAXT || a.T <= 0) return hipErrorInvalidValue;
+  if (a.exact)
+    hipLaunchKernelGGL(enc_attention_kernel, dim3(ND_H, a.B), dim3(1024), 0, s, a.qkv, a.mask.signal, a.mask.span,
+                       a.out, a.T);
   else
-    hipLaunchKernelGGL(enc_attention_h3_kernel<2>, dim3(std::min(B * ND_H, enc_attn_grid())), dim3(512), 0, s, qkv,
-                       signal, span, out, T, B, ovf);
+    hipLaunchKernelGGL(enc_attention_h3_kernel<2>, dim3(std::min(a.B * ND_H, enc_attn_grid())), dim3(512), 0, s,
+                       a.qkv, a.mask.signal, a.mask.span, a.out, a.T, a.B, a.ovf);
   return hipGetLastError();
 }
 
@@ -644,15 +644,8 @@ enc_attention_rank2_kernel(R2Args A, int T) {
   }
 }
 
-hipError_t launch_enc_attention_rank2(const float* signal, const int* span, const EmbedQkv& eq, const float* coef,
-                                      float* out, int B, int T, hipStream_t s) {
-  if (T > ENC_MAXT || T <= 0 || !eq.ac || !eq.bias || !coef) return hipErrorInvalidValue;
-  R2Args a;
-  a.signal = signal;
-  a.span = span;
-  a.eq = eq;
-  a.coef = coef;
-  a.out = out;
+hipError_t launch_enc_attention_rank2(const R2Args& a, int B, int T, hipStream_t s) {
+  if (T > ENC_MAXT || T <= 0 || !a.eq.ac || !a.eq.bias || !a.coef) return hipErrorInvalidValue;
   hipLaunchKernelGGL(enc_attention_rank2_kernel, dim3(B), dim3(512), 0, s, a, T);
   return hipGetLastError();
 }

@@ -548,13 +548,12 @@ bank_pack_d8_kernel(const float* __restrict__ x, const float* __restrict__ gm, c
   }
 }
 
-hipError_t launch_bank_pack_d8(const float* x, const float* ln_g, const float* ln_b, void* bank, float* kscale,
-                               int* kemax, const int* span, int B, int T, int* ovf, hipStream_t s) {
-  if (T < 1 || T > 512 || B < 1 || !bank || !kscale || !kemax) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(kemax, 0, (size_t)B * sizeof(int), s);
+hipError_t launch_bank_pack_d8(const BankPackArgs& a, hipStream_t s) {
+  if (a.T < 1 || a.T > 512 || a.B < 1 || !a.bank || !a.kscale || !a.kemax) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(a.kemax, 0, (size_t)a.B * sizeof(int), s);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(bank_pack_d8_kernel, dim3(B * B8_KB), dim3(256), 0, s, x, ln_g, ln_b,
-                     reinterpret_cast<i32x4*>(bank), kscale, kemax, span, T, ovf);
+  hipLaunchKernelGGL(bank_pack_d8_kernel, dim3(a.B * B8_KB), dim3(256), 0, s, a.x, a.ln_g, a.ln_b,
+                     reinterpret_cast<i32x4*>(a.bank), a.kscale, a.kemax, a.span, a.T, a.ovf);
   return hipGetLastError();
 }
 

@@ -206,10 +206,11 @@ __device__ __forceinline__ void flag_overflow(int* ovf, float amax) {
 }
 
 // Host side: a runtime value picks a template instantiation.  Calls f(std::integral_constant<int, V>) for the
-// first V of Vs equal to v; false when none is.  A kernel family writes its forms once as a function that maps
-// the runtime choice to a kernel pointer through this, and both its launcher and its hipFuncSetAttribute loop
-// (over the choices) call that function.  hipcc emits the kernels a list instantiates last value first: the
-// lists are written in the order that keeps each code object's kernels where they were (same addresses).
+// first V of Vs equal to v; false when none is.  Every kernel family (attentions, GEMMs, FFN, LSTM) writes its
+// forms once as a function that maps the runtime choice to a kernel pointer through this, and both its launcher
+// and its hipFuncSetAttribute loop (over the choices) call that function.  hipcc emits the kernels a list
+// instantiates last value first: the lists are written in the order that keeps each code object's kernels where
+// they were (same addresses).
 template <int... Vs, typename F>
 inline bool pick_form(int v, F&& f) {
   return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);

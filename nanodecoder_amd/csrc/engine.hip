@@ -181,12 +181,7 @@ static int alloc_workspaces(nd_ctx* c) {
 static hipError_t enqueue_encode_transformer(nd_ctx* c, int B, int T, hipStream_t s) {
   const Model& m = c->m;
   const int M = B * T, D = c->D, F = c->F;
-  nd::EmbedQkv eq;
-  eq.ac = m.eq_ac;
-  eq.bias = m.enc[0].nbqkv;
-  eq.mww = m.eq_m[0];
-  eq.mwb = m.eq_m[1];
-  eq.mbb = m.eq_m[2];
+  const nd::EmbedQkv eq{.ac = m.eq_ac, .bias = m.enc[0].nbqkv, .mww = m.eq_m[0], .mwb = m.eq_m[1], .mbb = m.eq_m[2]};
   LCHK(nd::launch_enc_embed(c->sig, m.enc_lin_w, m.enc_lin_b, c->x, c->x_part, B, T, s));
   int pnx = 1, pny = 0;
   bool qkv_done = false;  // this layer's q | k | v already in c->big
@@ -194,29 +189,24 @@ static hipError_t enqueue_encode_transformer(nd_ctx* c, int B, int T, hipStream_
     const EncLayer& L = m.enc[li];
     // encoder/transformer.py:36-54
     if (li == 0) {
-      LCHK(nd::launch_enc_attention_rank2(c->sig, c->span, eq, m.eq_coef, c->att, B, T, s));
+      LCHK(nd::launch_enc_attention_rank2({.signal = c->sig, .span = c->span, .eq = eq, .coef = m.eq_coef,
+                                           .out = c->att}, B, T, s));
     } else {
       if (!qkv_done) LCHK(G(c->x, D, L.nwqkv, 3 * D, D, L.nbqkv, c->big, 3 * D, M).h3(c).ln(c->x_part, pnx).run(s));
-      LCHK(nd::launch_enc_attention(c->big, c->sig, c->span, c->att, B, T, s, c->exact, c->ovf));
+      LCHK(nd::launch_enc_attention({.qkv = c->big, .mask = {c->sig, c->span}, .out = c->att, .B = B, .T = T,
+                                     .exact = c->exact, .ovf = c->ovf}, s));
     }
     qkv_done = false;
     if (!c->exact && L.w1h) {  // the fused block (nd_finalize makes w1h, w2h, woh and qkvh together)
-      nd::EncWo wo;
-      wo.att = c->att;
-      wo.woh = L.woh;
-      wo.wos = L.wos;
-      wo.bo = L.bo;
-      nd::EncQkv qk;
+      nd::EncQkv qk;  // the next layer's q | k | v, when there is one
       if (li + 1 < m.enc.size()) {
         const EncLayer& N = m.enc[li + 1];
-        qk.wh = N.qkvh;
-        qk.ws = N.qkvs;
-        qk.bias = N.nbqkv;
-        qk.out = c->big;
-        qkv_done = true;
+        qk = {.wh = N.qkvh, .ws = N.qkvs, .bias = N.nbqkv, .out = c->big};
+        qkv_done = qk.wh != nullptr;
       }
-      LCHK(nd::launch_enc_ffn(c->x, L.w1h, L.w1s, L.nb1, L.w2h, L.w2s, L.b2, c->x, c->x_part, M, F, c->ovf, s, &wo,
-                              qkv_done ? &qk : nullptr));
+      LCHK(nd::launch_enc_ffn({.y = c->x, .w1h = L.w1h, .w1s = L.w1s, .b1 = L.nb1, .w2h = L.w2h, .w2s = L.w2s,
+                               .b2 = L.b2, .x = c->x, .xpart = c->x_part, .M = M, .F = F, .ovf = c->ovf},
+                              {.att = c->att, .woh = L.woh, .wos = L.wos, .bo = L.bo}, qk, s));
       pnx = 1;
       continue;
     }
@@ -242,8 +232,9 @@ static hipError_t enqueue_encode_nano(nd_ctx* c, int B, int T, hipStream_t s) {
     if (l > 0)
       LCHK(G(bufs[(l - 1) & 1], 2 * c->H, L.wih, 8 * c->H, 2 * c->H, L.bsum, c->nano_xp, 8 * c->H, M).h3(c).run(s));
     if (last) LCHK(hipMemsetAsync(out, 0, (size_t)M * 2 * c->H * sizeof(float), s));
-    LCHK(nd::launch_lstm_layer(c->nano_xp, c->sig, L.wih, L.bsum, L.whh, c->len, B, T, out,
-                               last ? nullptr : L.bn_scale, last ? nullptr : L.bn_shift, l == 0, s, c->exact));
+    LCHK(nd::launch_lstm_layer({.xp = c->nano_xp, .signal = c->sig, .wih0 = L.wih, .bsum = L.bsum, .whh = L.whh,
+                                .len = c->len, .B = B, .T = T, .out = out, .bn_scale = last ? nullptr : L.bn_scale,
+                                .bn_shift = last ? nullptr : L.bn_shift, .layer0 = l == 0, .exact = c->exact}, s));
   }
   return G(bufs[(Lz - 1) & 1], 2 * c->H, m.nano_W, D, 2 * c->H, nullptr, c->x, D, M).h3(c).run(s);
 }
@@ -411,8 +402,9 @@ static hipError_t enqueue_dec_step(nd_ctx* c, const nd::RowSet& rows, int T, int
     // all step activations are P16-packed (kernels.hpp)
     if (c->cfg.self_attn_type == ND_SELF_AVERAGE) {
       // average_attn.py:55-106 + the layer residual (decoder/transformer.py:82-86)
-      LCHK(nd::launch_aan_prep(c->dx, L.ln1_g, L.ln1_b, cache, h.anc, h.anc_ld, step, S, c->axn, c->aavg, c->aavg_part,
-                               R, s));
+      LCHK(nd::launch_aan_prep({.x = c->dx, .ln_g = L.ln1_g, .ln_b = L.ln1_b, .hist = cache, .anc = h.anc,
+                                .anc_ld = h.anc_ld, .step = step, .max_steps = S, .xn = c->axn, .avg = c->aavg,
+                                .avg_part = c->aavg_part, .R = R}, s));
       LCHK(dg(c->aavg, D, L.paw1, D, D, L.nab1, c->ah, D).ln(c->aavg_part, 1).relu().run(s));
       LCHK(dg(c->ah, D, L.paw2, D, D, L.ab2, c->aa, D).res(c->aavg, D).run(s));
       LCHK(dg(c->axn, D, L.pgwx, 2 * D, D, L.gb, c->ag, 2 * D).run(s));
@@ -471,14 +463,11 @@ static hipError_t enqueue_dec_step(nd_ctx* c, const nd::RowSet& rows, int T, int
     if (const int ns = dec_ffn_splits(c, R)) {  // beam rows: the fused block, hidden on chip (ffn.hip)
       const auto& i1 = c->m.split.at(L.pw1);
       const auto& i2 = c->m.split.at(L.pw2);
-      nd::DecFfn df;
-      df.nsplit = ns;
-      df.slab = c->dffn_slab;
-      df.tickets = c->dffn_cnt;
-      df.skip = done;
-      df.skip_rpc = rpc;
-      LCHK(nd::launch_dec_ffn(c->dmid, i1.first, i1.second, L.nb1, i2.first, i2.second, L.b2, c->dx, c->dx_part, R, F,
-                              c->ovf, df, s));
+      LCHK(nd::launch_dec_ffn({.y = c->dmid, .w1h = i1.first, .w1s = i1.second, .b1 = L.nb1, .w2h = i2.first,
+                               .w2s = i2.second, .b2 = L.b2, .x = c->dx, .xpart = c->dx_part, .M = R, .F = F,
+                               .ovf = c->ovf},
+                              {.nsplit = ns, .slab = c->dffn_slab, .tickets = c->dffn_cnt, .skip = done,
+                               .skip_rpc = rpc}, s));
       pnx = 1;  // each row's exact statistics in one partial
     } else {
       LCHK(dg(c->dmid, D, L.pw1, F, D, L.nb1, c->dhid, F).ln(c->dmid_part, pnm).relu().run(s));
@@ -500,8 +489,9 @@ static hipError_t enqueue_memory(nd_ctx* c, int B, int T, int rpc, hipStream_t s
   }
   const bool tf = c->cfg.encoder_type == ND_ENC_TRANSFORMER;
   if (c->bank_d8)
-    return nd::launch_bank_pack_d8(c->x, tf ? c->m.bank_ln_g : nullptr, tf ? c->m.bank_ln_b : nullptr, c->mem_p, c->bank_ks,
-                                   c->bank_em, c->span, B, T, c->ovf, s);
+    return nd::launch_bank_pack_d8({.x = c->x, .ln_g = tf ? c->m.bank_ln_g : nullptr,
+                                    .ln_b = tf ? c->m.bank_ln_b : nullptr, .bank = c->mem_p, .kscale = c->bank_ks,
+                                    .kemax = c->bank_em, .span = c->span, .B = B, .T = T, .ovf = c->ovf}, s);
   if (!tf) return hipSuccess;  // the NanoEncoder's output is the bank as it stands
   return nd::launch_memory_pack(c->x, c->m.bank_ln_g, c->m.bank_ln_b, c->mem_p, B, T, T, s);
 }

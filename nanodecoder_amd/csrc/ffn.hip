@@ -616,52 +616,46 @@ enc_ffn_kernel(const float* y, const uint16_t* __restrict__ w1h, float w1s, cons
   }
 }
 
-hipError_t launch_enc_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h,
-                          float w2s, const float* b2, float* x, float* xpart, int M, int F, int* ovf, hipStream_t s,
-                          const EncWo* wo, const EncQkv* qk) {
-  if (M <= 0) return hipSuccess;
-  if (F % FF_HC != 0 || F > FF_MAXF || F < FF_HC || !y || !w1h || !b1 || !w2h || !b2 || !x)
+// The forms of the block: the Wo fold in front, the QKV fold behind (encoder), or the decoder's split form.
+// Launches the form's kernel with nsplit splits per row block; a combination without a kernel is invalid.
+static hipError_t launch_ffn(const FfnArgs& a, const EncWo& wo, const EncQkv& qk, const DecFfn& df, bool dec,
+                             hipStream_t s) {
+  const dim3 grid((a.M + FF_BM - 1) / FF_BM, dec ? df.nsplit : 1), block(FF_BM / 16 * 64);
+  const int form = 4 * dec + 2 * (wo.att != nullptr) + (qk.wh != nullptr);
+  const bool ok = pick_form<4, 0, 1, 2, 3>(form, [&](auto V) {
+    constexpr int v = decltype(V)::value;
+    hipLaunchKernelGGL((enc_ffn_kernel<1, (v & 2) != 0, (v & 1) != 0, (v & 4) != 0>), grid, block, 0, s, a.y, a.w1h,
+                       a.w1s, a.b1, a.w2h, a.w2s, a.b2, a.x, a.xpart, a.M, a.F, a.ovf, wo, qk, df);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+static bool ffn_args_ok(const FfnArgs& a) {
+  return a.F % FF_HC == 0 && a.F <= FF_MAXF && a.F >= FF_HC && a.y && a.w1h && a.b1 && a.w2h && a.b2 && a.x;
+}
+
+hipError_t launch_enc_ffn(const FfnArgs& a, EncWo wo, EncQkv qk, hipStream_t s) {
+  if (a.M <= 0) return hipSuccess;
+  if (!ffn_args_ok(a)) return hipErrorInvalidValue;
+  if (wo.att && (!wo.woh || !wo.bo || wo.att == a.x || wo.att == a.y)) return hipErrorInvalidValue;
+  if (!wo.att && a.x == a.y) return hipErrorInvalidValue;  // with wo, x may alias y (the residual): each
+                                                            // workgroup reads its rows before it writes them
+  if (qk.wh && (!qk.bias || !qk.out || qk.out == a.x || qk.out == a.y || qk.out == wo.att))
     return hipErrorInvalidValue;
-  if (wo && (!wo->att || !wo->woh || !wo->bo || wo->att == x || wo->att == y)) return hipErrorInvalidValue;
-  if (!wo && x == y) return hipErrorInvalidValue;  // with wo, x may alias y (the residual): each
-                                                    // workgroup reads its rows before it writes them
-  if (qk && (!qk->wh || !qk->bias || !qk->out || qk->out == x || qk->out == y || (wo && qk->out == wo->att)))
-    return hipErrorInvalidValue;
-  const dim3 grid((M + FF_BM - 1) / FF_BM), block(FF_BM / 16 * 64);
-  const EncWo w = wo ? *wo : EncWo();
-  const EncQkv k = qk ? *qk : EncQkv();
-#define ND_FFN_GO(WO, QK)                                                                                          \
-  hipLaunchKernelGGL((enc_ffn_kernel<1, WO, QK, false>), grid, block, 0, s, y, w1h, w1s, b1, w2h, w2s, b2, x, xpart, \
-                     M, F, ovf, w, k, DecFfn())
-  if (wo && qk)
-    ND_FFN_GO(true, true);
-  else if (wo)
-    ND_FFN_GO(true, false);
-  else if (qk)
-    ND_FFN_GO(false, true);
-  else
-    ND_FFN_GO(false, false);
-#undef ND_FFN_GO
-  return hipGetLastError();
+  return launch_ffn(a, wo, qk, DecFfn(), false, s);
 }
 
 size_t dec_ffn_slab_floats(int M, int nsplit) {
   return (size_t)((M + FF_BM - 1) / FF_BM) * nsplit * 16 * (FF_BM / 16 * 64) * 4;
 }
 
-hipError_t launch_dec_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h,
-                          float w2s, const float* b2, float* x, float* xpart, int M, int F, int* ovf,
-                          const DecFfn& df, hipStream_t s) {
-  if (M <= 0) return hipSuccess;
-  if (F % FF_HC != 0 || F > FF_MAXF || F < FF_HC || M % 16 || !y || !w1h || !b1 || !w2h || !b2 || !x || x == y)
-    return hipErrorInvalidValue;
-  if (df.nsplit < 1 || df.nsplit > F / FF_HC || (df.nsplit > 1 && (!df.slab || !df.tickets)) ||
+hipError_t launch_dec_ffn(const FfnArgs& a, const DecFfn& df, hipStream_t s) {
+  if (a.M <= 0) return hipSuccess;
+  if (!ffn_args_ok(a) || a.M % 16 || a.x == a.y) return hipErrorInvalidValue;
+  if (df.nsplit < 1 || df.nsplit > a.F / FF_HC || (df.nsplit > 1 && (!df.slab || !df.tickets)) ||
       (df.skip && df.skip_rpc < 1))
     return hipErrorInvalidValue;
-  const dim3 grid((M + FF_BM - 1) / FF_BM, df.nsplit), block(FF_BM / 16 * 64);
-  hipLaunchKernelGGL((enc_ffn_kernel<1, false, false, true>), grid, block, 0, s, y, w1h, w1s, b1, w2h, w2s, b2, x,
-                     xpart, M, F, ovf, EncWo(), EncQkv(), df);
-  return hipGetLastError();
+  return launch_ffn(a, EncWo(), EncQkv(), df, true, s);
 }
 
 }  // namespace nd

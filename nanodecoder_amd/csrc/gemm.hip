@@ -1186,8 +1186,6 @@ split_weight_kernel(const float* __restrict__ W, int ld, int K, size_t groups, f
   o[3] = l1;
 }
 
-hipError_t launch_split_weight(const float* W, int N, int K, uint16_t* Wh, float* wscale, hipStream_t s, int ld);
-
 // P16H image (see mfma16h): thread = (column block, k pair, lane)
 __global__ void __launch_bounds__(256) pack_p16h_kernel(const float* __restrict__ W, int ld, int N, int K, float scale,
                                                         uint16_t* __restrict__ out) {
@@ -1248,8 +1246,7 @@ hipError_t launch_pack_p16h(const float* W, int ld, int N, int K, uint16_t* out,
 // 2^s puts max|W| 2^s in [2^13, 2^14): hi stays far from the fp16 maximum
 // (65504) and lo (about 2^-11 of its element) stays normal for elements
 // above about 2^-14 of the largest.
-hipError_t launch_split_weight(const float* W, int N, int K, uint16_t* Wh, float* wscale, hipStream_t s, int ld) {
-  if (ld == 0) ld = K;
+hipError_t launch_split_weight(const float* W, int ld, int N, int K, uint16_t* Wh, float* wscale, hipStream_t s) {
   if (N <= 0 || K % 32 != 0 || ld < K || ld % 4 || !W || !Wh || !wscale) return hipErrorInvalidValue;
   int s_exp = 0;
   hipError_t e = weight_scale_exp(W, ld, N, K, s, &s_exp);
@@ -1289,18 +1286,54 @@ hipError_t launch_fold_layernorm(const float* W, const float* bias, const float*
 }
 
 // ---------------------------------------------------------------------------
-#define ND_DISPATCH_FLAGS(KERNEL, ...)                                                          \
-  do {                                                                                          \
-    const bool ln_ = g.norm, re_ = g.relu, rs_ = g.R != nullptr;                     \
-    if (!ln_ && !re_ && !rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, false, false>), grid, block, 0, s, g); \
-    if (!ln_ && !re_ && rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, false, true>), grid, block, 0, s, g);   \
-    if (!ln_ && re_ && !rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, true, false>), grid, block, 0, s, g);   \
-    if (!ln_ && re_ && rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, true, true>), grid, block, 0, s, g);     \
-    if (ln_ && !re_ && !rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, false, false>), grid, block, 0, s, g);   \
-    if (ln_ && !re_ && rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, false, true>), grid, block, 0, s, g);     \
-    if (ln_ && re_ && !rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, true, false>), grid, block, 0, s, g);     \
-    if (ln_ && re_ && rs_) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, true, true>), grid, block, 0, s, g);       \
-  } while (0)
+// The forms of a GEMM kernel family, as one index: 8 H3 (split-fp16 weight image) + 4 LN + 2 RELU + RESID.
+static int form_of(const GemmArgs& g) { return 8 * (g.Wh != nullptr) + 4 * g.norm + 2 * g.relu + (g.R != nullptr); }
+#define ND_ALL_EPI(h) 8 * (h) + 7, 8 * (h) + 6, 8 * (h) + 5, 8 * (h) + 4, 8 * (h) + 3, 8 * (h) + 2, 8 * (h) + 1, 8 * (h)
+// f(H3, LN, RELU, RESID as std::bool_constant) for the form v when Vs lists it; false: the family has no such form
+template <int... Vs, typename F>
+static bool flag_form(int v, F&& f) {
+  return pick_form<Vs...>(v, [&](auto V) {
+    constexpr int x = decltype(V)::value;
+    f(std::bool_constant<(x & 8) != 0>{}, std::bool_constant<(x & 4) != 0>{}, std::bool_constant<(x & 2) != 0>{},
+      std::bool_constant<(x & 1) != 0>{});
+  });
+}
+// One form function per family: f(kernel) for the form v (form_of); the launcher and, where the kernel takes
+// dynamic LDS, init_gemm_attributes go through it.
+template <int BM, int BN, int WM, int WN, int BK, typename F>
+static bool f32_form(int v, F&& f) {
+  return flag_form<ND_ALL_EPI(0), ND_ALL_EPI(1)>(v, [&](auto H, auto L, auto RE, auto RS) {
+    f(gemm_f32_kernel<BM, BN, WM, WN, BK, H.value, L.value, RE.value, RS.value>);
+  });
+}
+template <typename F>
+static bool f32d_form(int v, F&& f) {  // fp32 weights only
+  return flag_form<ND_ALL_EPI(0)>(v, [&](auto, auto L, auto RE, auto RS) {
+    f(gemm_f32d_kernel<L.value, RE.value, RS.value>);
+  });
+}
+template <int NT, int KS, int KW, typename F>
+static bool p16_form(int v, F&& f) {
+  return flag_form<ND_ALL_EPI(0), ND_ALL_EPI(1)>(v, [&](auto H, auto L, auto RE, auto RS) {
+    f(gemm_p16_kernel<NT, KS, KW, H.value, L.value, RE.value, RS.value>);
+  });
+}
+template <int BMB, int BNB, typename F>
+static bool p16s_form(int v, F&& f) {
+  return flag_form<ND_ALL_EPI(1), ND_ALL_EPI(0)>(v, [&](auto H, auto L, auto RE, auto RS) {
+    f(gemm_p16s_kernel<BMB, BNB, H.value, L.value, RE.value, RS.value>);
+  });
+}
+template <typename F>
+static bool p16k_form(int v, F&& f) {  // no LN (K >= 1024), no ReLU
+  return flag_form<0, 1, 8, 9>(v, [&](auto H, auto, auto, auto RS) { f(gemm_p16k_kernel<H.value, RS.value>); });
+}
+#undef ND_ALL_EPI
+// what a launcher hands its form function: launches the kernel on g; a form the family lacks is an invalid argument
+static auto launch_on(const GemmArgs& g, dim3 grid, dim3 block, size_t lds, hipStream_t s) {
+  return [=, &g](auto kern) { hipLaunchKernelGGL(kern, grid, block, lds, s, g); };
+}
+static hipError_t launched(bool form_found) { return form_found ? hipGetLastError() : hipErrorInvalidValue; }
 
 // kernel routes taken (include/nanodec.h ND_ROUTE_*), counted at enqueue time
 static std::atomic<long long> g_routes[ND_ROUTE_N];
@@ -1319,11 +1352,7 @@ static hipError_t launch_cfg(GemmArgs& g, hipStream_t s) {
   g.xcd_map = nmb % 8 == 0;
   dim3 grid((g.N / BN) * nmb), block(WM * WN * 64);
   g.part_n_out = g.N / BN;
-  if (g.Wh)
-    ND_DISPATCH_FLAGS(gemm_f32_kernel, BM, BN, WM, WN, BK, true);
-  else
-    ND_DISPATCH_FLAGS(gemm_f32_kernel, BM, BN, WM, WN, BK, false);
-  return hipGetLastError();
+  return launched(f32_form<BM, BN, WM, WN, BK>(form_of(g), launch_on(g, grid, block, 0, s)));
 }
 
 // gemm_f32d_kernel: fp32 weights, row-major A / C, 256 x 256 tiles, at least FD_SLOTS k steps
@@ -1337,16 +1366,7 @@ static hipError_t launch_f32d(GemmArgs& g, hipStream_t s) {
   g.xcd_map = nmb % 8 == 0;
   dim3 grid((g.N / 256) * nmb), block(512);
   g.part_n_out = g.N / 256;
-  const bool ln = g.norm, re = g.relu, rs = g.R != nullptr;
-  if (!ln && !re && !rs) hipLaunchKernelGGL((gemm_f32d_kernel<false, false, false>), grid, block, 0, s, g);
-  if (!ln && !re && rs) hipLaunchKernelGGL((gemm_f32d_kernel<false, false, true>), grid, block, 0, s, g);
-  if (!ln && re && !rs) hipLaunchKernelGGL((gemm_f32d_kernel<false, true, false>), grid, block, 0, s, g);
-  if (!ln && re && rs) hipLaunchKernelGGL((gemm_f32d_kernel<false, true, true>), grid, block, 0, s, g);
-  if (ln && !re && !rs) hipLaunchKernelGGL((gemm_f32d_kernel<true, false, false>), grid, block, 0, s, g);
-  if (ln && !re && rs) hipLaunchKernelGGL((gemm_f32d_kernel<true, false, true>), grid, block, 0, s, g);
-  if (ln && re && !rs) hipLaunchKernelGGL((gemm_f32d_kernel<true, true, false>), grid, block, 0, s, g);
-  if (ln && re && rs) hipLaunchKernelGGL((gemm_f32d_kernel<true, true, true>), grid, block, 0, s, g);
-  return hipGetLastError();
+  return launched(f32d_form(form_of(g), launch_on(g, grid, block, 0, s)));
 }
 
 // Row split a (a x 8/a rectangle of XCDs) that minimises the operand blocks
@@ -1368,15 +1388,10 @@ template <int NT, int KS, int KW>
 static hipError_t launch_p16(GemmArgs& g, hipStream_t s) {
   if (g.N % (NT * 16) != 0 || g.K != KS * KW) return hipErrorInvalidValue;
   dim3 grid(g.N / (NT * 16), (g.M + 15) / 16), block(NT * KS * 64);
-  count_route(g.K != 256 ? ND_ROUTE_P16_LONGK : NT == 1 ? ND_ROUTE_P16_SMALL : NT == 4 ? ND_ROUTE_P16_N64
-                                                                                        : ND_ROUTE_P16_LN128);
+  count_route(g.K != 256 ? ND_ROUTE_P16_LONGK : ND_ROUTE_P16_SMALL);
   g.xcd_a = p16_xcd_rows((int)grid.x, (int)grid.y, NT);
   g.part_n_out = g.N / 16;
-  if (g.Wh)
-    ND_DISPATCH_FLAGS(gemm_p16_kernel, NT, KS, KW, true);
-  else
-    ND_DISPATCH_FLAGS(gemm_p16_kernel, NT, KS, KW, false);
-  return hipGetLastError();
+  return launched(p16_form<NT, KS, KW>(form_of(g), launch_on(g, grid, block, 0, s)));
 }
 
 template <int BMB, int BNB>
@@ -1390,47 +1405,23 @@ static hipError_t launch_p16s(GemmArgs& g, hipStream_t s) {
   dim3 grid(g.N / (BNB * 16), (g.M + 16 * BMB - 1) / (16 * BMB)), block(BMB * BNB * 64);
   count_route(BNB == 4 ? ND_ROUTE_P16S_2X4 : ND_ROUTE_P16S_2X2);
   g.part_n_out = g.N / 16;
-  const size_t lds = p16s_lds<BMB, BNB>();
-  const bool h3_ = g.Wh != nullptr, ln_ = g.norm, re_ = g.relu, rs_ = g.R != nullptr;
-#define ND_P16S(H, L, RE, RS)                                        \
-  if (h3_ == H && ln_ == L && re_ == RE && rs_ == RS)                \
-    hipLaunchKernelGGL((gemm_p16s_kernel<BMB, BNB, H, L, RE, RS>), grid, block, lds, s, g);
-#define ND_P16S_H(H)                                                                                   \
-  ND_P16S(H, false, false, false) ND_P16S(H, false, false, true) ND_P16S(H, false, true, false)        \
-  ND_P16S(H, false, true, true) ND_P16S(H, true, false, false) ND_P16S(H, true, false, true)           \
-  ND_P16S(H, true, true, false) ND_P16S(H, true, true, true)
-  ND_P16S_H(false) ND_P16S_H(true)
-#undef ND_P16S_H
-#undef ND_P16S
-  return hipGetLastError();
+  return launched(p16s_form<BMB, BNB>(form_of(g), launch_on(g, grid, block, p16s_lds<BMB, BNB>(), s)));
 }
 
-template <int BMB, int BNB, bool H>
-static hipError_t set_p16s_attr_h() {
-  const void* fns[] = {(const void*)gemm_p16s_kernel<BMB, BNB, H, false, false, false>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, false, false, true>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, false, true, false>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, false, true, true>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, true, false, false>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, true, false, true>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, true, true, false>,
-                       (const void*)gemm_p16s_kernel<BMB, BNB, H, true, true, true>};
-  for (const void* f : fns) {
-    hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p16s_lds<BMB, BNB>());
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
-}
-
-template <int BMB, int BNB>
-static hipError_t set_p16s_attr() {
-  hipError_t e = set_p16s_attr_h<BMB, BNB, false>();
-  return e != hipSuccess ? e : set_p16s_attr_h<BMB, BNB, true>();
-}
-
+// the LDS-staged P16 kernels' tiles exceed the default dynamic-LDS limit: every form of both tile shapes
 hipError_t init_gemm_attributes() {
-  hipError_t e = set_p16s_attr<2, 4>();
-  return e != hipSuccess ? e : set_p16s_attr<2, 2>();
+  hipError_t e = hipSuccess;
+  for (int v = 0; v < 16; ++v) {
+    p16s_form<2, 4>(v, [&](auto kern) {
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p16s_lds<2, 4>());
+    });
+    p16s_form<2, 2>(v, [&](auto kern) {
+      if (e == hipSuccess)
+        e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p16s_lds<2, 2>());
+    });
+  }
+  return e;
 }
 
 static hipError_t check_args(const GemmArgs& g) {
@@ -1501,8 +1492,9 @@ hipError_t launch_gemm_p16(GemmArgs& g, hipStream_t s) {
     const long mb32 = (g.M + 31) / 32;
     if (g.N % 64 == 0 && (long)(g.N / 64) * mb32 >= 128) return launch_p16s<2, 4>(g, s);
     if (g.N % 32 == 0 && (long)(g.N / 32) * mb32 >= 128) return launch_p16s<2, 2>(g, s);
-    if (g.norm && g.N % 128 == 0 && (long)(g.N / 128) * ((g.M + 15) / 16) >= 128) return launch_p16<8, 1, 256>(g, s);
-    if (g.N % 64 == 0 && (long)(g.N / 64) * ((g.M + 15) / 16) >= 128) return launch_p16<4, 2, 128>(g, s);
+    // No wider one-block-row tile (128 or 64 columns x 16 rows) can follow: ceil(M/16) <= 2 ceil(M/32), so
+    // (N/128) ceil(M/16) >= 128 implies (N/64) ceil(M/32) >= 128, the first test above, and (N/64) ceil(M/16)
+    // >= 128 implies (N/32) ceil(M/32) >= 128, the second.  (ND_ROUTE_P16_LN128 and ND_ROUTE_P16_N64, retired.)
     return launch_p16<1, 4, 64>(g, s);
   }
   // split over workgroups (gemm_p16k_kernel): 32 x 32 tiles x K / 512 slices, when the tiles x slices fill
@@ -1513,18 +1505,7 @@ hipError_t launch_gemm_p16(GemmArgs& g, hipStream_t s) {
     if (g.M > 128 && tiles <= g.sk_tiles) {
       count_route(ND_ROUTE_P16_SPLITK);
       g.part_n_out = g.N / 16;
-      const dim3 grid(tiles * S), block(PK_NW * 64);
-      if (g.Wh) {
-        if (g.R)
-          hipLaunchKernelGGL((gemm_p16k_kernel<true, true>), grid, block, 0, s, g);
-        else
-          hipLaunchKernelGGL((gemm_p16k_kernel<true, false>), grid, block, 0, s, g);
-      } else if (g.R) {
-        hipLaunchKernelGGL((gemm_p16k_kernel<false, true>), grid, block, 0, s, g);
-      } else {
-        hipLaunchKernelGGL((gemm_p16k_kernel<false, false>), grid, block, 0, s, g);
-      }
-      return hipGetLastError();
+      return launched(p16k_form(form_of(g), launch_on(g, dim3(tiles * S), dim3(PK_NW * 64), 0, s)));
     }
   }
   // K = 2048 on 8 K-slice waves of 256 (16 waves of 128: pooled greedy 16.30 -> 16.63 ms, round 4, dropped)

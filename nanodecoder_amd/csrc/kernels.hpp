@@ -78,10 +78,10 @@ hipError_t launch_gemm(GemmArgs& g, hipStream_t s);
 // packed, lda/ldw/ldr/ldc ignored, rows padded to a multiple of 16 in every
 // buffer (part buffers included); LN requires part_in.
 hipError_t launch_gemm_p16(GemmArgs& g, hipStream_t s);
-// W [N, K] fp32 (leading dimension ld, 0 = K) -> Wh (split-fp16, [N][K/8][hi 8 | lo 8] halves) with the
+// W [N, K] fp32 (leading dimension ld) -> Wh (split-fp16, [N][K/8][hi 8 | lo 8] halves) with the
 // power-of-two scale that puts max|W| just under 2^14; returns 2^-s in
 // *wscale (synchronises the stream: load-time only).  K % 32 == 0.
-hipError_t launch_split_weight(const float* W, int N, int K, uint16_t* Wh, float* wscale, hipStream_t s, int ld = 0);
+hipError_t launch_split_weight(const float* W, int ld, int N, int K, uint16_t* Wh, float* wscale, hipStream_t s);
 // P16H image of a row-major weight [N, K] (leading dim ld) for the split-fp16
 // P16 kernels: [N/16][K/32][hi | lo][64 lanes][8 halves] of W * 2^s (scale as
 // launch_split_weight; synchronises the stream).  N % 16 == 0, K % 32 == 0.
@@ -96,6 +96,16 @@ hipError_t launch_pack_p16(const float* src, int ld, float* dst, int M, int N, h
 // (LayerNorm(x) W^T + b == xhat (W diag(g))^T + (W beta + b)); bias may be null.
 hipError_t launch_fold_layernorm(const float* W, const float* bias, const float* ln_g, const float* ln_b,
                                  float* W_out, float* b_out, int N, int K, hipStream_t s);
+
+// Launch arguments: host-only aggregates filled by field name; the launchers unpack them into the kernels'
+// argument lists.  (GemmArgs, EncWo, EncQkv, DecFfn and R2Args are kernel arguments themselves, passed by value:
+// their member order and types are the kernels' layout.)
+// the source-side key mask: keys t < span[c], those with signal[c*T + t] == pad_val filled with ND_MASK_FILL
+struct SrcMask {
+  const float* signal = nullptr;
+  const int* span = nullptr;
+  float pad_val = 0.f;
+};
 
 // ---- encoder -------------------------------------------------------------
 // Layer 0 of the Transformer encoder reads x = s w + b (Linear(1, d) of the
@@ -123,39 +133,68 @@ struct R2Args {
   const float* coef = nullptr;
   float* out = nullptr;
 };
-hipError_t launch_enc_attention_rank2(const float* signal, const int* span, const EmbedQkv& eq, const float* coef,
-                                      float* out, int B, int T, hipStream_t s);
+hipError_t launch_enc_attention_rank2(const R2Args& a, int B, int T, hipStream_t s);
 // ac and the three means (double scal[3]) from the LN-folded weight [768, 256]
 hipError_t launch_embed_qkv_prep(const float* w_in, const float* b_in, const float* nwqkv, float* ac, double* scal,
                                  hipStream_t s);
 // x[b*T+t][:] = signal[b][t] * w_in + b_in (Linear(1, d)); part: full-row stats
 hipError_t launch_enc_embed(const float* signal, const float* w_in, const float* b_in, float* x, float* part, int B,
                             int T, hipStream_t s);
-// flash attention over qkv [B*T, 768]; mask signal==0; keys >= span excluded
-// exact: the fp32-MFMA kernel instead of split-fp16;
-// ovf: split-fp16 range guard word (nullable)
-hipError_t launch_enc_attention(const float* qkv, const float* signal, const int* span, float* out, int B, int T,
-                                hipStream_t s, bool exact = false, int* ovf = nullptr);
+// flash attention over qkv [B*T, 768]; mask: signal == 0 (pad_val is not read), keys >= span excluded
+struct EncAttnArgs {
+  const float* qkv = nullptr;
+  SrcMask mask;
+  float* out = nullptr;
+  int B = 0, T = 0;
+  bool exact = false;  // the fp32-MFMA kernel instead of split-fp16
+  int* ovf = nullptr;  // split-fp16 range guard word (nullable)
+};
+hipError_t launch_enc_attention(const EncAttnArgs& a, hipStream_t s);
 // NanoEncoder BiLSTM layer (both directions): xp [B*T, 1024] projections
 // (or, layer0, computed from signal with wih0/bsum [2][512]); whh [2][512][128];
 // out [B*T, 256] (h, or BatchNorm(h) when bn_scale != nullptr).
-hipError_t launch_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum,
-                             const float* whh, const int* len, int B, int T, float* out, const float* bn_scale,
-                             const float* bn_shift, bool layer0, hipStream_t s, bool exact = false);
+struct LstmArgs {
+  const float* xp = nullptr;
+  const float* signal = nullptr;
+  const float* wih0 = nullptr;
+  const float* bsum = nullptr;
+  const float* whh = nullptr;
+  const int* len = nullptr;
+  int B = 0, T = 0;
+  float* out = nullptr;
+  const float* bn_scale = nullptr;
+  const float* bn_shift = nullptr;
+  bool layer0 = false;
+  bool exact = false;  // fp32 MFMAs instead of split-fp16
+};
+hipError_t launch_lstm_layer(const LstmArgs& a, hipStream_t s);
 // fused encoder FFN block (ffn.hip): x = y + W2 relu(W1' LN(y) + b1') + b2 with
 // the LN affine folded into W1' / b1'; w1h = P16H image of W1' [F, 256], w2h =
 // P16H image of W2 [256, F] (launch_pack_p16h), w*s their scales; xpart gets
 // each row's exact {mean, M2} in slot 0 (one partial).  F % 32 == 0, F <= 2048.
-// wo (nullable): the attention block's output projection folded in front,
-// y = x + att Wo^T + bo with y the residual argument (x may alias it), woh
-// the P16H image of Wo [256, 256], wos its scale.
+struct FfnArgs {
+  const float* y = nullptr;
+  const uint16_t* w1h = nullptr;
+  float w1s = 1.f;
+  const float* b1 = nullptr;
+  const uint16_t* w2h = nullptr;
+  float w2s = 1.f;
+  const float* b2 = nullptr;
+  float* x = nullptr;
+  float* xpart = nullptr;
+  int M = 0, F = 0;
+  int* ovf = nullptr;  // split-fp16 range guard word (nullable)
+};
+// wo (att == nullptr: none): the attention block's output projection folded in
+// front, y = x + att Wo^T + bo with y the residual argument (x may alias it),
+// woh the P16H image of Wo [256, 256], wos its scale.
 struct EncWo {
   const float* att = nullptr;
   const uint16_t* woh = nullptr;
   float wos = 1.f;
   const float* bo = nullptr;
 };
-// qk (nullable): the NEXT layer's QKV projection folded behind, out = LN(x)
+// qk (wh == nullptr: none): the NEXT layer's QKV projection folded behind, out = LN(x)
 // W'^T + b' (wh: P16H image of the LN-folded W' [768, 256], ws its scale;
 // out row-major [M, 768])
 struct EncQkv {
@@ -164,9 +203,7 @@ struct EncQkv {
   const float* bias = nullptr;
   float* out = nullptr;
 };
-hipError_t launch_enc_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h,
-                          float w2s, const float* b2, float* x, float* xpart, int M, int F, int* ovf, hipStream_t s,
-                          const EncWo* wo = nullptr, const EncQkv* qk = nullptr);
+hipError_t launch_enc_ffn(const FfnArgs& a, EncWo wo, EncQkv qk, hipStream_t s);
 // The same block for the beam's decoder rows (P16-packed y and x, the layer's
 // position_ffn.py:27-40 at decoder/transformer.py:92): the d_ff walk split
 // over nsplit workgroups per 128-row block (blockIdx.y), whose partial
@@ -182,9 +219,7 @@ struct DecFfn {
   int skip_rpc = 1;
 };
 size_t dec_ffn_slab_floats(int M, int nsplit);
-hipError_t launch_dec_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h,
-                          float w2s, const float* b2, float* x, float* xpart, int M, int F, int* ovf,
-                          const DecFfn& df, hipStream_t s);
+hipError_t launch_dec_ffn(const FfnArgs& a, const DecFfn& df, hipStream_t s);
 // out[r] = LN(x[r]) (rows of 256)
 hipError_t launch_layernorm(const float* x, const float* g, const float* b, float* out, int rows, hipStream_t s);
 
@@ -220,14 +255,7 @@ hipError_t launch_fill_i32(int* p, int v, int n, hipStream_t s);
 // raises the dynamic-LDS limit of every form of the decoder attentions and the GEMMs (once per process)
 hipError_t init_kernel_attributes();
 
-// Launch arguments of the decoder-step kernels: host-only aggregates filled by field name; the launchers
-// unpack them into the kernels' argument lists.  Three bundles recur:
-// the source-side key mask: keys t < span[c], those with signal[c*T + t] == pad_val filled with ND_MASK_FILL
-struct SrcMask {
-  const float* signal = nullptr;
-  const int* span = nullptr;
-  float pad_val = 0.f;
-};
+// Two more bundles recur in the decoder-step launch arguments (with SrcMask, above):
 // the chunks and rows a launch covers: rows r = c * rpc + j of the chunks c < C
 struct RowSet {
   int C = 0;
@@ -331,8 +359,19 @@ hipError_t launch_memory_pack(const float* x, const float* ln_g, const float* ln
 hipError_t init_mem_attributes();
 // 24-bit fixed-point memory bank (bank8.hip): digits in bank (B * 512 * 256 * 3
 // bytes), per-row scales kscale [B * 512], per-chunk biased max exponent kemax [B]
-hipError_t launch_bank_pack_d8(const float* x, const float* ln_g, const float* ln_b, void* bank, float* kscale,
-                               int* kemax, const int* span, int B, int T, int* ovf, hipStream_t s);
+// from the encoder output rows x [B*T, 256] (LN when ln_g; keys >= span zero); ovf: a non-finite row (nullable)
+struct BankPackArgs {
+  const float* x = nullptr;
+  const float* ln_g = nullptr;
+  const float* ln_b = nullptr;
+  void* bank = nullptr;
+  float* kscale = nullptr;
+  int* kemax = nullptr;
+  const int* span = nullptr;
+  int B = 0, T = 0;
+  int* ovf = nullptr;
+};
+hipError_t launch_bank_pack_d8(const BankPackArgs& a, hipStream_t s);
 struct BankD8Args {
   const float* qp = nullptr;  // [C, 8*256] row-major
   const void* bank = nullptr;
@@ -367,9 +406,19 @@ hipError_t launch_assemble_reads(const unsigned char* bases, const int* chunk_of
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)
-hipError_t launch_aan_prep(const float* x, const float* ln_g, const float* ln_b, float* hist, const int* anc,
-                           int anc_ld, int step, int max_steps, float* xn, float* avg, float* avg_part, int R,
-                           hipStream_t s);
+struct AanPrepArgs {
+  const float* x = nullptr;
+  const float* ln_g = nullptr;
+  const float* ln_b = nullptr;
+  float* hist = nullptr;
+  const int* anc = nullptr;  // nullptr: identity
+  int anc_ld = 0, step = 0, max_steps = 0;
+  float* xn = nullptr;
+  float* avg = nullptr;
+  float* avg_part = nullptr;
+  int R = 0;
+};
+hipError_t launch_aan_prep(const AanPrepArgs& a, hipStream_t s);
 hipError_t launch_aan_gate(const float* g, const float* xn, const float* a, const float* x, float* out, float* part,
                            int R, hipStream_t s);
 // random sampling (translate/translator.py:371-394): temperature, top-k

@@ -405,29 +405,24 @@ lstm_dir_kernel(const float* __restrict__ xp,      // [B*T, 1024] input projecti
   }
 }
 
-hipError_t launch_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum,
-                             const float* whh, const int* len, int B, int T, float* out, const float* bn_scale,
-                             const float* bn_shift, bool layer0, hipStream_t s, bool exact) {
-  const bool f32 = exact;
-  // split-fp16: 4 sequences per workgroup (measured: 0.95 ms per layer at 4, 1.04 at 8, 1.52 at 16), the
-  // cell's sigmoid / tanh on the hardware exp and reciprocal; fp32 MFMAs: 16 sequences per workgroup
-  const int ns = f32 ? 16 : 4;
-  dim3 grid((B + ns - 1) / ns, 2), block(ns == 4 ? 512 : 1024);
-#define ND_LSTM_GO(L0, H, F, S)                                                                                       \
-  hipLaunchKernelGGL((lstm_dir_kernel<L0, H, F, S>), grid, block, 0, s, xp, signal, wih0, bsum, whh, len, B, T, out, \
-                     bn_scale, bn_shift)
-  if (f32) {
-    if (layer0)
-      ND_LSTM_GO(true, false, false, 16);
-    else
-      ND_LSTM_GO(false, false, false, 16);
-  } else if (layer0) {
-    ND_LSTM_GO(true, true, true, 4);
-  } else {
-    ND_LSTM_GO(false, true, true, 4);
-  }
-#undef ND_LSTM_GO
-  return hipGetLastError();
+// The forms of the layer: layer 0 (projections computed in the kernel) or not, in exact fp32 or split-fp16.
+// split-fp16: 4 sequences per workgroup (measured: 0.95 ms per layer at 4, 1.04 at 8, 1.52 at 16), the
+// cell's sigmoid / tanh on the hardware exp and reciprocal; fp32 MFMAs: 16 sequences per workgroup
+template <typename F>
+static bool lstm_form(bool layer0, bool exact, F&& f) {
+  return pick_form<0, 1, 2, 3>(2 * exact + layer0, [&](auto V) {
+    constexpr int v = decltype(V)::value;
+    constexpr bool split = (v & 2) == 0;
+    f(lstm_dir_kernel<(v & 1) != 0, split, split, split ? 4 : 16>, split ? 4 : 16);
+  });
+}
+
+hipError_t launch_lstm_layer(const LstmArgs& a, hipStream_t s) {
+  const bool ok = lstm_form(a.layer0, a.exact, [&](auto kern, int ns) {
+    hipLaunchKernelGGL(kern, dim3((a.B + ns - 1) / ns, 2), dim3(ns == 4 ? 512 : 1024), 0, s, a.xp, a.signal, a.wih0,
+                       a.bsum, a.whh, a.len, a.B, a.T, a.out, a.bn_scale, a.bn_shift);
+  });
+  return ok ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 }  // namespace nd

@@ -218,7 +218,7 @@ static hipError_t pack_step_weight(nd_ctx* c, const float* src, int ld, float* d
   auto jt = c->m.split_rm.find(dst);
   if (jt != c->m.split_rm.end()) hr = jt->second.first;
   if (!hr && (e = dalloc(c, &hr, (size_t)2 * rows * cols)) != hipSuccess) return e;
-  if ((e = nd::launch_split_weight(src, rows, cols, hr, &sc, c->es, ld)) != hipSuccess) return e;
+  if ((e = nd::launch_split_weight(src, ld, rows, cols, hr, &sc, c->es)) != hipSuccess) return e;
   c->m.split_rm[dst] = {hr, sc};
   return hipSuccess;
 }
@@ -608,7 +608,7 @@ int nd_finalize(nd_ctx* c) {
       auto it = c->m.split.find(W);
       if (it != c->m.split.end()) h = it->second.first;  // finalize called again: refresh in place
       hipError_t e = h ? hipSuccess : dalloc(c, &h, (size_t)2 * N * K);
-      if (e == hipSuccess) e = nd::launch_split_weight(W, N, K, h, &sc, c->es);
+      if (e == hipSuccess) e = nd::launch_split_weight(W, K, N, K, h, &sc, c->es);
       if (e == hipSuccess) c->m.split[W] = {h, sc};
       return e;
     };

@@ -2,53 +2,43 @@
 // nd_assemble_reads): launches on the caller's stream, with no context.  The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
-static hipError_t gemm(const float* A, int lda, const float* W, int N, int K, const float* bias, float* C, int ldc,
-                       int M, hipStream_t s, bool norm = false, bool relu = false, const float* R = nullptr,
-                       int ldr = 0) {
-  nd::GemmArgs g;
-  g.A = A; g.lda = lda; g.W = W; g.ldw = K; g.bias = bias; g.R = R; g.ldr = ldr; g.C = C; g.ldc = ldc;
-  g.norm = norm; g.M = M; g.N = N; g.K = K; g.relu = relu;
-  return nd::launch_gemm(g, s);
+// an entry's status from its launcher's: "name: <the HIP error's text>" in nd_last_error
+static int status(const char* name, hipError_t e, int code = ND_ERR_ARG) {
+  return e == hipSuccess ? ND_OK : fail(code, std::string(name) + ": " + hipGetErrorString(e));
+}
+// the P16 GEMM entries also report the output's row partials
+static int status_p16(const char* name, nd::GemmArgs g, int32_t* part_n_out, void* stream) {
+  const int rc = status(name, nd::launch_gemm_p16(g, (hipStream_t)stream));
+  if (rc == ND_OK && part_n_out) *part_n_out = g.part_n_out;
+  return rc;
 }
 
 int nd_op_gemm(const float* A, const float* W, const float* bias, const float* R, float* C, int32_t M, int32_t N,
                int32_t K, int32_t norm, int32_t relu, void* stream) {
-  hipError_t e = gemm(A, K, W, N, K, bias, C, N, M, (hipStream_t)stream, norm != 0, relu != 0, R, N);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm: ") + hipGetErrorString(e));
-  return ND_OK;
+  nd::GemmArgs g{.A = A, .lda = K, .W = W, .ldw = K, .bias = bias, .R = R, .ldr = N, .C = C, .ldc = N,
+                 .norm = norm != 0, .M = M, .N = N, .K = K, .relu = relu != 0};
+  return status("gemm", nd::launch_gemm(g, (hipStream_t)stream));
 }
 
 int nd_op_split_weight(const float* W, int32_t N, int32_t K, uint16_t* Wh, float* wscale, void* stream) {
-  hipError_t e = nd::launch_split_weight(W, N, K, Wh, wscale, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("split_weight: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("split_weight", nd::launch_split_weight(W, K, N, K, Wh, wscale, (hipStream_t)stream));
 }
 
 int nd_op_gemm_split(const float* A, const uint16_t* Wh, float wscale, const float* bias, const float* R, float* C,
                      int32_t M, int32_t N, int32_t K, int32_t norm, int32_t relu, void* stream) {
   if (!Wh) return fail(ND_ERR_ARG, "gemm_split: null Wh");
-  G g(A, K, nullptr, N, K, bias, C, N, M);
-  g.a.Wh = Wh;
-  g.a.wscale = wscale;
-  g.a.norm = norm != 0;
-  g.a.relu = relu != 0;
-  if (R) g.res(R, N);
-  hipError_t e = g.run((hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_split: ") + hipGetErrorString(e));
-  return ND_OK;
+  nd::GemmArgs g{.A = A, .lda = K, .ldw = K, .bias = bias, .R = R, .ldr = R ? N : 0, .C = C, .ldc = N,
+                 .norm = norm != 0, .M = M, .N = N, .K = K, .relu = relu != 0, .Wh = Wh, .wscale = wscale};
+  return status("gemm_split", nd::launch_gemm(g, (hipStream_t)stream));
 }
 
 int nd_op_gemm_split_q24(const float* A, const uint16_t* Wh, float wscale, const float* bias, void* img,
                          int32_t plane_rows, int32_t M, int32_t N, int32_t K, int32_t norm, void* stream) {
   if (!Wh || !img || plane_rows < M) return fail(ND_ERR_ARG, "gemm_split_q24: null Wh / image, or plane_rows < M");
-  G g(A, K, nullptr, N, K, bias, nullptr, N, M);
-  g.a.Wh = Wh;
-  g.a.wscale = wscale;
-  g.a.norm = norm != 0;
-  g.q24(static_cast<uint8_t*>(img), (size_t)plane_rows * CTXQ_ROW);
-  hipError_t e = g.run((hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_split_q24: ") + hipGetErrorString(e));
-  return ND_OK;
+  nd::GemmArgs g{.A = A, .lda = K, .ldw = K, .bias = bias, .ldc = N, .norm = norm != 0, .M = M, .N = N, .K = K,
+                 .Wh = Wh, .wscale = wscale, .q24 = static_cast<uint8_t*>(img),
+                 .q24_plane = (size_t)plane_rows * CTXQ_ROW};
+  return status("gemm_split_q24", nd::launch_gemm(g, (hipStream_t)stream));
 }
 
 static int ensure_attributes() {
@@ -60,15 +50,10 @@ int nd_op_dec_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b
                   const float* b2, float* x, float* xpart, int32_t M, int32_t F, int32_t nsplit, float* slab,
                   int32_t* tickets, const int32_t* skip, int32_t skip_rpc, int32_t* overflow, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  nd::DecFfn df;
-  df.nsplit = nsplit;
-  df.slab = slab;
-  df.tickets = tickets;
-  df.skip = skip;
-  df.skip_rpc = skip_rpc;
-  hipError_t e = nd::launch_dec_ffn(y, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, df, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ffn: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_ffn", nd::launch_dec_ffn({.y = y, .w1h = w1h, .w1s = w1s, .b1 = b1, .w2h = w2h, .w2s = w2s,
+                                               .b2 = b2, .x = x, .xpart = xpart, .M = M, .F = F, .ovf = overflow},
+                                              {.nsplit = nsplit, .slab = slab, .tickets = tickets, .skip = skip,
+                                               .skip_rpc = skip_rpc}, (hipStream_t)stream));
 }
 
 int64_t nd_op_dec_ffn_slab_floats(int32_t M, int32_t nsplit) {
@@ -79,27 +64,21 @@ int nd_op_gemm_p16(const float* A, const float* W, const float* bias, const floa
                    int32_t N, int32_t K, const float* part_in, int32_t part_n_in, float* part_out, int32_t relu,
                    int32_t* part_n_out, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  nd::GemmArgs g;
-  g.A = A; g.W = W; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K; g.relu = relu != 0;
-  g.norm = part_in != nullptr; g.part_in = part_in; g.part_n_in = part_n_in; g.part_out = part_out;
-  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16: ") + hipGetErrorString(e));
-  if (part_n_out) *part_n_out = g.part_n_out;
-  return ND_OK;
+  return status_p16("gemm_p16", {.A = A, .W = W, .bias = bias, .R = R, .C = C, .norm = part_in != nullptr, .M = M,
+                                 .N = N, .K = K, .relu = relu != 0, .part_out = part_out, .part_in = part_in,
+                                 .part_n_in = part_n_in}, part_n_out, stream);
 }
 
 int nd_op_pack_p16h(const float* W, int32_t N, int32_t K, uint16_t* out, float* wscale, void* stream) {
-  hipError_t e = nd::launch_pack_p16h(W, K, N, K, out, wscale, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("pack_p16h: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("pack_p16h", nd::launch_pack_p16h(W, K, N, K, out, wscale, (hipStream_t)stream));
 }
 
 int nd_op_enc_ffn(const float* y, const uint16_t* w1h, float w1s, const float* b1, const uint16_t* w2h, float w2s,
                   const float* b2, float* x, float* xpart, int32_t M, int32_t F, int32_t* overflow, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  hipError_t e = nd::launch_enc_ffn(y, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_ffn: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("enc_ffn", nd::launch_enc_ffn({.y = y, .w1h = w1h, .w1s = w1s, .b1 = b1, .w2h = w2h, .w2s = w2s,
+                                               .b2 = b2, .x = x, .xpart = xpart, .M = M, .F = F, .ovf = overflow},
+                                              {}, {}, (hipStream_t)stream));
 }
 
 int nd_op_enc_ffn_wo(const float* att, const float* x_in, const uint16_t* woh, float wos, const float* bo,
@@ -107,20 +86,12 @@ int nd_op_enc_ffn_wo(const float* att, const float* x_in, const uint16_t* woh, f
                      float* x, float* xpart, const uint16_t* qkvh, float qkvs, const float* qkvb, float* qkv,
                      int32_t M, int32_t F, int32_t* overflow, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  nd::EncWo wo;
-  wo.att = att;
-  wo.woh = woh;
-  wo.wos = wos;
-  wo.bo = bo;
-  nd::EncQkv qk;
-  qk.wh = qkvh;
-  qk.ws = qkvs;
-  qk.bias = qkvb;
-  qk.out = qkv;
-  hipError_t e = nd::launch_enc_ffn(x_in, w1h, w1s, b1, w2h, w2s, b2, x, xpart, M, F, overflow, (hipStream_t)stream,
-                                    &wo, qkvh ? &qk : nullptr);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_ffn_wo: ") + hipGetErrorString(e));
-  return ND_OK;
+  if (!att && M > 0) return status("enc_ffn_wo", hipErrorInvalidValue);  // this entry is the Wo fold: att is not optional
+  return status("enc_ffn_wo",
+                nd::launch_enc_ffn({.y = x_in, .w1h = w1h, .w1s = w1s, .b1 = b1, .w2h = w2h, .w2s = w2s, .b2 = b2,
+                                    .x = x, .xpart = xpart, .M = M, .F = F, .ovf = overflow},
+                                   {.att = att, .woh = woh, .wos = wos, .bo = bo},
+                                   {.wh = qkvh, .ws = qkvs, .bias = qkvb, .out = qkv}, (hipStream_t)stream));
 }
 
 int nd_op_gemm_p16_split(const float* A, const uint16_t* Wh, float wscale, const float* bias, const float* R, float* C,
@@ -128,14 +99,9 @@ int nd_op_gemm_p16_split(const float* A, const uint16_t* Wh, float wscale, const
                          int32_t relu, int32_t* part_n_out, void* stream) {
   if (int rc = ensure_attributes()) return rc;
   if (!Wh) return fail(ND_ERR_ARG, "gemm_p16_split: null Wh");
-  nd::GemmArgs g;
-  g.A = A; g.Wh = Wh; g.wscale = wscale; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K;
-  g.relu = relu != 0; g.norm = part_in != nullptr; g.part_in = part_in; g.part_n_in = part_n_in;
-  g.part_out = part_out;
-  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_split: ") + hipGetErrorString(e));
-  if (part_n_out) *part_n_out = g.part_n_out;
-  return ND_OK;
+  return status_p16("gemm_p16_split", {.A = A, .bias = bias, .R = R, .C = C, .norm = part_in != nullptr, .M = M,
+                                       .N = N, .K = K, .relu = relu != 0, .part_out = part_out, .part_in = part_in,
+                                       .part_n_in = part_n_in, .Wh = Wh, .wscale = wscale}, part_n_out, stream);
 }
 
 static int gemm_p16_splitk(const float* A, const uint16_t* Wh, const float* W, float wscale, const float* bias,
@@ -146,15 +112,12 @@ static int gemm_p16_splitk(const float* A, const uint16_t* Wh, const float* W, f
     return fail(ND_ERR_ARG, "gemm_p16_splitk: bad arguments");
   if ((K != 1024 && K != 2048) || N % 32 || M <= 128 || ((M + 31) / 32) * (N / 32) > tiles)
     return fail(ND_ERR_ARG, "gemm_p16_splitk: needs K 1024 / 2048, N % 32 == 0, M > 128 and enough tiles");
-  nd::GemmArgs g;
-  g.A = A; g.Wh = Wh; g.W = W; g.wscale = wscale; g.bias = bias; g.R = R; g.C = C; g.M = M; g.N = N; g.K = K;
-  g.part_out = part_out;
-  g.sk_slab = slab; g.sk_cnt = tickets; g.sk_tiles = tiles;
   const long long before = nd::gemm_route_count(ND_ROUTE_P16_SPLITK, false);
-  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_splitk: ") + hipGetErrorString(e));
+  const int rc = status_p16("gemm_p16_splitk", {.A = A, .W = W, .bias = bias, .R = R, .C = C, .M = M, .N = N, .K = K,
+                                                .part_out = part_out, .Wh = Wh, .wscale = wscale, .sk_slab = slab,
+                                                .sk_cnt = tickets, .sk_tiles = tiles}, part_n_out, stream);
+  if (rc != ND_OK) return rc;
   if (nd::gemm_route_count(ND_ROUTE_P16_SPLITK, false) == before) return fail(ND_ERR_ARG, "gemm_p16_splitk: not taken");
-  if (part_n_out) *part_n_out = g.part_n_out;
   return ND_OK;
 }
 
@@ -180,42 +143,32 @@ int nd_op_gemm_p16_split_rm(const float* A, const uint16_t* Wh, float wscale, co
                             int32_t* part_n_out, void* stream) {
   if (int rc = ensure_attributes()) return rc;
   if (!Wh || !Wh_rm) return fail(ND_ERR_ARG, "gemm_p16_split_rm: null weight image");
-  nd::GemmArgs g;
-  g.A = A; g.Wh = Wh; g.wscale = wscale; g.Wh_rm = Wh_rm; g.wscale_rm = wscale_rm; g.bias = bias; g.R = R; g.C = C;
-  g.M = M; g.N = N; g.K = K; g.relu = relu != 0; g.norm = part_in != nullptr; g.part_in = part_in;
-  g.part_n_in = part_n_in; g.part_out = part_out;
-  hipError_t e = nd::launch_gemm_p16(g, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("gemm_p16_split_rm: ") + hipGetErrorString(e));
-  if (part_n_out) *part_n_out = g.part_n_out;
-  return ND_OK;
+  return status_p16("gemm_p16_split_rm",
+                    {.A = A, .bias = bias, .R = R, .C = C, .norm = part_in != nullptr, .M = M, .N = N, .K = K,
+                     .relu = relu != 0, .part_out = part_out, .part_in = part_in, .part_n_in = part_n_in, .Wh = Wh,
+                     .wscale = wscale, .Wh_rm = Wh_rm, .wscale_rm = wscale_rm}, part_n_out, stream);
 }
 
 int nd_op_pack_p16(const float* src, float* dst, int32_t M, int32_t N, void* stream) {
-  hipError_t e = nd::launch_pack_p16(src, N, dst, M, N, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("pack_p16: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("pack_p16", nd::launch_pack_p16(src, N, dst, M, N, (hipStream_t)stream));
 }
 
 int nd_op_fold_layernorm(const float* W, const float* bias, const float* ln_g, const float* ln_b, float* W_out,
                          float* b_out, int32_t N, int32_t K, void* stream) {
-  hipError_t e = nd::launch_fold_layernorm(W, bias, ln_g, ln_b, W_out, b_out, N, K, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("fold_layernorm: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("fold_layernorm", nd::launch_fold_layernorm(W, bias, ln_g, ln_b, W_out, b_out, N, K, (hipStream_t)stream));
 }
 
 int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B, int32_t T,
                         void* stream) {
-  hipError_t e = nd::launch_enc_attention(qkv, signal, span, out, B, T, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("enc_attention: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("enc_attention", nd::launch_enc_attention({.qkv = qkv, .mask = {signal, span}, .out = out, .B = B,
+                                                           .T = T}, (hipStream_t)stream));
 }
 
 int nd_op_dec_self_attention(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
                              int32_t max_steps, float* out, int32_t R, void* stream) {
-  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
-                                                .max_steps = max_steps, .out = out, .R = R}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_self_attention",
+                nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
+                                               .max_steps = max_steps, .out = out, .R = R}, (hipStream_t)stream));
 }
 
 int nd_op_dec_self_attention_beam(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
@@ -223,11 +176,10 @@ int nd_op_dec_self_attention_beam(const float* qkv, float* cache, const int32_t*
                                   void* stream) {
   if (!qkv || !cache || !anc || !out || rpc < 2 || rpc > 8 || R % rpc)
     return fail(ND_ERR_ARG, "dec_self_attention_beam: bad arguments");
-  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
-                                                .max_steps = max_steps, .out = out, .R = R,
-                                                .rows = {.C = R / rpc, .rpc = rpc, .done = done}}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_beam: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_self_attention_beam",
+                nd::launch_dec_self_attention({.qkv = qkv, .cache = cache, .anc = anc, .anc_ld = anc_ld, .step = step,
+                                               .max_steps = max_steps, .out = out, .R = R,
+                                               .rows = {.C = R / rpc, .rpc = rpc, .done = done}}, (hipStream_t)stream));
 }
 
 int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
@@ -235,12 +187,11 @@ int nd_op_dec_self_attention_q24(const float* qkv, void* cache, const int32_t* a
                                  void* stream) {
   if (!qkv || !cache || !out || rpc < 1 || rpc > 8 || R % rpc || (rpc > 1 && !anc))
     return fail(ND_ERR_ARG, "dec_self_attention_q24: bad arguments");
-  hipError_t e = nd::launch_dec_self_attention({.qkv = qkv, .cache = static_cast<float*>(cache), .anc = anc,
-                                                .anc_ld = anc_ld, .step = step, .max_steps = max_steps, .out = out,
-                                                .R = R, .rows = {.C = R / rpc, .rpc = rpc, .done = done}, .q24 = true},
-                                               (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_q24: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_self_attention_q24",
+                nd::launch_dec_self_attention({.qkv = qkv, .cache = static_cast<float*>(cache), .anc = anc,
+                                               .anc_ld = anc_ld, .step = step, .max_steps = max_steps, .out = out,
+                                               .R = R, .rows = {.C = R / rpc, .rpc = rpc, .done = done}, .q24 = true},
+                                              (hipStream_t)stream));
 }
 
 int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int32_t V, const int32_t* tok,
@@ -249,19 +200,17 @@ int nd_op_dec_self_attention_table(const float* table, int32_t table_steps, int3
   if (!table || !tok || !hist || !out || R < 1 || V < 1 || step < 0 || step >= table_steps)
     return fail(ND_ERR_ARG, "dec_self_attention_table: bad arguments");
   const nd::QkvRows qr{.tok = tok, .V = V, .tok0 = tok0, .rm = 1, .hist = hist, .hist_ld = hist_ld};
-  hipError_t e = nd::launch_dec_self_attention({.qkv = table, .cache = cache, .step = step, .max_steps = max_steps,
-                                                .out = out, .R = R, .rows = {.C = R}, .qr = qr}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_self_attention_table: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_self_attention_table",
+                nd::launch_dec_self_attention({.qkv = table, .cache = cache, .step = step, .max_steps = max_steps,
+                                               .out = out, .R = R, .rows = {.C = R}, .qr = qr}, (hipStream_t)stream));
 }
 
 int nd_op_dec_mem_attention(const float* qp, const float* mem, const float* signal, const int32_t* span, float pad_val,
                             float* out, int32_t C, int32_t rpc, int32_t T, int32_t ldT, int32_t grid, void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  hipError_t e = nd::launch_dec_mem_attention({.qp = qp, .mem = mem, .mask = {signal, span, pad_val}, .out = out, .C = C,
-                                               .rpc = rpc, .T = T, .ldT = ldT, .grid = grid}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_mem_attention: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_mem_attention",
+                nd::launch_dec_mem_attention({.qp = qp, .mem = mem, .mask = {signal, span, pad_val}, .out = out, .C = C,
+                                              .rpc = rpc, .T = T, .ldT = ldT, .grid = grid}, (hipStream_t)stream));
 }
 
 int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
@@ -271,25 +220,22 @@ int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, co
     return fail(ND_ERR_ARG, "lstm_layer: bad arguments");
   if ((bn_scale == nullptr) != (bn_shift == nullptr))
     return fail(ND_ERR_ARG, "lstm_layer: bn_scale and bn_shift must both be set or both be null");
-  hipError_t e = nd::launch_lstm_layer(xp, signal, wih0, bsum, whh, len, B, T, out, bn_scale, bn_shift, layer0 != 0,
-                                       (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("lstm_layer: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("lstm_layer",
+                nd::launch_lstm_layer({.xp = xp, .signal = signal, .wih0 = wih0, .bsum = bsum, .whh = whh, .len = len,
+                                       .B = B, .T = T, .out = out, .bn_scale = bn_scale, .bn_shift = bn_shift,
+                                       .layer0 = layer0 != 0}, (hipStream_t)stream));
 }
 
 int nd_normalize_reads(const double* d_raw, const int64_t* d_offsets, int32_t R, int32_t method, float* d_out,
                        void* stream) {
-  hipError_t e = nd::launch_read_normalize(d_raw, (const long long*)d_offsets, R, method, d_out, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("normalize_reads: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("normalize_reads",
+                nd::launch_read_normalize(d_raw, (const long long*)d_offsets, R, method, d_out, (hipStream_t)stream));
 }
 
 int nd_window_reads(const float* d_sig, const int64_t* d_offsets, const int32_t* d_read, const int32_t* d_start,
                     const int32_t* d_len, int32_t C, int32_t T, float* d_signal, void* stream) {
-  hipError_t e = nd::launch_read_window(d_sig, (const long long*)d_offsets, d_read, d_start, d_len, C, T, d_signal,
-                                        (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("window_reads: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("window_reads", nd::launch_read_window(d_sig, (const long long*)d_offsets, d_read, d_start, d_len, C, T,
+                                                       d_signal, (hipStream_t)stream));
 }
 
 int64_t nd_assemble_reads_work_bytes(int32_t C, int64_t total_bases) {
@@ -309,26 +255,23 @@ int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const 
       (total_bases > 0 && (!d_bases || !d_seq)))
     return fail(ND_ERR_ARG, "assemble_reads: null buffer");
   if (R == 0) return ND_OK;
-  hipError_t e = nd::launch_assemble_reads(d_bases, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq, d_seq_len,
-                                           d_status, d_work, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_HIP, std::string("assemble_reads: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("assemble_reads",
+                nd::launch_assemble_reads(d_bases, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq, d_seq_len,
+                                          d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
 }
 
 int nd_op_memory_pack(const float* x, const float* ln_g, const float* ln_b, float* out, int32_t B, int32_t T,
                       int32_t ldT, void* stream) {
-  hipError_t e = nd::launch_memory_pack(x, ln_g, ln_b, out, B, T, ldT, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("memory_pack: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("memory_pack", nd::launch_memory_pack(x, ln_g, ln_b, out, B, T, ldT, (hipStream_t)stream));
 }
 
 int nd_op_bank_pack_d8(const float* x, const float* ln_g, const float* ln_b, void* bank, float* kscale,
                        int32_t* kemax, const int32_t* span, int32_t B, int32_t T, int32_t* ovf, void* stream) {
   if (!x || !bank || !kscale || !kemax || (ln_g == nullptr) != (ln_b == nullptr))
     return fail(ND_ERR_ARG, "bank_pack_d8: bad arguments");
-  hipError_t e = nd::launch_bank_pack_d8(x, ln_g, ln_b, bank, kscale, kemax, span, B, T, ovf, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("bank_pack_d8: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("bank_pack_d8",
+                nd::launch_bank_pack_d8({.x = x, .ln_g = ln_g, .ln_b = ln_b, .bank = bank, .kscale = kscale,
+                                         .kemax = kemax, .span = span, .B = B, .T = T, .ovf = ovf}, (hipStream_t)stream));
 }
 
 int nd_op_dec_bank_d8(const float* qp, const void* bank, const float* kscale, const int32_t* kemax,
@@ -337,40 +280,36 @@ int nd_op_dec_bank_d8(const float* qp, const void* bank, const float* kscale, co
   if (int rc = ensure_attributes()) return rc;
   if (!qp || !bank || !kscale || !kemax || !signal || !span || !out || grid < 0)
     return fail(ND_ERR_ARG, "dec_bank_d8: bad arguments");
-  hipError_t e = nd::launch_dec_bank_d8({.qp = qp, .bank = bank, .kscale = kscale, .kemax = kemax,
-                                         .mask = {signal, span, pad_val}, .out = out, .C = C, .T = T, .ovf = ovf,
-                                         .grid = grid}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_bank_d8: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_bank_d8",
+                nd::launch_dec_bank_d8({.qp = qp, .bank = bank, .kscale = kscale, .kemax = kemax,
+                                        .mask = {signal, span, pad_val}, .out = out, .C = C, .T = T, .ovf = ovf,
+                                        .grid = grid}, (hipStream_t)stream));
 }
 
 int nd_op_dec_ctx_attention(const float* q, const float* kv, int32_t ld, int32_t koff, const float* signal,
                             const int32_t* span, float pad_val, float* out, int32_t C, int32_t rpc, int32_t T,
                             void* stream) {
   if (int rc = ensure_attributes()) return rc;
-  hipError_t e = nd::launch_dec_ctx_attention({.q = q, .kv = kv, .ld = ld, .koff = koff, .T = T, .out = out,
-                                               .mask = {signal, span, pad_val}, .rows = {.C = C, .rpc = rpc}},
-                                              (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_ctx_attention",
+                nd::launch_dec_ctx_attention({.q = q, .kv = kv, .ld = ld, .koff = koff, .T = T, .out = out,
+                                              .mask = {signal, span, pad_val}, .rows = {.C = C, .rpc = rpc}},
+                                             (hipStream_t)stream));
 }
 
 int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
                        const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
                        int32_t Lk, int32_t causal, void* stream) {
-  hipError_t e = nd::launch_tf_attention({.q = q, .ldq = ldq, .kv = kv, .ldkv = ldkv, .koff = koff, .voff = voff,
-                                          .mask = {signal, span, pad_val}, .out = out, .B = B, .Lq = Lq, .Lk = Lk,
-                                          .causal = causal != 0}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("tf_attention: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("tf_attention",
+                nd::launch_tf_attention({.q = q, .ldq = ldq, .kv = kv, .ldkv = ldkv, .koff = koff, .voff = voff,
+                                         .mask = {signal, span, pad_val}, .out = out, .B = B, .Lq = Lq, .Lk = Lk,
+                                         .causal = causal != 0}, (hipStream_t)stream));
 }
 
 int nd_op_ctx_pack_q24(const float* kv, int32_t ld, int32_t layers, void* out, const int32_t* span, int32_t B,
                        int32_t T, void* stream) {
   if (!kv || !out || !span) return fail(ND_ERR_ARG, "ctx_pack_q24: bad arguments");
-  hipError_t e = nd::launch_ctx_pack_q24(kv, ld, layers, static_cast<uint8_t*>(out), span, B, T, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("ctx_pack_q24: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("ctx_pack_q24",
+                nd::launch_ctx_pack_q24(kv, ld, layers, static_cast<uint8_t*>(out), span, B, T, (hipStream_t)stream));
 }
 
 int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int32_t koff, int32_t q24,
@@ -380,19 +319,15 @@ int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int
   if (int rc = ensure_attributes()) return rc;
   if (!q || !kv || !signal || !span || !out || !clist || (nsplit > 1 && !part))
     return fail(ND_ERR_ARG, "dec_ctx_attention_list: bad arguments");
-  hipError_t e = nd::launch_dec_ctx_attention(
+  return status("dec_ctx_attention_list", nd::launch_dec_ctx_attention(
       {.q = q, .kv = kv, .ld = ld, .koff = koff, .q24 = q24 != 0, .T = T, .out = out, .mask = {signal, span, pad_val},
        .rows = {.C = C, .rpc = rpc, .done = done, .clist = clist, .ccap = ccap}, .nsplit = nsplit, .part = part},
-      (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_list: ") + hipGetErrorString(e));
-  return ND_OK;
+      (hipStream_t)stream));
 }
 
 int nd_op_alive_list(const int32_t* done, int32_t C, int32_t* list, int32_t cap, int32_t* ovf, void* stream) {
   if (!done || !list) return fail(ND_ERR_ARG, "alive_list: bad arguments");
-  hipError_t e = nd::launch_alive_list(done, C, list, cap, ovf, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("alive_list: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("alive_list", nd::launch_alive_list(done, C, list, cap, ovf, (hipStream_t)stream));
 }
 
 int nd_op_dec_ctx_attention_q24(const float* q, const void* kvq, int32_t layers, int32_t layer, const float* signal,
@@ -402,9 +337,8 @@ int nd_op_dec_ctx_attention_q24(const float* q, const void* kvq, int32_t layers,
   if (!q || !kvq || !signal || !span || !out || layer < 0 || layer >= layers)
     return fail(ND_ERR_ARG, "dec_ctx_attention_q24: bad arguments");
   const uint8_t* plane = static_cast<const uint8_t*>(kvq) + (size_t)layer * C * T * CTXQ_ROW;
-  hipError_t e = nd::launch_dec_ctx_attention({.q = q, .kv = plane, .ld = CTXQ_ROW, .koff = 0, .q24 = true, .T = T,
-                                               .out = out, .mask = {signal, span, pad_val},
-                                               .rows = {.C = C, .rpc = rpc}}, (hipStream_t)stream);
-  if (e != hipSuccess) return fail(ND_ERR_ARG, std::string("dec_ctx_attention_q24: ") + hipGetErrorString(e));
-  return ND_OK;
+  return status("dec_ctx_attention_q24",
+                nd::launch_dec_ctx_attention({.q = q, .kv = plane, .ld = CTXQ_ROW, .koff = 0, .q24 = true, .T = T,
+                                              .out = out, .mask = {signal, span, pad_val},
+                                              .rows = {.C = C, .rpc = rpc}}, (hipStream_t)stream));
 }

@@ -1,5 +1,6 @@
-"""Decoder attention op entries that set kernel attributes before they validate (needs an MI355X): each
-refusal returns ND_ERR_ARG from the launcher and launches nothing (the output keeps its sentinel)."""
+"""Decoder attention, FFN, P16 GEMM and encoder attention op entries whose refusal comes from the launcher, most
+of them after the kernel attributes are set (needs an MI355X): each returns ND_ERR_ARG and launches nothing
+(the output keeps its sentinel)."""
 import ctypes
 
 import pytest
@@ -67,3 +68,58 @@ def test_bank_d8_refuses_long_chunk(bufs):
     rc = _lib.lib().nd_op_dec_bank_d8(_p(b["q"]), _p(b["bank"]), _p(b["ks"]), _p(b["em"]), _p(b["signal"]),
                                       _p(b["span"]), PAD, _p(b["out"]), C, 513, None, 0, None)
     _refused(b, rc, b"dec_bank_d8")
+
+
+def _enc_ffn(b, y, x, F):
+    w = _p(b["q"])
+    return _lib.lib().nd_op_enc_ffn(y, w, 1.0, w, w, 1.0, w, x, _p(b["part"]), 16, F, None, None)
+
+
+def test_enc_ffn_refuses_ragged_d_ff(bufs):
+    _refused(bufs, _enc_ffn(bufs, _p(bufs["q"]), _p(bufs["out"]), 48), b"enc_ffn")  # F % 32 != 0
+
+
+def test_enc_ffn_refuses_in_place(bufs):
+    _refused(bufs, _enc_ffn(bufs, _p(bufs["out"]), _p(bufs["out"]), 64), b"enc_ffn")  # x == y without the Wo fold
+
+
+def test_enc_ffn_wo_refuses_attention_rows_as_output(bufs):
+    b = bufs
+    w, x = _p(b["q"]), _p(b["out"])
+    rc = _lib.lib().nd_op_enc_ffn_wo(x, _p(b["kv"]), w, 1.0, w, w, 1.0, w, w, 1.0, w, x, _p(b["part"]), None, 1.0,
+                                     None, None, 16, 64, None, None)  # att == x
+    _refused(b, rc, b"enc_ffn_wo")
+
+
+@pytest.mark.parametrize("M,nsplit,slab", [
+    (24, 1, True),    # P16 rows come in blocks of 16
+    (16, 3, True),    # more splits than d_ff has 32-wide chunks (F = 64)
+    (16, 2, False),   # a split launch needs its slab
+])
+def test_dec_ffn_refuses(bufs, M, nsplit, slab):
+    b = bufs
+    w = _p(b["q"])
+    rc = _lib.lib().nd_op_dec_ffn(_p(b["kv"]), w, 1.0, w, w, 1.0, w, _p(b["out"]), _p(b["part"]), M, 64, nsplit,
+                                  _p(b["bank"]) if slab else None, _p(b["em"]), None, 1, None, None)
+    _refused(b, rc, b"dec_ffn")
+
+
+@pytest.mark.parametrize("N,K", [(24, 256), (16, 384)])  # N % 16 != 0; no kernel for this K
+def test_gemm_p16_refuses(bufs, N, K):
+    b = bufs
+    rc = _lib.lib().nd_op_gemm_p16(_p(b["kv"]), _p(b["bank"]), _p(b["q"]), None, _p(b["out"]), 16, N, K, None, 0,
+                                   None, 0, None, None)
+    _refused(b, rc, b"gemm_p16")
+
+
+def test_gemm_p16_split_refuses_partial_count(bufs):
+    b = bufs
+    rc = _lib.lib().nd_op_gemm_p16_split(_p(b["kv"]), _p(b["bank"]), 1.0, _p(b["q"]), None, _p(b["out"]), 16, 16, 256,
+                                         _p(b["part"]), 3, None, 0, None, None)  # 3 partials do not tile 256 columns
+    _refused(b, rc, b"gemm_p16_split")
+
+
+def test_enc_attention_refuses_long_chunk(bufs):
+    b = bufs
+    rc = _lib.lib().nd_op_enc_attention(_p(b["bank"]), _p(b["signal"]), _p(b["span"]), _p(b["out"]), C, 513, None)
+    _refused(b, rc, b"enc_attention")

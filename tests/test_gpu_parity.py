@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 import torch
 
-from nanodecoder_amd import synth
+from nanodecoder_amd import _lib, synth
 from tests import golden_util as gu
 
 pytestmark = pytest.mark.gpu
@@ -315,8 +315,10 @@ def test_gemm_p16_vs_fp64(M, N, K, ln, relu, res, stats, split):
     part_out = torch.full(((M + 15) // 16 * 16, 16, 2), float("nan"), device=dev) if stats else None
     Wh, sc = op_pack_p16h(Wd) if split else (None, 1.0)
     Wr, sr = op_split_weight(Wd) if split == "rm" else (None, 1.0)  # large M: the LDS-tiled kernel on P16 operands
+    _lib.gemm_routes(reset=True)
     Cp, pn = op_gemm_p16(pack_p16(A.to(dev)), pack_p16(Wd), bd, M, N, K, pack_p16(R.to(dev)) if res else None,
                          part_in, relu, part_out, Wh=Wh, wscale=sc, Wh_rm=Wr, wscale_rm=sr)
+    routes = _lib.gemm_routes(reset=True)
     out = unpack_p16(Cp, M).cpu().double()
     a = A.double()
     if ln:
@@ -328,7 +330,11 @@ def test_gemm_p16_vs_fp64(M, N, K, ln, relu, res, stats, split):
         ref = ref + R.double()
     assert (out - ref).abs().max().item() < 2e-4
     if stats:
-        assert pn in (N // 16, N // 64, N // 128, N // 256)   # one partial per column tile of the kernel taken
+        # one partial per column tile of the kernel taken: a 16-column block on every P16 kernel, the tile's
+        # width on the LDS-tiled kernel (the large-M route; its 128 and 256 tiles start at M = 32641 and 65281)
+        assert not routes["p16_n64"] and not routes["p16_ln128"]  # retired: no shape reaches them
+        width = next((w for r, w in (("tile64", 64), ("tile128", 128), ("tile256", 256)) if routes[r]), 16)
+        assert pn == N // width
         want = row_partials(out.float(), pn)[:, :pn]
         got = part_out[:M, :pn].cpu()
         assert torch.allclose(got[:, :, 0], want[:, :, 0], atol=1e-5)
