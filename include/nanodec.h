@@ -264,6 +264,46 @@ int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const 
                       int32_t C, int64_t total_bases, uint8_t* d_seq, int32_t* d_seq_len, int32_t* d_status,
                       void* d_work, int64_t work_bytes, void* stream);
 
+/* Per-base qualities (FASTQ).  The reference writes no qualities; these three
+ * entry points carry the model's own probability of each called token through
+ * the assembly vote.  No context needed.
+ *
+ * Token weight of a token with log-probability lp (fp32):
+ *   w = min(65535, floor(65535 * exp((double)lp) + 0.5)), a uint16; 0 for a
+ *   non-finite lp or a token id outside [0, V) (the beam's -1 padding).
+ * nd_token_weights writes d_w [B, S] from d_tokens [B, S] and exactly one of
+ *   d_logp     [B, S, V] f32: lp = d_logp[b][s][d_tokens[b][s]]
+ *   d_tok_logp [B, S]    f32: lp = d_tok_logp[b][s]
+ * in one launch on `stream`, with no allocation and no synchronisation.
+ * Negative sizes, V < 1, B * S >= 2^31, a null buffer, or neither or both of
+ * the two log-prob inputs return ND_ERR_ARG before any HIP call.
+ *
+ * Column quality of one column of a read's vote: n = its votes of all classes,
+ * S = the sum of the weights of the votes for the winning class (the winner
+ * exactly as nd_assemble_reads picks it), E = 65535 n - S; Q is the largest k
+ * in 0..40 with (double)E * RATIO[k] <= (double)(65535 n), RATIO[k] the double
+ * 10.0 ** (k / 10.0); Q = 0 when n = 0.  nd_phred_ratios copies the first
+ * n <= 41 entries of RATIO out (ND_ERR_ARG for a null out or another n).
+ *
+ * nd_assemble_reads_q is nd_assemble_reads with
+ *   d_qw   [total_bases] u16 (in):  the weight of each byte of d_bases
+ *   d_qual [total_bases] u8  (out): Q of the columns of the assembled reads,
+ *          laid out like d_seq; 0 past a read's length
+ * Overlap, placement, d_seq, d_seq_len and d_status are those of
+ * nd_assemble_reads on the same input; the weight sums are 64-bit integers,
+ * so the bytes do not depend on the order the votes arrive in.  d_work holds
+ * nd_assemble_reads_q_work_bytes(C, total_bases) bytes (nd_assemble_reads' plus
+ * 5 * total_bases * 8); argument checks and the R == 0 and C == 0 paths as
+ * nd_assemble_reads. */
+int nd_token_weights(const int32_t* d_tokens, const float* d_logp, const float* d_tok_logp, int32_t B, int32_t S,
+                     int32_t V, uint16_t* d_w, void* stream);
+int nd_phred_ratios(double* out, int32_t n);
+int64_t nd_assemble_reads_q_work_bytes(int32_t C, int64_t total_bases);
+int nd_assemble_reads_q(const uint8_t* d_bases, const uint16_t* d_qw, const int32_t* d_chunk_off,
+                        const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
+                        uint8_t* d_qual, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
+                        void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

@@ -6,6 +6,7 @@ and windowed in a worker pool (translate.py:131-163), translated, and written
 as result/<read>.fasta, segment/<read>.txt and a line of speed.txt
 (translate.py:81-98).  One bad read prints ``!!!error!!!`` and the run goes
 on (translate.py:97-98).  ``-pack_reads N`` translates N reads per engine pass.
+``-fastq`` also writes result/<read>.fastq with per-base qualities.
 """
 from __future__ import annotations
 
@@ -110,13 +111,21 @@ def _extract(args):
         return ["!" + prefix, repr(e)]
 
 
-def write_output(opt, file_src, all_predictions, time_translate, sequence=None):
+def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None):
     """translate.py:81-98.  ``sequence``: the read already assembled
-    (-assembly gpu); None assembles it here."""
+    (-assembly gpu); None assembles it here.  ``weights`` (-fastq): the
+    chunks' per-base weights; ``sequence`` is then (sequence, quality string),
+    and result/<read>.fastq is written before the .fasta resume keys on."""
     try:
-        c_bpread = sequence if sequence is not None else \
-            frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
         name = file_src.split(".txt")[0]
+        if weights is not None:
+            c_bpread, quality = sequence if sequence is not None else \
+                frontend.assemble_read_q(all_predictions, weights, opt.src_seq_length, opt.src_seq_stride)
+            with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
+                f.write("@%s\n%s\n+\n%s\n" % (name, c_bpread, quality))
+        else:
+            c_bpread = sequence if sequence is not None else \
+                frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
         with open(os.path.join(opt.save_data, "result", name + ".fasta"), "w") as f:
             f.writelines(">%s\n%s" % (name, c_bpread))
         with open(os.path.join(opt.save_data, "segment", file_src), "w+") as f:
@@ -134,6 +143,8 @@ ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled /
 
 def main(opt=None):
     opt = opt or parse_translate_opts()
+    if getattr(opt, "fastq", False) and opt.attn_debug:
+        raise ValueError("-fastq is not available together with -attn_debug")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
@@ -185,6 +196,8 @@ def _translate_attn(opt, translator, group):
 
 def _translate_group(opt, translator, group, raw=False):
     t0 = time.time()
+    fastq = bool(getattr(opt, "fastq", False))
+    want = dict(qualities=True) if fastq else {}
     try:
         if opt.attn_debug:
             outs = _translate_attn(opt, translator, group)
@@ -192,28 +205,30 @@ def _translate_group(opt, translator, group, raw=False):
             outs = translator.translate_raw_reads([g[1] for g in group], batch_size=opt.batch_size,
                                                   normalization=opt.normalization_raw,
                                                   src_seq_length=opt.src_seq_length,
-                                                  src_seq_stride=opt.src_seq_stride)
+                                                  src_seq_stride=opt.src_seq_stride, **want)
         else:
-            outs = translator.translate_reads([g[1:] for g in group], batch_size=opt.batch_size)
+            outs = translator.translate_reads([g[1:] for g in group], batch_size=opt.batch_size, **want)
     except Exception as e:
         for g in group:
             print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
         return 0
     dt = time.time() - t0
-    total = max(1, sum(len(preds) for _, preds in outs))
+    total = max(1, sum(len(o[1]) for o in outs))
     seqs = [None] * len(outs)
+    weights = [o[2] for o in outs] if fastq else [None] * len(outs)  # -fastq: per chunk, its bases' weights
     if getattr(opt, "assembly", "cpu") == "gpu":
         # the whole group in one device call; a read left None (its host fallback raised) is assembled
         # again by write_output, which reports that read's error as -assembly cpu does
         try:
-            seqs = frontend.assemble_reads([preds for _, preds in outs], opt.src_seq_length, opt.src_seq_stride,
-                                           device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True)
+            seqs = frontend.assemble_reads([o[1] for o in outs], opt.src_seq_length, opt.src_seq_stride,
+                                           device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True,
+                                           **(dict(weights=weights) if fastq else {}))
         except Exception as e:
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    for g, (_, preds), seq in zip(group, outs, seqs):
-        write_output(opt, g[0], preds, dt * len(preds) / total, sequence=seq)
+    for g, o, seq, w in zip(group, outs, seqs, weights):
+        write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w)
     return len(group)
 
 

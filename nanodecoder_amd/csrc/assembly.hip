@@ -28,6 +28,14 @@
 // A read's consensus is never longer than the sum of its chunk lengths
 // (disp <= la), so read r's counts and output live at the byte offset of its
 // first chunk, chunk_off[read_off[r]].
+//
+// With per-base weights (nd_assemble_reads_q) the same four kernels also carry
+// a quality through the vote: the vote kernel adds each base's uint16 weight
+// into wsum[5][total_bases] (64-bit unsigned integer atomics: the number of
+// chunks on one column is not bounded, and integer sums do not depend on the
+// arrival order), and the call kernel turns a column's n votes and the winning
+// class's weight sum S into Q, the largest k in 0..40 with
+// (double)(65535 n - S) * PHRED_RATIO[k] <= (double)(65535 n); 0 when n = 0.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -35,6 +43,21 @@ namespace nd {
 
 #define ASM_THREADS 256
 #define ASM_MAXLEN 199  // longest chunk assembled here (difflib autojunk starts at 200)
+
+// the doubles 10.0 ** (k / 10.0), k = 0..40, printed with 17 significant digits
+#define ASM_PHRED_RATIOS                                                                          \
+  1, 1.2589254117941673, 1.5848931924611136, 1.9952623149688795, 2.5118864315095801,              \
+  3.1622776601683795, 3.9810717055349722, 5.011872336272722, 6.3095734448019334,                  \
+  7.9432823472428158, 10, 12.589254117941675, 15.848931924611133, 19.952623149688797,             \
+  25.118864315095795, 31.622776601683793, 39.810717055349734, 50.118723362727224,                 \
+  63.095734448019329, 79.43282347242814, 100, 125.89254117941675, 158.48931924611142,             \
+  199.52623149688787, 251.18864315095797, 316.22776601683796, 398.10717055349733,                 \
+  501.18723362727246, 630.957344480193, 794.32823472428129, 1000, 1258.9254117941675,             \
+  1584.893192461114, 1995.2623149688789, 2511.8864315095798, 3162.2776601683795,                  \
+  3981.0717055349733, 5011.8723362727251, 6309.5734448019302, 7943.2823472428136, 10000
+static const double h_phred_ratio[PHRED_LEVELS] = {ASM_PHRED_RATIOS};
+__constant__ double d_phred_ratio[PHRED_LEVELS] = {ASM_PHRED_RATIOS};
+const double* phred_ratios() { return h_phred_ratio; }
 
 __device__ __forceinline__ int asm_class(unsigned char ch) {
   if (ch >= 'a' && ch <= 'z') ch -= 32;
@@ -156,11 +179,14 @@ asm_place_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read
   if (tid == 0) seq_len[r] = smax[0];
 }
 
-// one wave per chunk: its chars vote at pos[c] + x of the read's columns
+// one wave per chunk: its chars vote at pos[c] + x of the read's columns; QUAL: each vote's weight qw[.] is
+// added to wsum of its class and column
+template <bool QUAL>
 __global__ void __launch_bounds__(ASM_THREADS)
-asm_vote_kernel(const unsigned char* __restrict__ bases, const int* __restrict__ chunk_off,
-                const int* __restrict__ read_off, const int* __restrict__ pos, const int* __restrict__ rd,
-                const int* __restrict__ status, int C, int total, int* __restrict__ count) {
+asm_vote_kernel(const unsigned char* __restrict__ bases, const unsigned short* __restrict__ qw,
+                const int* __restrict__ chunk_off, const int* __restrict__ read_off, const int* __restrict__ pos,
+                const int* __restrict__ rd, const int* __restrict__ status, int C, int total,
+                int* __restrict__ count, unsigned long long* __restrict__ wsum) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -169,15 +195,21 @@ asm_vote_kernel(const unsigned char* __restrict__ bases, const int* __restrict__
   const int r0 = chunk_off[read_off[r]], cols = chunk_off[read_off[r + 1]] - r0;
   for (int x = lane; x < len; x += 64) {
     const int col = p + x, cls = asm_class(bases[o + x]);
-    if (col >= 0 && col < cols && r0 + col < total && cls >= 0) atomicAdd(&count[(size_t)cls * total + r0 + col], 1);
+    if (col >= 0 && col < cols && r0 + col < total && cls >= 0) {
+      atomicAdd(&count[(size_t)cls * total + r0 + col], 1);
+      if (QUAL) atomicAdd(&wsum[(size_t)cls * total + r0 + col], (unsigned long long)qw[o + x]);
+    }
   }
 }
 
-// one wave per chunk's span of the output: column g - r0 of read rd[c], 0 past the read's length
+// one wave per chunk's span of the output: column g - r0 of read rd[c], 0 past the read's length; QUAL: the
+// column's Q from its votes and the winning class's weight sum
+template <bool QUAL>
 __global__ void __launch_bounds__(ASM_THREADS)
 asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_off, const int* __restrict__ rd,
-                const int* __restrict__ seq_len, const int* __restrict__ count, int C, int total,
-                unsigned char* __restrict__ seq) {
+                const int* __restrict__ seq_len, const int* __restrict__ count,
+                const unsigned long long* __restrict__ wsum, int C, int total, unsigned char* __restrict__ seq,
+                unsigned char* __restrict__ qual) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -186,53 +218,101 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
   for (int x = lane; x < len; x += 64) {
     const int g = o + x;
     if (g >= total) break;
-    unsigned char out = 0;
+    unsigned char out = 0, q = 0;
     if (g - r0 < n) {
       int best = count[g], cls = 0;
+      long long votes = best;
       for (int k = 1; k < 5; ++k) {
         const int v = count[(size_t)k * total + g];
+        votes += v;
         if (v > best) {
           best = v;
           cls = k;
         }
       }
       out = (unsigned char)((0x4D54474341ull >> (8 * cls)) & 0xFFu);  // "ACGTM"[cls]
+      if (QUAL && votes > 0) {
+        const unsigned long long full = 65535ull * (unsigned long long)votes;
+        const double e = (double)(full - wsum[(size_t)cls * total + g]), f = (double)full;  // both exact
+        for (int k = 1; k < PHRED_LEVELS && e * d_phred_ratio[k] <= f; ++k) q = (unsigned char)k;
+      }
     }
     seq[g] = out;
+    if (QUAL) qual[g] = q;
   }
 }
 
-size_t assemble_work_bytes(int C, long long total) {
-  return (size_t)2 * C * sizeof(int) + (size_t)5 * total * sizeof(int);
+size_t assemble_work_bytes(int C, long long total, bool qual) {
+  return (size_t)2 * C * sizeof(int) + (size_t)5 * total * sizeof(int) +
+         (qual ? (size_t)5 * total * sizeof(unsigned long long) : 0);
 }
 
-hipError_t launch_assemble_reads(const unsigned char* bases, const int* chunk_off, const int* read_off, int R, int C,
-                                 int total, unsigned char* seq, int* seq_len, int* status, void* work,
-                                 hipStream_t s) {
+hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
+                                 const int* read_off, int R, int C, int total, unsigned char* seq,
+                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s) {
+  const bool q = qual != nullptr;  // with qualities: qw and qual both given
   if (R < 0 || C < 0 || total < 0 || !chunk_off || !read_off || (R > 0 && (!seq_len || !status)) ||
-      (C > 0 && !work) || (total > 0 && (!bases || !seq)))
+      (C > 0 && !work) || (total > 0 && (!bases || !seq)) || (qw != nullptr) != q)
     return hipErrorInvalidValue;
   if (R == 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(status, 0, (size_t)R * sizeof(int), s);
   if (e != hipSuccess) return e;
   if (C == 0) return hipMemsetAsync(seq_len, 0, (size_t)R * sizeof(int), s);  // no chunks: every read is ""
-  int* pos = static_cast<int*>(work);
+  // the 64-bit weight sums first, so they are 8-byte aligned whatever C is
+  unsigned long long* wsum = static_cast<unsigned long long*>(work);
+  int* pos = q ? reinterpret_cast<int*>(wsum + (size_t)5 * total) : static_cast<int*>(work);
   int* rd = pos + C;
   int* count = rd + C;
   if (total > 0) {
     e = hipMemsetAsync(count, 0, (size_t)5 * total * sizeof(int), s);
+    if (e == hipSuccess && q) e = hipMemsetAsync(wsum, 0, (size_t)5 * total * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
   }
   const int per = ASM_THREADS / 64;
-  hipLaunchKernelGGL(asm_overlap_kernel, dim3(C), dim3(ASM_THREADS), 0, s, bases, chunk_off, read_off, R, pos, rd,
-                     status);
-  hipLaunchKernelGGL(asm_place_kernel, dim3(R), dim3(ASM_THREADS), 0, s, chunk_off, read_off, pos, status, seq_len);
-  if (total > 0) {
-    hipLaunchKernelGGL(asm_vote_kernel, dim3((C + per - 1) / per), dim3(ASM_THREADS), 0, s, bases, chunk_off,
-                       read_off, pos, rd, status, C, total, count);
-    hipLaunchKernelGGL(asm_call_kernel, dim3((C + per - 1) / per), dim3(ASM_THREADS), 0, s, chunk_off, read_off, rd,
-                       seq_len, count, C, total, seq);
+  const dim3 grid((C + per - 1) / per), block(ASM_THREADS);
+  hipLaunchKernelGGL(asm_overlap_kernel, dim3(C), block, 0, s, bases, chunk_off, read_off, R, pos, rd, status);
+  hipLaunchKernelGGL(asm_place_kernel, dim3(R), block, 0, s, chunk_off, read_off, pos, status, seq_len);
+  if (total > 0 && q) {
+    hipLaunchKernelGGL(asm_vote_kernel<true>, grid, block, 0, s, bases, qw, chunk_off, read_off, pos, rd, status, C,
+                       total, count, wsum);
+    hipLaunchKernelGGL(asm_call_kernel<true>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, C,
+                       total, seq, qual);
+  } else if (total > 0) {
+    hipLaunchKernelGGL(asm_vote_kernel<false>, grid, block, 0, s, bases, qw, chunk_off, read_off, pos, rd, status, C,
+                       total, count, wsum);
+    hipLaunchKernelGGL(asm_call_kernel<false>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, C,
+                       total, seq, qual);
   }
+  return hipGetLastError();
+}
+
+// w[i] = the token weight of tokens[i]: min(65535, floor(65535 exp((double)lp) + 0.5)) of its log-prob lp
+// (logp[i][tokens[i]], or tok_logp[i]); 0 for a token outside [0, V) or a non-finite lp
+#define TW_THREADS 256
+__global__ void __launch_bounds__(TW_THREADS)
+token_weights_kernel(const int* __restrict__ tokens, const float* __restrict__ logp,
+                     const float* __restrict__ tok_logp, int n, int V, unsigned short* __restrict__ w) {
+  const int i = blockIdx.x * TW_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int t = tokens[i];
+  unsigned short out = 0;
+  if (t >= 0 && t < V) {
+    const float lp = logp ? logp[(size_t)i * V + t] : tok_logp[i];
+    if (isfinite(lp)) {
+      const double x = floor(__dadd_rn(__dmul_rn(65535.0, exp((double)lp)), 0.5));  // a product, then a sum: no FMA
+      out = (unsigned short)(x < 65535.0 ? x : 65535.0);
+    }
+  }
+  w[i] = out;
+}
+
+hipError_t launch_token_weights(const int* tokens, const float* logp, const float* tok_logp, int n, int V,
+                                unsigned short* w, hipStream_t s) {
+  if (n < 0 || V < 1 || (n > 0 && (!tokens || !w)) || (logp != nullptr) == (tok_logp != nullptr))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(token_weights_kernel, dim3((n + TW_THREADS - 1) / TW_THREADS), dim3(TW_THREADS), 0, s, tokens,
+                     logp, tok_logp, n, V, w);
   return hipGetLastError();
 }
 

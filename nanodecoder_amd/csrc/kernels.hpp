@@ -398,11 +398,20 @@ hipError_t launch_read_window(const float* sig, const long long* off, const int*
 // strings (ASCII, spaces removed) are concatenated in bases[total]: chunk c = chunk_off[c] .. chunk_off[c+1],
 // read r = chunks read_off[r] .. read_off[r+1].  Read r's bases go to seq at chunk_off[read_off[r]], their
 // count to seq_len[r]; status[r] != 0 (bit 0: a chunk of 200 or more chars, bit 1: a char outside ACGTM) means
-// the read was not assembled (seq_len[r] = -1).  work holds assemble_work_bytes(C, total) bytes
-size_t assemble_work_bytes(int C, long long total);
-hipError_t launch_assemble_reads(const unsigned char* bases, const int* chunk_off, const int* read_off, int R, int C,
-                                 int total, unsigned char* seq, int* seq_len, int* status, void* work,
-                                 hipStream_t s);
+// the read was not assembled (seq_len[r] = -1).  With qw (each base's uint16 weight) and qual, both or neither,
+// the columns' qualities Q in 0..40 go to qual, laid out like seq.  work holds assemble_work_bytes(C, total,
+// qual != nullptr) bytes
+size_t assemble_work_bytes(int C, long long total, bool qual = false);
+hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
+                                 const int* read_off, int R, int C, int total, unsigned char* seq,
+                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s);
+// the column quality's table, the doubles 10.0 ** (k / 10.0) for k < PHRED_LEVELS
+#define PHRED_LEVELS 41
+const double* phred_ratios();
+// token weights: w[i] = min(65535, floor(65535 exp((double)lp) + 0.5)) with lp = logp[i][tokens[i]] (logp
+// [n, V]) or tok_logp[i], exactly one of the two given; 0 for a token outside [0, V) or a non-finite lp
+hipError_t launch_token_weights(const int* tokens, const float* logp, const float* tok_logp, int n, int V,
+                                unsigned short* w, hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

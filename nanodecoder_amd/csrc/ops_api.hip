@@ -1,5 +1,6 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads): launches on the caller's stream, with no context.  The nd_op_* calls exist for the op-level tests.
+// nd_assemble_reads, nd_assemble_reads_q, nd_token_weights): launches on the caller's stream, with no context.
+// The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
 // an entry's status from its launcher's: "name: <the HIP error's text>" in nd_last_error
@@ -256,8 +257,52 @@ int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const 
     return fail(ND_ERR_ARG, "assemble_reads: null buffer");
   if (R == 0) return ND_OK;
   return status("assemble_reads",
-                nd::launch_assemble_reads(d_bases, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq, d_seq_len,
-                                          d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+                nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
+                                          nullptr, d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int64_t nd_assemble_reads_q_work_bytes(int32_t C, int64_t total_bases) {
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true) : -1;
+}
+
+int nd_assemble_reads_q(const uint8_t* d_bases, const uint16_t* d_qw, const int32_t* d_chunk_off,
+                        const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
+                        uint8_t* d_qual, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
+                        void* stream) {
+  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "assemble_reads_q: R, C and total_bases must be >= 0 and total_bases < 2^31");
+  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, true);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "assemble_reads_q: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_assemble_reads_q_work_bytes asks for");
+  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
+      (total_bases > 0 && (!d_bases || !d_qw || !d_seq || !d_qual)))
+    return fail(ND_ERR_ARG, "assemble_reads_q: null buffer");
+  if (R == 0) return ND_OK;
+  if (total_bases == 0)  // nothing to weigh: the plain call's paths (no chunks, or only empty ones)
+    return status("assemble_reads_q",
+                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
+                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+  return status("assemble_reads_q",
+                nd::launch_assemble_reads(d_bases, d_qw, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
+                                          d_qual, d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_token_weights(const int32_t* d_tokens, const float* d_logp, const float* d_tok_logp, int32_t B, int32_t S,
+                     int32_t V, uint16_t* d_w, void* stream) {
+  if (B < 0 || S < 0 || V < 1 || (int64_t)B * S >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "token_weights: B and S must be >= 0, V >= 1 and B * S < 2^31");
+  if ((d_logp != nullptr) == (d_tok_logp != nullptr))
+    return fail(ND_ERR_ARG, "token_weights: exactly one of d_logp and d_tok_logp must be given");
+  if ((int64_t)B * S > 0 && (!d_tokens || !d_w)) return fail(ND_ERR_ARG, "token_weights: null buffer");
+  return status("token_weights", nd::launch_token_weights(d_tokens, d_logp, d_tok_logp, B * S, V, d_w,
+                                                          (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_phred_ratios(double* out, int32_t n) {
+  if (!out || n < 0 || n > PHRED_LEVELS) return fail(ND_ERR_ARG, "phred_ratios: out null, or n outside [0, 41]");
+  for (int k = 0; k < n; ++k) out[k] = nd::phred_ratios()[k];
+  return ND_OK;
 }
 
 int nd_op_memory_pack(const float* x, const float* ln_g, const float* ln_b, float* out, int32_t B, int32_t T,

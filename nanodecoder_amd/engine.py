@@ -306,6 +306,27 @@ class Engine:
                    "nd_score_targets")
         return dict(scores=sc, tok_logp=tl, logp=lp, overflow=self._take_overflow())
 
+    def token_weights(self, tokens, logp=None, tok_logp=None):
+        """The uint16 weights of a call's tokens (nd_token_weights, on the current stream): w =
+        min(65535, floor(65535 exp(lp) + 0.5)) with lp = logp[..., token] (``logp`` [..., V], what a translate
+        call returns with return_logp) or tok_logp[...] (score_targets' return_tok_logp), exactly one of the
+        two; 0 for a token outside the vocabulary (the beam's -1 padding) or a non-finite lp.  Returns an
+        int16 device tensor shaped like ``tokens`` that holds the uint16 bits (view it as uint16 on the host)."""
+        if (logp is None) == (tok_logp is None):
+            raise ValueError("token_weights needs exactly one of logp and tok_logp")
+        V = self.cfg.vocab
+        tokens = torch.as_tensor(tokens).to(self.device, torch.int32, non_blocking=True).contiguous()
+        lp = torch.as_tensor(logp if tok_logp is None else tok_logp).to(self.device, torch.float32,
+                                                                         non_blocking=True).contiguous()
+        if tokens.dim() != 2 or tuple(lp.shape) != tuple(tokens.shape) + ((V,) if tok_logp is None else ()):
+            raise ValueError("tokens must be [B, S] and logp [B, S, V] (tok_logp [B, S])")
+        B, S = tokens.shape
+        w = torch.empty(B, S, dtype=torch.int16, device=self.device)
+        _lib.check(self._L.nd_token_weights(_ptr(tokens), _ptr(lp) if tok_logp is None else None,
+                                            None if tok_logp is None else _ptr(lp), B, S, V, _ptr(w),
+                                            self._stream()), "nd_token_weights")
+        return w
+
     def encode(self, signal, lengths, spans=None):
         """Memory bank [B, T, d] of the encoder (rows >= span unspecified)."""
         signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
@@ -432,6 +453,13 @@ class EnginePool:
         # the gold rows stay referenced like the other inputs (see _call)
         self._held[r["lane"]] = r["inputs"] = r["inputs"] + (kw.get("gold"), kw.get("gold_len"))
         return r
+
+    def token_weights(self, tokens, logp=None, tok_logp=None, lane: int = 0):
+        """Engine.token_weights on the stream of ``lane``: pass the ``lane`` of the result whose outputs
+        these are, so the weights follow that call in stream order and need no join."""
+        eng = self.engines[lane]
+        with torch.cuda.stream(eng.stream):
+            return eng.token_weights(tokens, logp=logp, tok_logp=tok_logp)
 
     def encode(self, signal, lengths, spans=None):
         """Engine.encode on the next lane's context, joined to the current

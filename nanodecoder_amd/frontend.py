@@ -202,12 +202,124 @@ def assemble_read(all_predictions, src_seq_length: int, src_seq_stride: int) -> 
     return simple_assembly(all_predictions, flag_intersection=False)
 
 
+# ---------------------------------------------------------------- per-base qualities (FASTQ)
+# The reference writes no qualities.  A token's weight is its model probability in 16 bits,
+# w = min(65535, floor(65535 * exp((double)lp) + 0.5)) (nd_token_weights; 0 for a non-finite lp or the beam's -1
+# padding); every char of a token's word carries the token's weight.  A column of a read's vote with n votes, of
+# which those for the winning class weigh S together, gets the largest Q in 0..40 with
+# float(65535 n - S) * PHRED_RATIO[Q] <= float(65535 n), and Q = 0 when n = 0: one fp64 product and one compare
+# per level, on exact integers, so the device (assembly.hip, nd_assemble_reads_q) gives the same bytes.
+PHRED_RATIO = (  # the doubles 10.0 ** (k / 10.0), k = 0..40, printed with 17 significant digits
+    1.0, 1.2589254117941673, 1.5848931924611136, 1.9952623149688795, 2.5118864315095801, 3.1622776601683795,
+    3.9810717055349722, 5.011872336272722, 6.3095734448019334, 7.9432823472428158, 10.0, 12.589254117941675,
+    15.848931924611133, 19.952623149688797, 25.118864315095795, 31.622776601683793, 39.810717055349734,
+    50.118723362727224, 63.095734448019329, 79.43282347242814, 100.0, 125.89254117941675, 158.48931924611142,
+    199.52623149688787, 251.18864315095797, 316.22776601683796, 398.10717055349733, 501.18723362727246,
+    630.957344480193, 794.32823472428129, 1000.0, 1258.9254117941675, 1584.893192461114, 1995.2623149688789,
+    2511.8864315095798, 3162.2776601683795, 3981.0717055349733, 5011.8723362727251, 6309.5734448019302,
+    7943.2823472428136, 10000.0)
+WEIGHT_ONE = 65535  # the weight of probability 1
+
+
+def token_weight(lp) -> int:
+    """The uint16 weight of a token of log-probability ``lp`` (float32)."""
+    lp = float(np.float32(lp))
+    if not math.isfinite(lp):
+        return 0
+    try:
+        return int(min(float(WEIGHT_ONE), math.floor(WEIGHT_ONE * math.exp(lp) + 0.5)))
+    except OverflowError:
+        return WEIGHT_ONE
+
+
+def column_quality(n, S):
+    """Q of columns with ``n`` votes whose winning class weighs ``S`` (ints or integer arrays): int or uint8
+    array."""
+    n64, s64 = np.asarray(n, np.int64), np.asarray(S, np.int64)
+    full = WEIGHT_ONE * n64
+    e, f = (full - s64).astype(np.float64), full.astype(np.float64)
+    ok = e[..., None] * np.asarray(PHRED_RATIO, np.float64) <= f[..., None]  # true up to Q: the ratios increase
+    q = np.where(n64 > 0, ok.sum(-1) - 1, 0).astype(np.uint8)
+    return int(q) if q.ndim == 0 else q
+
+
+def quality_string(q) -> str:
+    """FASTQ text of the qualities ``q``: chr(33 + Q) per base."""
+    return (np.asarray(q, np.uint8) + np.uint8(33)).tobytes().decode("ascii")
+
+
+def _valid_weights(bpreads, weights):
+    """The weights of simple_assembly's ``valid`` chunks, one int64 array per chunk."""
+    if len(weights) != len(bpreads):
+        raise ValueError("one weight array per chunk")
+    return [np.asarray(w, np.int64).reshape(-1) for x, w in zip(bpreads, weights) if x[0] != ""]
+
+
+def _add_count_q(consensus, wsum, start, segment, w):
+    """_add_count, each vote's weight added to ``wsum`` beside its count."""
+    if len(w) != len(segment):
+        raise ValueError("a chunk of %d bases with %d weights" % (len(segment), len(w)))
+    if start < 0:
+        segment, w = segment[-start:], w[-start:]
+        start = 0
+    for i, base in enumerate(segment):
+        k = BASE_DICT[base.upper()]
+        consensus[k][start + i] += 1
+        wsum[k][start + i] += w[i]
+
+
+def simple_assembly_q(bpreads, weights):
+    """simple_assembly with flag_intersection, line for line, with the weight sums [5, length] (int64) of the
+    votes beside the counts: (consensus, wsum)."""
+    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
+    vw = _valid_weights(bpreads, weights)
+    consensus = np.zeros([len(BASE_KEYS), 1000])
+    wsum = np.zeros([len(BASE_KEYS), 1000], np.int64)
+    pos = 0
+    length = 0
+    census_len = 1000
+    for indx, bpread in enumerate(valid):
+        if indx == 0:
+            _add_count_q(consensus, wsum, 0, bpread, vw[0])
+            continue
+        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
+        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
+        disp = match_block[0] - match_block[1]
+        if disp + pos + len(valid[indx]) > census_len:
+            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
+            wsum = np.pad(wsum, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
+            census_len += 1000
+        _add_count_q(consensus, wsum, pos + disp, valid[indx], vw[indx])
+        pos += disp
+        length = max(length, pos + len(valid[indx]))
+    return consensus[:, :length], wsum[:, :length]
+
+
+def assemble_read_q(all_predictions, weights, src_seq_length: int, src_seq_stride: int):
+    """assemble_read with per-base qualities: (sequence, quality string).  ``weights``: per chunk, the uint16
+    weight of every char of its x[0] with the spaces removed.  The sequence is assemble_read's, and what
+    assemble_read raises is raised here."""
+    if src_seq_stride < src_seq_length:
+        consensus, wsum = simple_assembly_q(all_predictions, weights)
+        win = np.argmax(consensus, axis=0)
+        n = consensus.sum(axis=0).astype(np.int64)
+        S = wsum[win, np.arange(win.size)] if win.size else np.zeros(0, np.int64)
+        return index2base(win), quality_string(column_quality(n, S))
+    # the concatenation branch: every base is its own column, n = 1 and S = its weight
+    seq = simple_assembly(all_predictions, flag_intersection=False)
+    vw = _valid_weights(all_predictions, weights)
+    w = np.concatenate(vw) if vw else np.zeros(0, np.int64)
+    if w.size != len(seq):
+        raise ValueError("a read of %d bases with %d weights" % (len(seq), w.size))
+    return seq, quality_string(column_quality(np.ones(w.size, np.int64), w))
+
+
 # ---------------------------------------------------------------- assembly on the device (-assembly gpu)
 ASM_STATUS_LONG = 1   # include/nanodec.h nd_assemble_reads: a chunk of 200 or more chars (difflib autojunk)
 ASM_STATUS_CHAR = 2   # a char whose upper case is not in BASE_KEYS
 
 
-def pack_assembly_input(reads):
+def pack_assembly_input(reads, weights=None):
     """The input of nd_assemble_reads for a group of reads (each the
     all_predictions assemble_read takes): every chunk's x[0] with the spaces
     removed, as ASCII bytes, concatenated.  Returns (bases uint8 [total],
@@ -216,8 +328,12 @@ def pack_assembly_input(reads):
     ``host`` lists the reads kept back for assemble_read: text that is not
     ASCII, and a hypothesis of nothing but spaces (simple_assembly drops ""
     before it removes the spaces, so that one stays in its chunk list as an
-    empty string).  Such a read is packed with no chunks."""
-    lens, parts, host = [], [], []
+    empty string).  Such a read is packed with no chunks.
+    With ``weights`` (per read, per chunk, the uint16 weight of every char of that string) a fifth value
+    follows: qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q)."""
+    lens, parts, host, wparts = [], [], [], []
+    if weights is not None and len(weights) != len(reads):
+        raise ValueError("one list of weights per read")
     read_off = np.zeros(len(reads) + 1, np.int64)
     for r, preds in enumerate(reads):
         strs = [x[0].replace(" ", "") for x in preds]
@@ -229,6 +345,14 @@ def pack_assembly_input(reads):
             host.append(r)
             read_off[r + 1] = read_off[r]
             continue
+        if weights is not None:
+            if len(weights[r]) != len(strs):
+                raise ValueError("one weight array per chunk")
+            for st, w in zip(strs, weights[r]):
+                w = np.asarray(w, np.uint16).reshape(-1)
+                if w.size != len(st):
+                    raise ValueError("a chunk of %d bases with %d weights" % (len(st), w.size))
+                wparts.append(w)
         parts.append(raw)
         lens.extend(len(s) for s in strs)
         read_off[r + 1] = read_off[r] + len(strs)
@@ -237,12 +361,16 @@ def pack_assembly_input(reads):
     if chunk_off[-1] >= 2 ** 31:
         raise ValueError("more than 2^31 - 1 bases in one assembly group")
     bases = np.frombuffer(bytearray(b"").join(parts), np.uint8)  # a bytearray: writable, as torch.from_numpy wants
-    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
+    if weights is None:
+        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
+    qw = np.concatenate(wparts) if wparts else np.zeros(0, np.uint16)
+    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw
 
 
-def _assemble_device(bases, chunk_off, read_off, device):
+def _assemble_device(bases, chunk_off, read_off, device, qw=None):
     """One nd_assemble_reads call on the CURRENT stream of ``device``:
-    (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host."""
+    (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host.  With ``qw`` (uint16 [total], each
+    base's weight) the call is nd_assemble_reads_q and qual uint8 [total] follows."""
     import ctypes
 
     import torch
@@ -251,7 +379,7 @@ def _assemble_device(bases, chunk_off, read_off, device):
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     R, C, total = len(read_off) - 1, len(chunk_off) - 1, int(bases.size)
     L = _lib.lib()
-    work_bytes = int(L.nd_assemble_reads_work_bytes(C, total))
+    work_bytes = int((L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes)(C, total))
     with torch.cuda.device(dev):
         off_d = _pinned(np.concatenate([chunk_off, read_off])).to(dev, non_blocking=True)
         bases_d = _pinned(bases).to(dev, non_blocking=True)
@@ -260,15 +388,27 @@ def _assemble_device(bases, chunk_off, read_off, device):
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        _lib.check(L.nd_assemble_reads(p(bases_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d), p(out_d[0]),
-                                       p(out_d[1]), p(work_d), work_bytes, stream), "nd_assemble_reads")
+        if qw is None:
+            _lib.check(L.nd_assemble_reads(p(bases_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
+                                           p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
+                       "nd_assemble_reads")
+        else:
+            if qw.dtype != np.uint16 or qw.size != total:
+                raise ValueError("qw must hold one uint16 per base")
+            qw_d = _pinned(qw.view(np.int16)).to(dev, non_blocking=True)  # the bits: torch has no uint16 copy
+            qual_d = torch.empty(total, dtype=torch.uint8, device=dev)
+            _lib.check(L.nd_assemble_reads_q(p(bases_d), p(qw_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
+                                             p(qual_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
+                       "nd_assemble_reads_q")
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         seq = seq_d.cpu().numpy()
+        if qw is not None:
+            return seq, out[0], out[1], qual_d.cpu().numpy()
     return seq, out[0], out[1]
 
 
 def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None, stats=None,
-                   defer_errors: bool = False):
+                   defer_errors: bool = False, weights=None):
     """assemble_read for a group of reads: one string per read.
 
     ``device=None``, or ``src_seq_stride >= src_seq_length`` (translate.py's
@@ -282,16 +422,33 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
     counted: ``stats`` (a dict) gets its "reads" and "fallback" entries
     increased by the reads of this call and by those assembled on the host.
     ``defer_errors``: a read whose host assembly raises yields None instead
-    (the caller assembles it again where it handles that read's errors)."""
+    (the caller assembles it again where it handles that read's errors).
+    ``weights`` (per read, per chunk, the uint16 weight of every char of the chunk's string; see
+    assemble_read_q): every read yields (sequence, quality string) instead, the device call is
+    nd_assemble_reads_q, and the host path and the fallback are assemble_read_q."""
     reads = list(reads)
+    if weights is None:
+        one = lambda r: assemble_read(reads[r], src_seq_length, src_seq_stride)  # noqa: E731
+    else:
+        weights = list(weights)
+        if len(weights) != len(reads):
+            raise ValueError("one list of weights per read")
+        one = lambda r: assemble_read_q(reads[r], weights[r], src_seq_length, src_seq_stride)  # noqa: E731
     if device is None or src_seq_stride >= src_seq_length:
-        return [assemble_read(p, src_seq_length, src_seq_stride) for p in reads]
-    bases, chunk_off, read_off, host = pack_assembly_input(reads)
+        return [one(r) for r in range(len(reads))]
     R = len(reads)
-    out = [""] * R  # no bases at all: every device read is ""
+    if weights is None:
+        bases, chunk_off, read_off, host = pack_assembly_input(reads)
+        out = [""] * R  # no bases at all: every device read is ""
+    else:
+        bases, chunk_off, read_off, host, qw = pack_assembly_input(reads, weights)
+        out = [("", "")] * R
     todo = set(host)
     if bases.size:
-        seq, seq_len, status = _assemble_device(bases, chunk_off, read_off, device)
+        if weights is None:
+            seq, seq_len, status = _assemble_device(bases, chunk_off, read_off, device)
+        else:
+            seq, seq_len, status, qual = _assemble_device(bases, chunk_off, read_off, device, qw)
         raw = seq.tobytes()
         start = chunk_off[read_off[:-1]]
         for r in range(R):
@@ -299,12 +456,14 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
                 todo.add(r)
             elif seq_len[r] > 0:
                 out[r] = raw[start[r]: start[r] + seq_len[r]].decode("ascii")
+                if weights is not None:
+                    out[r] = (out[r], quality_string(qual[start[r]: start[r] + seq_len[r]]))
     if stats is not None:
         stats["reads"] = stats.get("reads", 0) + R
         stats["fallback"] = stats.get("fallback", 0) + len(todo)
     for r in sorted(todo):
         try:
-            out[r] = assemble_read(reads[r], src_seq_length, src_seq_stride)
+            out[r] = one(r)
         except Exception:
             if not defer_errors:
                 raise

@@ -77,6 +77,10 @@ def translate_parser() -> argparse.ArgumentParser:
          help="gpu: assemble each group's overlapping chunks into reads on the GPU (assembly.hip; the same "
               "bytes; a read it does not cover is assembled on the host and counted in the log) instead of "
               "read by read in Python")
+    _add(g, "fastq", action="store_true",
+         help="also write result/<read>.fastq: per-base qualities 0..40 from the model's own probability of "
+              "each called base, carried through the assembly vote (not recalibrated against error rates); "
+              "the .fasta, segment and speed.txt outputs are unchanged; not together with -attn_debug")
     return p
 
 

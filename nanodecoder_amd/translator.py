@@ -140,7 +140,10 @@ class Translator(object):
         self._pinned, self._pin_i = None, 0
         self.last_gold_scores = None  # per-chunk gold scores of the last translate(src, tgt=...)
 
-    def _check_supported(self):
+    def _check_supported(self, qualities: bool = False):
+        if qualities and self.beam_size > 1 and self.cfg.self_attn_type == "average":
+            # the beam's qualities come from the scoring pass, which refuses such decoders
+            raise NotImplementedError("qualities with beam search are not supported for average-attention decoders")
         if self.beam_size == 1:
             # translator.py:371-394: keep_topk == 1 (or temp == 0) is argmax, anything else samples
             if self.sample_from_topk > self.cfg.vocab:
@@ -204,11 +207,12 @@ class Translator(object):
         return max(1, int(getattr(self.engine, "lanes", 1)))
 
     def _submit(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
-                attn: bool = False):
+                attn: bool = False, qual: bool = False):
         """Stage up to max_batch chunks with their reference spans (and, for
         the classic Beam, their reference batch ids) and enqueue the engine
         call.  Greedy and sampling calls return before the device finishes;
-        ``_finish`` collects the results."""
+        ``_finish`` collects the results.  ``qual``: the token weights of each
+        chunk's best hypothesis are wanted too (see stream_reads)."""
         n = len(chunks)
         lens = np.array([len(c) for c in chunks], np.int32)
         if (lens < 1).any():
@@ -224,15 +228,20 @@ class Translator(object):
         L[:n], S[:n] = lens, spans
         if dev_in is not None:
             sig, L, S = dev_in
-        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in)
-        job["again"] = lambda: self._submit(chunks, spans, groups, attn)
+        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual)
+        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual)
         return job
 
-    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs):
+    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs, qual: bool = False):
         """The engine call for one staged batch (signal [B, T], chunk lengths
         and spans [B]; the first n rows are chunks), its results copied to
-        pinned host buffers on the call's own stream."""
-        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs)
+        pinned host buffers on the call's own stream.  ``qual``: a greedy or
+        sampling call also returns its log-probs and the chosen tokens'
+        weights (nd_token_weights) follow it on its stream; a beam call's
+        inputs are kept for the scoring pass of ``_beam_weights``."""
+        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual)
+        # without qualities the engine sees exactly the arguments it always has
+        want = dict(return_logp=True) if qual else {}
         if self.beam_size == 1:
             if not (self.random_sampling_temp == 0.0 or self.sample_from_topk == 1):
                 # sample_with_temperature's random branch (translator.py:376-393)
@@ -240,10 +249,13 @@ class Translator(object):
                 seed = (self._seed * 0x9E3779B97F4A7C15 + self._draws) & (2 ** 64 - 1)
                 r = self.engine.translate_sample(sig, L, S, temp=self.random_sampling_temp,
                                                  keep_topk=self.sample_from_topk, seed=seed, max_len=self.max_length,
-                                                 min_len=self.min_length, return_attn=attn)
+                                                 min_len=self.min_length, return_attn=attn, **want)
             else:
                 r = self.engine.translate_greedy(sig, L, S, max_len=self.max_length, min_len=self.min_length,
-                                                 return_attn=attn)
+                                                 return_attn=attn, **want)
+            if qual:
+                r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"],
+                                                         **({"lane": r["lane"]} if "lane" in r else {}))
             job.update(kind="greedy", r=r)
         else:
             # reference batches: the chunks of one group, sorted by length
@@ -279,11 +291,13 @@ class Translator(object):
                     coverage_penalty=gs.coverage_penalty, beta=gs.beta, stepwise_penalty=self.stepwise_penalty,
                     block_ngram_repeat=self.block_ngram_repeat, ignore_ids=exclusion, cut=cut, return_attn=attn)
             job.update(kind="beam", r=r, grp=grp, sorted_rows=sorted_rows, cut=cut)
+            if qual:
+                job["eng_in"] = (sig, L, S)
         if self._real_engine():
             self._copy_out(job)
         return job
 
-    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow")
+    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow", "weights")
 
     def _copy_out(self, job):
         """Enqueue the call's device-to-host copies (into pinned buffers) on
@@ -336,11 +350,16 @@ class Translator(object):
         the attention rows of each hypothesis ([steps, cut] arrays, cut as the
         reference's results["attention"] has it)."""
         n, lens, attn = job["n"], job["lens"], job["attn"]
+        qual = job.get("qual", False)
         out = []
         if job["kind"] == "greedy":
             tok, sc, at, ov = self._host(job, "tokens", "scores", "attn", "overflow")
             if self._overflowed(job, ov):
                 return self._rerun_exact(job)
+            if qual:
+                w = self._host(job, "weights")[0].view(np.uint16)
+                return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]))
+                        for i in range(n)]
             for i in range(n):
                 if attn:  # results["attention"]: rows cut at the chunk's length (translator.py:491-501)
                     out.append(([float(sc[i])], [tok[i].tolist()], [at[i, :, : lens[i]]]))
@@ -351,9 +370,12 @@ class Translator(object):
         tok, sc, ln, at, done, ov = self._host(job, "tokens", "scores", "lens", "attn", "done_step", "overflow")
         if self._overflowed(job, ov):
             return self._rerun_exact(job)
+        w = self._beam_weights(job, tok, ln) if qual else None
         for i in range(n):
             o = ([float(sc[i, k]) for k in range(self.n_best)],
                  [tok[i, k, : ln[i, k]].tolist() for k in range(self.n_best)])
+            if qual:
+                o = o + (self._char_weights(o[1][0], w[i]),)
             if attn:
                 atts = []
                 for k in range(self.n_best):
@@ -369,6 +391,52 @@ class Translator(object):
                 o = o + (atts,)
             out.append(o)
         return out
+
+    def _beam_weights(self, job, tok, ln):
+        """The token weights [B, L] (uint16) of a finished beam call's best hypotheses: the existing
+        teacher-forced scoring pass (score_targets) over the call's own inputs, each gold row the hypothesis'
+        tokens as returned (EOS included when it finished) and gold_len its length, then nd_token_weights of
+        the pass's per-token log-probs.  The encoder runs a second time for this."""
+        sig, ln_in, sp = job["eng_in"]
+        B = job["B"]
+        n_tok = np.clip(ln[:B, 0].astype(np.int32), 1, min(tok.shape[2], self.engine.max_steps))
+        L = min(self.engine.max_steps, (int(n_tok.max()) + 7) // 8 * 8)  # one captured graph per (B, T, L)
+        gold = np.full((B, L), self.cfg.pad_idx, np.int32)
+        for i in range(B):
+            gold[i, : n_tok[i]] = tok[i, 0, : n_tok[i]]
+        gold[gold < 0] = self.cfg.eos_idx  # a row without a hypothesis (engine padding) scores a lone EOS
+        gold_t, len_t = torch.from_numpy(gold), torch.from_numpy(n_tok)
+
+        def score():
+            r = self.engine.score_targets(sig, ln_in, sp, gold=gold_t, gold_len=len_t, return_tok_logp=True)
+            if "event" in r:
+                r["event"].synchronize()
+            ov = r.get("overflow")
+            return r, ov is not None and int(ov.cpu().reshape(-1)[0]) != 0
+        r, over = score()
+        if over and not job.get("exact"):
+            # split-fp16 range guard: the pass again with every product in exact fp32 (see _rerun_exact)
+            self.engine.set_exact_fp32(True)
+            try:
+                r, _ = score()
+            finally:
+                self.engine.set_exact_fp32(False)
+        w = self.engine.token_weights(gold_t, tok_logp=r["tok_logp"], **({"lane": r["lane"]} if "lane" in r else {}))
+        if "lane" in r:
+            self.engine.engines[r["lane"]].stream.synchronize()
+        return w.cpu().numpy().view(np.uint16)
+
+    def _char_weights(self, toks, w) -> np.ndarray:
+        """The weight of every character of a hypothesis' string with the spaces removed (uint16): the
+        tokens up to the first EOS as _tokens_to_sent cuts them, each character of a token's word carrying
+        the token's weight."""
+        out = []
+        for t, wt in zip(toks, w):
+            word = self.cfg.itos[t]
+            if t == self.cfg.eos_idx:
+                break
+            out.extend([int(wt)] * len(word.replace(" ", "")))
+        return np.asarray(out, np.uint16)
 
     def _run(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
              attn: bool = False):
@@ -507,7 +575,15 @@ class Translator(object):
             output += row_format.format(*row) + "\n"
         self.out_file_attn.write(output)
 
-    def stream_reads(self, reads: Iterable[Sequence], batch_size: int, attn_debug: bool = False):
+    def _want_qualities(self, qualities: bool, attn_debug: bool = False) -> bool:
+        if qualities:
+            if attn_debug:
+                raise ValueError("qualities are not available together with attn_debug")
+            self._check_supported(qualities=True)
+        return bool(qualities)
+
+    def stream_reads(self, reads: Iterable[Sequence], batch_size: int, attn_debug: bool = False,
+                     qualities: bool = False):
         """Generator over many reads (any iterable of chunk lists): chunks are
         packed across reads into engine batches of max_batch, one batch (one
         per EnginePool lane) stays in flight on the device while the next is
@@ -515,8 +591,14 @@ class Translator(object):
         (read index, per-chunk results) is yielded as each read completes.
         Each chunk keeps the span of the reference batch it would belong to
         (consecutive ``batch_size`` chunks of its own read), so results equal
-        per-read translate()."""
+        per-read translate().  ``qualities``: each chunk's result also carries,
+        as its third entry, the uint16 weights of its best hypothesis, one per
+        character of its string with the spaces removed (frontend.assemble_read_q
+        turns them into a read's quality string).  Greedy and sampling take them
+        from the call's own log-probs; beam search scores the best hypothesis in
+        a second, teacher-forced pass (_beam_weights)."""
         import collections
+        qualities = self._want_qualities(qualities, attn_debug)
         cap = self.engine.max_batch
         depth = self._depth()
         pending, inflight = [], collections.deque()
@@ -535,7 +617,7 @@ class Translator(object):
 
         def submit(items):
             return self._submit([g[2] for g in items], [g[3] for g in items], [g[4] for g in items],
-                                attn=attn_debug), items
+                                attn=attn_debug, qual=qualities), items
 
         for ri, read in enumerate(reads):
             chunks = [parse_chunk(c) for c in read]
@@ -562,25 +644,29 @@ class Translator(object):
             for r in collect(inflight.popleft()):
                 yield r, results.pop(r)
 
-    def translate_reads(self, reads: Sequence[Sequence], batch_size: int, attn_debug: bool = False):
+    def translate_reads(self, reads: Sequence[Sequence], batch_size: int, attn_debug: bool = False,
+                        qualities: bool = False):
         """Translate many reads (stream_reads); returns per read
-        (all_scores, all_predictions) as translate() does."""
+        (all_scores, all_predictions) as translate() does; with ``qualities``
+        (all_scores, all_predictions, all_weights), all_weights per chunk the
+        uint16 weights of its best hypothesis (see stream_reads)."""
         results = [None] * len(reads)
-        for ri, res in self.stream_reads(reads, batch_size, attn_debug):
+        for ri, res in self.stream_reads(reads, batch_size, attn_debug, **({"qualities": True} if qualities else {})):
             results[ri] = res
-        return self._report(results, attn_debug)
+        return self._report(results, attn_debug, qualities=qualities)
 
     def translate_raw_reads(self, raws: Sequence[np.ndarray], batch_size: int, normalization: str = "median",
-                            src_seq_length: int = 512, src_seq_stride: int = 512):
+                            src_seq_length: int = 512, src_seq_stride: int = 512, qualities: bool = False):
         """translate_reads on raw reads with the signal front end on the
         device (stream_raw_reads); returns per read (all_scores,
-        all_predictions)."""
+        all_predictions), with ``qualities`` also all_weights."""
         results = [None] * len(raws)
-        for ri, res in self.stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride):
+        for ri, res in self.stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
+                                             **({"qualities": True} if qualities else {})):
             results[ri] = res
-        return self._report(results, False)
+        return self._report(results, False, qualities=qualities)
 
-    def _report(self, results, attn_debug: bool, gold=None):
+    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False):
         """Per read (all_scores, all_predictions) from per-chunk results, with
         the reference's verbose / -dump_beam / report_score side outputs
         (translate/translator.py:255-369).  gold (translate with tgt): per chunk
@@ -589,7 +675,7 @@ class Translator(object):
         counter = 0
         pred_score_total, pred_words_total = 0.0, 0
         for r in results:
-            all_scores, all_predictions = [], []
+            all_scores, all_predictions, all_weights = [], [], []
             for res in r:
                 scores, toks = res[0], res[1]
                 sents = [self._tokens_to_sent(t) for t in toks]
@@ -597,6 +683,8 @@ class Translator(object):
                     self._write_attn(res[3], sents[0], res[2][0])
                 all_scores.append(scores[: self.n_best])
                 all_predictions.append([" ".join(s) for s in sents[: self.n_best]])
+                if qualities:
+                    all_weights.append(res[2])
                 pred_score_total += scores[0]
                 pred_words_total += len(sents[0])
                 if self.verbose:
@@ -614,7 +702,7 @@ class Translator(object):
                         self.logger.info(msg)
                     else:
                         os.write(1, msg.encode("utf-8"))
-            ret.append((all_scores, all_predictions))
+            ret.append((all_scores, all_predictions, all_weights) if qualities else (all_scores, all_predictions))
         if self.dump_beam:
             # translator.py:365-368 dumps the beam trace accumulator.  (The
             # reference reads it through a `self.translator` attribute the
@@ -636,7 +724,7 @@ class Translator(object):
             return self.engine.engines[self.engine._next].stream
         return torch.cuda.current_stream(self.engine.device)
 
-    def _submit_raw(self, items, batch_reads, normalization: str):
+    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False):
         """One engine batch from raw reads: chunk descriptors ``items`` =
         (read, chunk, start, length, span, reference batch) and the reads
         they cut (``batch_reads``: read -> float64 samples).  The front end
@@ -662,12 +750,13 @@ class Translator(object):
                                               normalization, B, T, self.engine.device)
             ls_d = torch.from_numpy(ls).pin_memory().to(self.engine.device, non_blocking=True)
             job = self._enqueue(sig, ls_d[:B], ls_d[B:], B, n, lens, [it[5] for it in items], False,
-                                (sig, ls_d, keep))
-        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization)
+                                (sig, ls_d, keep), qual)
+        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual)
         return job
 
     def stream_raw_reads(self, raws: Iterable, batch_size: int, normalization: str = "median",
-                         src_seq_length: int = 512, src_seq_stride: int = 512, arrays: bool = False):
+                         src_seq_length: int = 512, src_seq_stride: int = 512, arrays: bool = False,
+                         qualities: bool = False):
         """stream_reads on RAW reads (float64 sample arrays, as
         frontend.read_raw returns them) with extract_fast5_raw's
         normalisation and windowing (utils/labelop.py:194-243) on the device:
@@ -678,12 +767,16 @@ class Translator(object):
         results equal per-read translate() on the host front end's chunks.
         Yields (read index, per-chunk results) as stream_reads does; with
         ``arrays`` (greedy and sampling only) (read index, tokens [n_chunks,
-        max_length] int32, scores [n_chunks] float32) instead."""
+        max_length] int32, scores [n_chunks] float32) instead.  ``qualities``
+        as in stream_reads; with ``arrays`` a fourth array follows, the
+        tokens' weights [n_chunks, max_length] uint16 (one per token, EOS and
+        what follows it included)."""
         import collections
 
         from . import frontend
         if arrays and self.beam_size != 1:
             raise ValueError("arrays=True is for greedy / sampling decoding")
+        qualities = self._want_qualities(qualities)
         cap = self.engine.max_batch
         depth = self._depth()
         pending, batch_reads, inflight = [], {}, collections.deque()
@@ -693,15 +786,15 @@ class Translator(object):
         def collect(jb):
             job, items = jb
             if arrays:
-                tok, sc = self._finish_arrays(job)
-                outs = ((tok[i], sc[i]) for i in range(len(items)))
+                cols = self._finish_arrays(job)
+                outs = (tuple(a[i] for a in cols) for i in range(len(items)))
             else:
                 outs = self._finish(job)
             done = []
             for (ri, ci, _, _, _, _), o in zip(items, outs):
                 if arrays:
-                    results[ri][0][ci] = o[0]
-                    results[ri][1][ci] = o[1]
+                    for dst, v in zip(results[ri], o):
+                        dst[ci] = v
                 else:
                     results[ri][ci] = o
                 remaining[ri] -= 1
@@ -711,17 +804,20 @@ class Translator(object):
 
         def flush():
             nonlocal pending, batch_reads
-            inflight.append((self._submit_raw(pending, batch_reads, normalization), pending))
+            inflight.append((self._submit_raw(pending, batch_reads, normalization, qualities), pending))
             pending, batch_reads = [], {}
 
         for ri, raw in enumerate(raws):
             raw = np.asarray(raw, dtype=np.float64).reshape(-1)
             if raw.size == 0:
-                yield (ri, np.zeros((0, self.max_length), np.int32), np.zeros(0, np.float32)) if arrays else (ri, [])
+                empty = (np.zeros((0, self.max_length), np.int32), np.zeros(0, np.float32)) + \
+                    ((np.zeros((0, self.max_length), np.uint16),) if qualities else ())
+                yield (ri,) + empty if arrays else (ri, [])
                 continue
             wins = frontend.windows(int(raw.size), src_seq_length, src_seq_stride)
             if arrays:
-                results[ri] = (np.empty((len(wins), self.max_length), np.int32), np.empty(len(wins), np.float32))
+                results[ri] = (np.empty((len(wins), self.max_length), np.int32), np.empty(len(wins), np.float32)) + \
+                    ((np.empty((len(wins), self.max_length), np.uint16),) if qualities else ())
             else:
                 results[ri] = [None] * len(wins)
             remaining[ri] = len(wins)
@@ -744,10 +840,13 @@ class Translator(object):
                 yield (r,) + results.pop(r) if arrays else (r, results.pop(r))
 
     def _finish_arrays(self, job):
-        """(tokens [n, S], scores [n]) numpy of a greedy / sampling call."""
+        """(tokens [n, S], scores [n]) numpy of a greedy / sampling call; its tokens' weights [n, S] uint16
+        follow when the call was submitted with qualities."""
         tok, sc, ov = self._host(job, "tokens", "scores", "overflow")
         if self._overflowed(job, ov):
             return self._rerun_exact(job, self._finish_arrays)
+        if job.get("qual"):
+            return tok[: job["n"]], sc[: job["n"]], self._host(job, "weights")[0].view(np.uint16)[: job["n"]]
         return tok[: job["n"]], sc[: job["n"]]
 
     def translate_batch(self, batch, data=None, attn_debug=False, fast=False):
