@@ -304,6 +304,51 @@ int nd_assemble_reads_q(const uint8_t* d_bases, const uint16_t* d_qw, const int3
                         uint8_t* d_qual, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
                         void* stream);
 
+/* Per-base methylation probabilities (CpG models: a vocabulary with the tokens
+ * "C" and "M", M a methylated C).  The reference writes the hard letter M
+ * only; these three entry points carry P(methylated | the base is a C) from
+ * the calls' log-probs through the assembly vote, beside the quality.  No
+ * context needed.
+ *
+ * Token modification weight of token t with that step's log-probs lp (fp32),
+ * canon_id the id of "C" and mod_id the id of "M":
+ *   t not in {canon_id, mod_id} (the beam's -1 padding included): mw = 0;
+ *   else d = (double)lp[canon_id] - (double)lp[mod_id], p = 1 / (1 + exp(d)),
+ *   mw = min(65535, floor(65535 * p + 0.5)), a uint16, every operation in
+ *   double and rounded once (no FMA); d = +inf gives 0, d = -inf 65535; a NaN
+ *   d falls back to the hard call: 65535 when t == mod_id, else 0.
+ * nd_token_mod_weights writes d_mw [B, S] from d_tokens [B, S] and d_logp
+ * [B, S, V] in one launch on `stream`, with no allocation and no
+ * synchronisation.  Negative sizes, V < 1, B * S >= 2^31, an id outside
+ * [0, V), canon_id == mod_id or a null buffer return ND_ERR_ARG before any
+ * HIP call.
+ *
+ * Column value of one column of a read's vote: n_cm = its votes of class C
+ * plus those of class M, W = the sum of mw over exactly those votes (a 64-bit
+ * unsigned integer, so the bytes do not depend on the order the votes arrive
+ * in).  A column whose call (exactly as nd_assemble_reads makes it) is C or M
+ * is a site: ML = min(255, (256 * W) div (65535 * n_cm)), integer division
+ * (n_cm >= 1 there), SAM's ML scale.  Every other column gets 0.  The call
+ * itself is never changed: a column called C may carry ML >= 128 (a 1:1 tie
+ * of a C vote and a confident M vote goes to the lower class, C).
+ *
+ * nd_assemble_reads_m is nd_assemble_reads_q with
+ *   d_mw [total_bases] u16 (in):  the modification weight of each byte of
+ *        d_bases (every char of a token's word carries the token's)
+ *   d_ml [total_bases] u8  (out): ML of the columns of the assembled reads,
+ *        laid out like d_seq; 0 off-site and past a read's length
+ * d_seq, d_qual, d_seq_len and d_status are those of nd_assemble_reads_q on
+ * the same input.  d_work holds nd_assemble_reads_m_work_bytes(C, total_bases)
+ * bytes (nd_assemble_reads_q's plus total_bases * 8); argument checks and the
+ * R == 0 and C == 0 paths as nd_assemble_reads. */
+int nd_token_mod_weights(const int32_t* d_tokens, const float* d_logp, int32_t B, int32_t S, int32_t V,
+                         int32_t canon_id, int32_t mod_id, uint16_t* d_mw, void* stream);
+int64_t nd_assemble_reads_m_work_bytes(int32_t C, int64_t total_bases);
+int nd_assemble_reads_m(const uint8_t* d_bases, const uint16_t* d_qw, const uint16_t* d_mw,
+                        const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R, int32_t C,
+                        int64_t total_bases, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_ml, int32_t* d_seq_len,
+                        int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

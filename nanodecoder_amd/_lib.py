@@ -64,6 +64,10 @@ SIGNATURES = {
     "nd_phred_ratios": (_I, [ctypes.POINTER(ctypes.c_double), _I]),
     "nd_assemble_reads_q_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
     "nd_assemble_reads_q": (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "nd_token_mod_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P]),
+    "nd_assemble_reads_m_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
+    "nd_assemble_reads_m": (_I, [_P, _P, _P, _P, _P, _I, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P, ctypes.c_int64,
+                                 _P]),
     "nd_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "nd_set_graphs": (_I, [_P, _I]),
     "nd_set_timing": (_I, [_P, _I]),

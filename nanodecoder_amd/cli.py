@@ -6,7 +6,8 @@ and windowed in a worker pool (translate.py:131-163), translated, and written
 as result/<read>.fasta, segment/<read>.txt and a line of speed.txt
 (translate.py:81-98).  One bad read prints ``!!!error!!!`` and the run goes
 on (translate.py:97-98).  ``-pack_reads N`` translates N reads per engine pass.
-``-fastq`` also writes result/<read>.fastq with per-base qualities.
+``-fastq`` also writes result/<read>.fastq with per-base qualities;
+``-mod_probs`` (CpG models) result/<read>.mod.fastq with MM / ML tags.
 """
 from __future__ import annotations
 
@@ -111,14 +112,26 @@ def _extract(args):
         return ["!" + prefix, repr(e)]
 
 
-def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None):
+def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None, mods=None):
     """translate.py:81-98.  ``sequence``: the read already assembled
     (-assembly gpu); None assembles it here.  ``weights`` (-fastq): the
     chunks' per-base weights; ``sequence`` is then (sequence, quality string),
-    and result/<read>.fastq is written before the .fasta resume keys on."""
+    and result/<read>.fastq is written before the .fasta resume keys on.
+    ``mods`` (-mod_probs, beside ``weights``): the chunks' per-base
+    modification weights; ``sequence`` is then (sequence, quality string, ml),
+    result/<read>.mod.fastq is written before the .fasta too, and the .fastq
+    only with -fastq."""
     try:
         name = file_src.split(".txt")[0]
-        if weights is not None:
+        if mods is not None:
+            c_bpread, quality, ml = sequence if sequence is not None else \
+                frontend.assemble_read_m(all_predictions, weights, mods, opt.src_seq_length, opt.src_seq_stride)
+            with open(os.path.join(opt.save_data, "result", name + ".mod.fastq"), "w") as f:
+                f.write(frontend.mod_fastq_record(name, c_bpread, quality, ml))
+            if getattr(opt, "fastq", False):
+                with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
+                    f.write("@%s\n%s\n+\n%s\n" % (name, c_bpread, quality))
+        elif weights is not None:
             c_bpread, quality = sequence if sequence is not None else \
                 frontend.assemble_read_q(all_predictions, weights, opt.src_seq_length, opt.src_seq_stride)
             with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
@@ -145,12 +158,16 @@ def main(opt=None):
     opt = opt or parse_translate_opts()
     if getattr(opt, "fastq", False) and opt.attn_debug:
         raise ValueError("-fastq is not available together with -attn_debug")
+    if getattr(opt, "mod_probs", False) and opt.attn_debug:
+        raise ValueError("-mod_probs is not available together with -attn_debug")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
         os.makedirs(os.path.join(opt.save_data, sub), exist_ok=True)
     from .translator import build_translator
     translator = build_translator(opt, report_score=False, logger=logger)
+    if getattr(opt, "mod_probs", False):
+        translator._check_supported(mods=True)  # ValueError for a vocabulary without C or M, before any read
     todo, done = list_reads(opt)
     logger.info("%d reads have already translated, remains %d read\n" % (done, len(todo)))
     jobs = [(p, pre, suf, opt.normalization_raw, opt.src_seq_length, opt.src_seq_stride) for p, pre, suf in todo]
@@ -196,8 +213,11 @@ def _translate_attn(opt, translator, group):
 
 def _translate_group(opt, translator, group, raw=False):
     t0 = time.time()
-    fastq = bool(getattr(opt, "fastq", False))
+    mod_probs = bool(getattr(opt, "mod_probs", False))
+    fastq = bool(getattr(opt, "fastq", False)) or mod_probs  # the methylation values travel beside the qualities
     want = dict(qualities=True) if fastq else {}
+    if mod_probs:
+        want["mods"] = True
     try:
         if opt.attn_debug:
             outs = _translate_attn(opt, translator, group)
@@ -216,19 +236,22 @@ def _translate_group(opt, translator, group, raw=False):
     total = max(1, sum(len(o[1]) for o in outs))
     seqs = [None] * len(outs)
     weights = [o[2] for o in outs] if fastq else [None] * len(outs)  # -fastq: per chunk, its bases' weights
+    mods = [o[3] for o in outs] if mod_probs else [None] * len(outs)  # -mod_probs: their modification weights
     if getattr(opt, "assembly", "cpu") == "gpu":
         # the whole group in one device call; a read left None (its host fallback raised) is assembled
         # again by write_output, which reports that read's error as -assembly cpu does
         try:
             seqs = frontend.assemble_reads([o[1] for o in outs], opt.src_seq_length, opt.src_seq_stride,
                                            device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True,
-                                           **(dict(weights=weights) if fastq else {}))
+                                           **(dict(weights=weights) if fastq else {}),
+                                           **(dict(mod_weights=mods) if mod_probs else {}))
         except Exception as e:
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    for g, o, seq, w in zip(group, outs, seqs, weights):
-        write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w)
+    for g, o, seq, w, mw in zip(group, outs, seqs, weights, mods):
+        write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
+                     **(dict(mods=mw) if mod_probs else {}))
     return len(group)
 
 

@@ -36,6 +36,11 @@
 // arrival order), and the call kernel turns a column's n votes and the winning
 // class's weight sum S into Q, the largest k in 0..40 with
 // (double)(65535 n - S) * PHRED_RATIO[k] <= (double)(65535 n); 0 when n = 0.
+//
+// With per-base modification weights too (nd_assemble_reads_m, CpG models whose ninth token M is a methylated
+// C) the vote kernel also adds the uint16 mw of every vote of class C or M into msum[total_bases] (one more
+// 64-bit plane), and the call kernel gives a column called C or M the byte
+// ML = min(255, (256 W) div (65535 n_cm)), W its msum and n_cm its C plus M votes; 0 for every other column.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -180,13 +185,14 @@ asm_place_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read
 }
 
 // one wave per chunk: its chars vote at pos[c] + x of the read's columns; QUAL: each vote's weight qw[.] is
-// added to wsum of its class and column
-template <bool QUAL>
+// added to wsum of its class and column; MOD: a C or M vote's modification weight mw[.] to msum of its column
+template <bool QUAL, bool MOD = false>
 __global__ void __launch_bounds__(ASM_THREADS)
 asm_vote_kernel(const unsigned char* __restrict__ bases, const unsigned short* __restrict__ qw,
-                const int* __restrict__ chunk_off, const int* __restrict__ read_off, const int* __restrict__ pos,
-                const int* __restrict__ rd, const int* __restrict__ status, int C, int total,
-                int* __restrict__ count, unsigned long long* __restrict__ wsum) {
+                const unsigned short* __restrict__ mw, const int* __restrict__ chunk_off,
+                const int* __restrict__ read_off, const int* __restrict__ pos, const int* __restrict__ rd,
+                const int* __restrict__ status, int C, int total, int* __restrict__ count,
+                unsigned long long* __restrict__ wsum, unsigned long long* __restrict__ msum) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -198,18 +204,21 @@ asm_vote_kernel(const unsigned char* __restrict__ bases, const unsigned short* _
     if (col >= 0 && col < cols && r0 + col < total && cls >= 0) {
       atomicAdd(&count[(size_t)cls * total + r0 + col], 1);
       if (QUAL) atomicAdd(&wsum[(size_t)cls * total + r0 + col], (unsigned long long)qw[o + x]);
+      if (MOD && (cls == 1 || cls == 4)) atomicAdd(&msum[r0 + col], (unsigned long long)mw[o + x]);
     }
   }
 }
 
 // one wave per chunk's span of the output: column g - r0 of read rd[c], 0 past the read's length; QUAL: the
-// column's Q from its votes and the winning class's weight sum
-template <bool QUAL>
+// column's Q from its votes and the winning class's weight sum; MOD: ML of a column called C or M from its C
+// and M votes and their modification weight sum
+template <bool QUAL, bool MOD = false>
 __global__ void __launch_bounds__(ASM_THREADS)
 asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_off, const int* __restrict__ rd,
                 const int* __restrict__ seq_len, const int* __restrict__ count,
-                const unsigned long long* __restrict__ wsum, int C, int total, unsigned char* __restrict__ seq,
-                unsigned char* __restrict__ qual) {
+                const unsigned long long* __restrict__ wsum, const unsigned long long* __restrict__ msum, int C,
+                int total, unsigned char* __restrict__ seq, unsigned char* __restrict__ qual,
+                unsigned char* __restrict__ ml) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -218,7 +227,7 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
   for (int x = lane; x < len; x += 64) {
     const int g = o + x;
     if (g >= total) break;
-    unsigned char out = 0, q = 0;
+    unsigned char out = 0, q = 0, mod = 0;
     if (g - r0 < n) {
       int best = count[g], cls = 0;
       long long votes = best;
@@ -236,52 +245,72 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
         const double e = (double)(full - wsum[(size_t)cls * total + g]), f = (double)full;  // both exact
         for (int k = 1; k < PHRED_LEVELS && e * d_phred_ratio[k] <= f; ++k) q = (unsigned char)k;
       }
+      if (MOD && (cls == 1 || cls == 4)) {
+        const unsigned long long n_cm =
+            (unsigned long long)count[(size_t)total + g] + (unsigned long long)count[(size_t)4 * total + g];
+        if (n_cm > 0) {  // W <= 65535 n_cm < 2^47: 256 W fits
+          const unsigned long long v = (256ull * msum[g]) / (65535ull * n_cm);
+          mod = (unsigned char)(v < 255ull ? v : 255ull);
+        }
+      }
     }
     seq[g] = out;
     if (QUAL) qual[g] = q;
+    if (MOD) ml[g] = mod;
   }
 }
 
-size_t assemble_work_bytes(int C, long long total, bool qual) {
+size_t assemble_work_bytes(int C, long long total, bool qual, bool mod) {
   return (size_t)2 * C * sizeof(int) + (size_t)5 * total * sizeof(int) +
-         (qual ? (size_t)5 * total * sizeof(unsigned long long) : 0);
+         (qual ? (size_t)5 * total * sizeof(unsigned long long) : 0) +
+         (mod ? (size_t)total * sizeof(unsigned long long) : 0);
 }
 
 hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
                                  const int* read_off, int R, int C, int total, unsigned char* seq,
-                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s) {
+                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
+                                 const unsigned short* mw, unsigned char* ml) {
   const bool q = qual != nullptr;  // with qualities: qw and qual both given
+  const bool m = ml != nullptr;    // with modification values (only beside qualities): mw and ml both given
   if (R < 0 || C < 0 || total < 0 || !chunk_off || !read_off || (R > 0 && (!seq_len || !status)) ||
-      (C > 0 && !work) || (total > 0 && (!bases || !seq)) || (qw != nullptr) != q)
+      (C > 0 && !work) || (total > 0 && (!bases || !seq)) || (qw != nullptr) != q || (mw != nullptr) != m ||
+      (m && !q))
     return hipErrorInvalidValue;
   if (R == 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(status, 0, (size_t)R * sizeof(int), s);
   if (e != hipSuccess) return e;
   if (C == 0) return hipMemsetAsync(seq_len, 0, (size_t)R * sizeof(int), s);  // no chunks: every read is ""
-  // the 64-bit weight sums first, so they are 8-byte aligned whatever C is
+  // the 64-bit weight sums first, so they are 8-byte aligned whatever C is: wsum's five planes, then msum's one
   unsigned long long* wsum = static_cast<unsigned long long*>(work);
-  int* pos = q ? reinterpret_cast<int*>(wsum + (size_t)5 * total) : static_cast<int*>(work);
+  unsigned long long* msum = wsum + (size_t)5 * total;
+  int* pos = q ? reinterpret_cast<int*>(wsum + (size_t)(m ? 6 : 5) * total) : static_cast<int*>(work);
   int* rd = pos + C;
   int* count = rd + C;
   if (total > 0) {
     e = hipMemsetAsync(count, 0, (size_t)5 * total * sizeof(int), s);
-    if (e == hipSuccess && q) e = hipMemsetAsync(wsum, 0, (size_t)5 * total * sizeof(unsigned long long), s);
+    if (e == hipSuccess && q)
+      e = hipMemsetAsync(wsum, 0, (size_t)(m ? 6 : 5) * total * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
   }
   const int per = ASM_THREADS / 64;
   const dim3 grid((C + per - 1) / per), block(ASM_THREADS);
   hipLaunchKernelGGL(asm_overlap_kernel, dim3(C), block, 0, s, bases, chunk_off, read_off, R, pos, rd, status);
   hipLaunchKernelGGL(asm_place_kernel, dim3(R), block, 0, s, chunk_off, read_off, pos, status, seq_len);
-  if (total > 0 && q) {
-    hipLaunchKernelGGL(asm_vote_kernel<true>, grid, block, 0, s, bases, qw, chunk_off, read_off, pos, rd, status, C,
-                       total, count, wsum);
-    hipLaunchKernelGGL(asm_call_kernel<true>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, C,
-                       total, seq, qual);
+  if (total > 0 && m) {
+    hipLaunchKernelGGL((asm_vote_kernel<true, true>), grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd,
+                       status, C, total, count, wsum, msum);
+    hipLaunchKernelGGL((asm_call_kernel<true, true>), grid, block, 0, s, chunk_off, read_off, rd, seq_len, count,
+                       wsum, msum, C, total, seq, qual, ml);
+  } else if (total > 0 && q) {
+    hipLaunchKernelGGL(asm_vote_kernel<true>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
+                       C, total, count, wsum, msum);
+    hipLaunchKernelGGL(asm_call_kernel<true>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
+                       C, total, seq, qual, ml);
   } else if (total > 0) {
-    hipLaunchKernelGGL(asm_vote_kernel<false>, grid, block, 0, s, bases, qw, chunk_off, read_off, pos, rd, status, C,
-                       total, count, wsum);
-    hipLaunchKernelGGL(asm_call_kernel<false>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, C,
-                       total, seq, qual);
+    hipLaunchKernelGGL(asm_vote_kernel<false>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
+                       C, total, count, wsum, msum);
+    hipLaunchKernelGGL(asm_call_kernel<false>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
+                       C, total, seq, qual, ml);
   }
   return hipGetLastError();
 }
@@ -313,6 +342,40 @@ hipError_t launch_token_weights(const int* tokens, const float* logp, const floa
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(token_weights_kernel, dim3((n + TW_THREADS - 1) / TW_THREADS), dim3(TW_THREADS), 0, s, tokens,
                      logp, tok_logp, n, V, w);
+  return hipGetLastError();
+}
+
+// mw[i] = the modification weight of tokens[i] from its step's log-probs lp = logp[i]: 0 unless the token is
+// canon (C) or mod (M); else with d = (double)lp[canon] - (double)lp[mod], min(65535, floor(65535 / (1 + exp(d)) +
+// 0.5)), every operation rounded once (no FMA); a NaN d falls back to the hard call (65535 for mod, 0 for canon)
+__global__ void __launch_bounds__(TW_THREADS)
+token_mod_weights_kernel(const int* __restrict__ tokens, const float* __restrict__ logp, int n, int V, int canon,
+                         int mod, unsigned short* __restrict__ mw) {
+  const int i = blockIdx.x * TW_THREADS + threadIdx.x;
+  if (i >= n) return;
+  const int t = tokens[i];
+  unsigned short out = 0;
+  if (t == canon || t == mod) {  // both inside [0, V): the launcher checked
+    const double d = __dsub_rn((double)logp[(size_t)i * V + canon], (double)logp[(size_t)i * V + mod]);
+    if (d != d) {
+      out = t == mod ? 65535 : 0;
+    } else {
+      const double p = __ddiv_rn(1.0, __dadd_rn(1.0, exp(d)));  // exp(+inf) = inf -> 0, exp(-inf) = 0 -> 1
+      const double x = floor(__dadd_rn(__dmul_rn(65535.0, p), 0.5));
+      out = (unsigned short)(x < 65535.0 ? x : 65535.0);
+    }
+  }
+  mw[i] = out;
+}
+
+hipError_t launch_token_mod_weights(const int* tokens, const float* logp, int n, int V, int canon, int mod,
+                                    unsigned short* mw, hipStream_t s) {
+  if (n < 0 || V < 1 || canon < 0 || canon >= V || mod < 0 || mod >= V || canon == mod ||
+      (n > 0 && (!tokens || !logp || !mw)))
+    return hipErrorInvalidValue;
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(token_mod_weights_kernel, dim3((n + TW_THREADS - 1) / TW_THREADS), dim3(TW_THREADS), 0, s,
+                     tokens, logp, n, V, canon, mod, mw);
   return hipGetLastError();
 }
 

@@ -400,11 +400,14 @@ hipError_t launch_read_window(const float* sig, const long long* off, const int*
 // count to seq_len[r]; status[r] != 0 (bit 0: a chunk of 200 or more chars, bit 1: a char outside ACGTM) means
 // the read was not assembled (seq_len[r] = -1).  With qw (each base's uint16 weight) and qual, both or neither,
 // the columns' qualities Q in 0..40 go to qual, laid out like seq.  work holds assemble_work_bytes(C, total,
-// qual != nullptr) bytes
-size_t assemble_work_bytes(int C, long long total, bool qual = false);
+// qual != nullptr, ml != nullptr) bytes.  With mw (each base's uint16 modification weight) and ml too, both or
+// neither and only beside qw / qual, a column called C or M gets ML = min(255, (256 W) div (65535 n_cm)) in ml
+// (laid out like seq; W the mw sum of its C and M votes, n_cm their number), every other byte of ml 0
+size_t assemble_work_bytes(int C, long long total, bool qual = false, bool mod = false);
 hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
                                  const int* read_off, int R, int C, int total, unsigned char* seq,
-                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s);
+                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
+                                 const unsigned short* mw = nullptr, unsigned char* ml = nullptr);
 // the column quality's table, the doubles 10.0 ** (k / 10.0) for k < PHRED_LEVELS
 #define PHRED_LEVELS 41
 const double* phred_ratios();
@@ -412,6 +415,11 @@ const double* phred_ratios();
 // [n, V]) or tok_logp[i], exactly one of the two given; 0 for a token outside [0, V) or a non-finite lp
 hipError_t launch_token_weights(const int* tokens, const float* logp, const float* tok_logp, int n, int V,
                                 unsigned short* w, hipStream_t s);
+// modification weights: mw[i] = 0 unless tokens[i] is canon or mod (two different ids in [0, V)); else, with
+// d = (double)logp[i][canon] - (double)logp[i][mod], min(65535, floor(65535 / (1 + exp(d)) + 0.5)); a NaN d gives
+// the hard call (65535 for mod, 0 for canon)
+hipError_t launch_token_mod_weights(const int* tokens, const float* logp, int n, int V, int canon, int mod,
+                                    unsigned short* mw, hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

@@ -1,5 +1,5 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads, nd_assemble_reads_q, nd_token_weights): launches on the caller's stream, with no context.
+// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_token_weights, nd_token_mod_weights): launches on the caller's stream, with no context.
 // The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
@@ -297,6 +297,45 @@ int nd_token_weights(const int32_t* d_tokens, const float* d_logp, const float* 
   if ((int64_t)B * S > 0 && (!d_tokens || !d_w)) return fail(ND_ERR_ARG, "token_weights: null buffer");
   return status("token_weights", nd::launch_token_weights(d_tokens, d_logp, d_tok_logp, B * S, V, d_w,
                                                           (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_token_mod_weights(const int32_t* d_tokens, const float* d_logp, int32_t B, int32_t S, int32_t V,
+                         int32_t canon_id, int32_t mod_id, uint16_t* d_mw, void* stream) {
+  if (B < 0 || S < 0 || V < 1 || (int64_t)B * S >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "token_mod_weights: B and S must be >= 0, V >= 1 and B * S < 2^31");
+  if (canon_id < 0 || canon_id >= V || mod_id < 0 || mod_id >= V || canon_id == mod_id)
+    return fail(ND_ERR_ARG, "token_mod_weights: canon_id and mod_id must be two different ids in [0, V)");
+  if ((int64_t)B * S > 0 && (!d_tokens || !d_logp || !d_mw)) return fail(ND_ERR_ARG, "token_mod_weights: null buffer");
+  return status("token_mod_weights", nd::launch_token_mod_weights(d_tokens, d_logp, B * S, V, canon_id, mod_id, d_mw,
+                                                                  (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int64_t nd_assemble_reads_m_work_bytes(int32_t C, int64_t total_bases) {
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true, true) : -1;
+}
+
+int nd_assemble_reads_m(const uint8_t* d_bases, const uint16_t* d_qw, const uint16_t* d_mw,
+                        const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R, int32_t C,
+                        int64_t total_bases, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_ml, int32_t* d_seq_len,
+                        int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "assemble_reads_m: R, C and total_bases must be >= 0 and total_bases < 2^31");
+  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, true, true);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "assemble_reads_m: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_assemble_reads_m_work_bytes asks for");
+  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
+      (total_bases > 0 && (!d_bases || !d_qw || !d_mw || !d_seq || !d_qual || !d_ml)))
+    return fail(ND_ERR_ARG, "assemble_reads_m: null buffer");
+  if (R == 0) return ND_OK;
+  if (total_bases == 0)  // nothing to weigh: the plain call's paths (no chunks, or only empty ones)
+    return status("assemble_reads_m",
+                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
+                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+  return status("assemble_reads_m",
+                nd::launch_assemble_reads(d_bases, d_qw, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
+                                          d_qual, d_seq_len, d_status, d_work, (hipStream_t)stream, d_mw, d_ml),
+                ND_ERR_HIP);
 }
 
 int nd_phred_ratios(double* out, int32_t n) {

@@ -327,6 +327,23 @@ class Engine:
                                             self._stream()), "nd_token_weights")
         return w
 
+    def token_mod_weights(self, tokens, logp, canon_id: int, mod_id: int):
+        """The uint16 modification weights of a call's tokens (nd_token_mod_weights, on the current stream):
+        0 unless the token is ``canon_id`` ("C") or ``mod_id`` ("M"); else min(65535, floor(65535 p + 0.5)) with
+        p = 1 / (1 + exp(logp[..., canon_id] - logp[..., mod_id])), the model's P(methylated | the base is a C)
+        at that step (``logp`` [B, S, V]: a translate call's return_logp, or score_targets').  Returns an int16
+        device tensor shaped like ``tokens`` that holds the uint16 bits, as token_weights does."""
+        V = self.cfg.vocab
+        tokens = torch.as_tensor(tokens).to(self.device, torch.int32, non_blocking=True).contiguous()
+        lp = torch.as_tensor(logp).to(self.device, torch.float32, non_blocking=True).contiguous()
+        if tokens.dim() != 2 or tuple(lp.shape) != tuple(tokens.shape) + (V,):
+            raise ValueError("tokens must be [B, S] and logp [B, S, V]")
+        B, S = tokens.shape
+        mw = torch.empty(B, S, dtype=torch.int16, device=self.device)
+        _lib.check(self._L.nd_token_mod_weights(_ptr(tokens), _ptr(lp), B, S, V, int(canon_id), int(mod_id),
+                                                _ptr(mw), self._stream()), "nd_token_mod_weights")
+        return mw
+
     def encode(self, signal, lengths, spans=None):
         """Memory bank [B, T, d] of the encoder (rows >= span unspecified)."""
         signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
@@ -460,6 +477,12 @@ class EnginePool:
         eng = self.engines[lane]
         with torch.cuda.stream(eng.stream):
             return eng.token_weights(tokens, logp=logp, tok_logp=tok_logp)
+
+    def token_mod_weights(self, tokens, logp, canon_id: int, mod_id: int, lane: int = 0):
+        """Engine.token_mod_weights on the stream of ``lane`` (see token_weights)."""
+        eng = self.engines[lane]
+        with torch.cuda.stream(eng.stream):
+            return eng.token_mod_weights(tokens, logp, canon_id, mod_id)
 
     def encode(self, signal, lengths, spans=None):
         """Engine.encode on the next lane's context, joined to the current

@@ -314,12 +314,128 @@ def assemble_read_q(all_predictions, weights, src_seq_length: int, src_seq_strid
     return seq, quality_string(column_quality(np.ones(w.size, np.int64), w))
 
 
+# ---------------------------------------------------------------- per-base methylation probabilities (MM / ML)
+# CpG models have a ninth token M, a methylated C.  A C or M token's modification weight is the model's
+# P(methylated | the base is a C) at its step in 16 bits: with d = (double)lp[C] - (double)lp[M],
+# mw = min(65535, floor(65535 / (1 + exp(d)) + 0.5)), every operation rounded once (nd_token_mod_weights); 0 for
+# every other token; a NaN d gives the hard call.  Every char of a token's word carries the token's mw.  A column
+# of a read's vote called C or M is a site: with n_cm its C plus M votes and W the sum of their mw,
+# ML = min(255, (256 W) // (65535 n_cm)), SAM's ML scale; every other column gets 0.  Integers throughout, so the
+# device (assembly.hip, nd_assemble_reads_m) gives the same bytes.  The call itself is never changed.
+def token_mod_weight(lp_c, lp_m, is_mod) -> int:
+    """The uint16 modification weight of a C (``is_mod`` false) or M (true) token whose step gave the
+    log-probabilities ``lp_c`` and ``lp_m`` (float32) to the tokens C and M."""
+    d = float(np.float32(lp_c)) - float(np.float32(lp_m))
+    if math.isnan(d):
+        return WEIGHT_ONE if is_mod else 0
+    try:
+        e = math.exp(d)
+    except OverflowError:
+        e = math.inf
+    p = 1.0 / (1.0 + e)
+    return int(min(float(WEIGHT_ONE), math.floor(WEIGHT_ONE * p + 0.5)))
+
+
+def column_ml(n_cm, W):
+    """ML of sites with ``n_cm`` votes of class C or M whose modification weights sum to ``W`` (ints or integer
+    arrays): int or uint8 array; 0 where n_cm is 0."""
+    n64, w64 = np.asarray(n_cm, np.int64), np.asarray(W, np.int64)
+    ml = np.where(n64 > 0, np.minimum(255, (256 * w64) // np.maximum(WEIGHT_ONE * n64, 1)), 0).astype(np.uint8)
+    return int(ml) if ml.ndim == 0 else ml
+
+
+def _is_cm(base: str) -> bool:
+    return base.upper() in ("C", "M")
+
+
+def _add_count_m(consensus, wsum, msum, start, segment, w, mw):
+    """_add_count_q, a C or M vote's modification weight added to ``msum`` of its column."""
+    if len(mw) != len(segment):
+        raise ValueError("a chunk of %d bases with %d modification weights" % (len(segment), len(mw)))
+    _add_count_q(consensus, wsum, start, segment, w)
+    if start < 0:
+        segment, mw = segment[-start:], mw[-start:]
+        start = 0
+    for i, base in enumerate(segment):
+        if _is_cm(base):
+            msum[start + i] += mw[i]
+
+
+def simple_assembly_m(bpreads, weights, mod_weights):
+    """simple_assembly_q with the sums [length] (int64) of the C and M votes' modification weights beside it:
+    (consensus, wsum, msum)."""
+    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
+    vw = _valid_weights(bpreads, weights)
+    vm = _valid_weights(bpreads, mod_weights)
+    consensus = np.zeros([len(BASE_KEYS), 1000])
+    wsum = np.zeros([len(BASE_KEYS), 1000], np.int64)
+    msum = np.zeros(1000, np.int64)
+    pos = 0
+    length = 0
+    census_len = 1000
+    for indx, bpread in enumerate(valid):
+        if indx == 0:
+            _add_count_m(consensus, wsum, msum, 0, bpread, vw[0], vm[0])
+            continue
+        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
+        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
+        disp = match_block[0] - match_block[1]
+        if disp + pos + len(valid[indx]) > census_len:
+            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
+            wsum = np.pad(wsum, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
+            msum = np.pad(msum, (0, 1000), mode="constant", constant_values=0)
+            census_len += 1000
+        _add_count_m(consensus, wsum, msum, pos + disp, valid[indx], vw[indx], vm[indx])
+        pos += disp
+        length = max(length, pos + len(valid[indx]))
+    return consensus[:, :length], wsum[:, :length], msum[:length]
+
+
+def assemble_read_m(all_predictions, weights, mod_weights, src_seq_length: int, src_seq_stride: int):
+    """assemble_read_q with per-base methylation values: (sequence, quality string, ml uint8 [len(sequence)]).
+    ``mod_weights``: per chunk, the uint16 modification weight of every char of its x[0] with the spaces removed.
+    Sequence and qualities are assemble_read_q's; ml is 0 wherever the sequence is neither C nor M."""
+    if src_seq_stride < src_seq_length:
+        consensus, wsum, msum = simple_assembly_m(all_predictions, weights, mod_weights)
+        win = np.argmax(consensus, axis=0)
+        n = consensus.sum(axis=0).astype(np.int64)
+        S = wsum[win, np.arange(win.size)] if win.size else np.zeros(0, np.int64)
+        site = (win == BASE_DICT["C"]) | (win == BASE_DICT["M"])
+        n_cm = (consensus[BASE_DICT["C"]] + consensus[BASE_DICT["M"]]).astype(np.int64)
+        ml = np.where(site, column_ml(n_cm, msum), 0).astype(np.uint8)
+        return index2base(win), quality_string(column_quality(n, S)), ml
+    # the concatenation branch: every base is its own column, n_cm = 1 and W = its modification weight
+    seq, qual = assemble_read_q(all_predictions, weights, src_seq_length, src_seq_stride)
+    vm = _valid_weights(all_predictions, mod_weights)
+    mw = np.concatenate(vm) if vm else np.zeros(0, np.int64)
+    if mw.size != len(seq):
+        raise ValueError("a read of %d bases with %d modification weights" % (len(seq), mw.size))
+    site = np.fromiter((_is_cm(b) for b in seq), bool, len(seq))
+    return seq, qual, np.where(site, column_ml(np.ones(mw.size, np.int64), mw), 0).astype(np.uint8)
+
+
+def mod_fastq_record(name: str, sequence: str, quality: str, ml) -> str:
+    """The four lines of result/<read>.mod.fastq: the read with every M written as C (the canonical sequence the
+    SAM tags refer to), its qualities, and in the header, when the read has a site, the tags MM:Z:C+m. (every C
+    of the canonical sequence is listed: all skip counts 0, the '.' mode) and ML:B:C (the sites' ML in sequence
+    order)."""
+    ml = np.asarray(ml, np.uint8).reshape(-1)
+    if ml.size != len(sequence) or len(quality) != len(sequence):
+        raise ValueError("a read of %d bases with %d qualities and %d ML values" % (len(sequence), len(quality),
+                                                                                   ml.size))
+    sites = [int(v) for b, v in zip(sequence, ml) if _is_cm(b)]
+    head = "@" + name
+    if sites:
+        head += "\tMM:Z:C+m." + ",0" * len(sites) + ";\tML:B:C" + "".join(",%d" % v for v in sites)
+    return "%s\n%s\n+\n%s\n" % (head, sequence.replace("M", "C").replace("m", "c"), quality)
+
+
 # ---------------------------------------------------------------- assembly on the device (-assembly gpu)
 ASM_STATUS_LONG = 1   # include/nanodec.h nd_assemble_reads: a chunk of 200 or more chars (difflib autojunk)
 ASM_STATUS_CHAR = 2   # a char whose upper case is not in BASE_KEYS
 
 
-def pack_assembly_input(reads, weights=None):
+def pack_assembly_input(reads, weights=None, mod_weights=None):
     """The input of nd_assemble_reads for a group of reads (each the
     all_predictions assemble_read takes): every chunk's x[0] with the spaces
     removed, as ASCII bytes, concatenated.  Returns (bases uint8 [total],
@@ -330,10 +446,14 @@ def pack_assembly_input(reads, weights=None):
     before it removes the spaces, so that one stays in its chunk list as an
     empty string).  Such a read is packed with no chunks.
     With ``weights`` (per read, per chunk, the uint16 weight of every char of that string) a fifth value
-    follows: qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q)."""
-    lens, parts, host, wparts = [], [], [], []
+    follows: qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q).  With
+    ``mod_weights`` too (laid out like ``weights``, which it needs) a sixth: mw uint16 [total], each byte's
+    modification weight (nd_assemble_reads_m)."""
+    lens, parts, host, wparts, mparts = [], [], [], [], []
     if weights is not None and len(weights) != len(reads):
         raise ValueError("one list of weights per read")
+    if mod_weights is not None and (weights is None or len(mod_weights) != len(reads)):
+        raise ValueError("one list of modification weights per read, beside the weights")
     read_off = np.zeros(len(reads) + 1, np.int64)
     for r, preds in enumerate(reads):
         strs = [x[0].replace(" ", "") for x in preds]
@@ -353,6 +473,14 @@ def pack_assembly_input(reads, weights=None):
                 if w.size != len(st):
                     raise ValueError("a chunk of %d bases with %d weights" % (len(st), w.size))
                 wparts.append(w)
+        if mod_weights is not None:
+            if len(mod_weights[r]) != len(strs):
+                raise ValueError("one modification weight array per chunk")
+            for st, w in zip(strs, mod_weights[r]):
+                w = np.asarray(w, np.uint16).reshape(-1)
+                if w.size != len(st):
+                    raise ValueError("a chunk of %d bases with %d modification weights" % (len(st), w.size))
+                mparts.append(w)
         parts.append(raw)
         lens.extend(len(s) for s in strs)
         read_off[r + 1] = read_off[r] + len(strs)
@@ -364,13 +492,17 @@ def pack_assembly_input(reads, weights=None):
     if weights is None:
         return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
     qw = np.concatenate(wparts) if wparts else np.zeros(0, np.uint16)
-    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw
+    if mod_weights is None:
+        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw
+    mw = np.concatenate(mparts) if mparts else np.zeros(0, np.uint16)
+    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw, mw
 
 
-def _assemble_device(bases, chunk_off, read_off, device, qw=None):
+def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
     """One nd_assemble_reads call on the CURRENT stream of ``device``:
     (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host.  With ``qw`` (uint16 [total], each
-    base's weight) the call is nd_assemble_reads_q and qual uint8 [total] follows."""
+    base's weight) the call is nd_assemble_reads_q and qual uint8 [total] follows; with ``mw`` too (uint16 [total],
+    each base's modification weight) it is nd_assemble_reads_m and ml uint8 [total] follows qual."""
     import ctypes
 
     import torch
@@ -379,7 +511,10 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None):
     dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
     R, C, total = len(read_off) - 1, len(chunk_off) - 1, int(bases.size)
     L = _lib.lib()
-    work_bytes = int((L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes)(C, total))
+    if mw is not None and qw is None:
+        raise ValueError("mw needs qw")
+    work_bytes = int((L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes
+                      if mw is None else L.nd_assemble_reads_m_work_bytes)(C, total))
     with torch.cuda.device(dev):
         off_d = _pinned(np.concatenate([chunk_off, read_off])).to(dev, non_blocking=True)
         bases_d = _pinned(bases).to(dev, non_blocking=True)
@@ -397,18 +532,29 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None):
                 raise ValueError("qw must hold one uint16 per base")
             qw_d = _pinned(qw.view(np.int16)).to(dev, non_blocking=True)  # the bits: torch has no uint16 copy
             qual_d = torch.empty(total, dtype=torch.uint8, device=dev)
-            _lib.check(L.nd_assemble_reads_q(p(bases_d), p(qw_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
-                                             p(qual_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
-                       "nd_assemble_reads_q")
+            if mw is None:
+                _lib.check(L.nd_assemble_reads_q(p(bases_d), p(qw_d), p(off_d), p(off_d[C + 1:]), R, C, total,
+                                                 p(seq_d), p(qual_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes,
+                                                 stream), "nd_assemble_reads_q")
+            else:
+                if mw.dtype != np.uint16 or mw.size != total:
+                    raise ValueError("mw must hold one uint16 per base")
+                mw_d = _pinned(mw.view(np.int16)).to(dev, non_blocking=True)
+                ml_d = torch.empty(total, dtype=torch.uint8, device=dev)
+                _lib.check(L.nd_assemble_reads_m(p(bases_d), p(qw_d), p(mw_d), p(off_d), p(off_d[C + 1:]), R, C, total,
+                                                 p(seq_d), p(qual_d), p(ml_d), p(out_d[0]), p(out_d[1]), p(work_d),
+                                                 work_bytes, stream), "nd_assemble_reads_m")
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         seq = seq_d.cpu().numpy()
+        if mw is not None:
+            return seq, out[0], out[1], qual_d.cpu().numpy(), ml_d.cpu().numpy()
         if qw is not None:
             return seq, out[0], out[1], qual_d.cpu().numpy()
     return seq, out[0], out[1]
 
 
 def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None, stats=None,
-                   defer_errors: bool = False, weights=None):
+                   defer_errors: bool = False, weights=None, mod_weights=None):
     """assemble_read for a group of reads: one string per read.
 
     ``device=None``, or ``src_seq_stride >= src_seq_length`` (translate.py's
@@ -425,8 +571,13 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
     (the caller assembles it again where it handles that read's errors).
     ``weights`` (per read, per chunk, the uint16 weight of every char of the chunk's string; see
     assemble_read_q): every read yields (sequence, quality string) instead, the device call is
-    nd_assemble_reads_q, and the host path and the fallback are assemble_read_q."""
+    nd_assemble_reads_q, and the host path and the fallback are assemble_read_q.
+    ``mod_weights`` (beside ``weights``, laid out like them; see assemble_read_m): every read yields (sequence,
+    quality string, ml uint8 array), the device call is nd_assemble_reads_m, and the host path and the fallback
+    are assemble_read_m."""
     reads = list(reads)
+    if mod_weights is not None and weights is None:
+        raise ValueError("mod_weights need weights")
     if weights is None:
         one = lambda r: assemble_read(reads[r], src_seq_length, src_seq_stride)  # noqa: E731
     else:
@@ -434,21 +585,32 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
         if len(weights) != len(reads):
             raise ValueError("one list of weights per read")
         one = lambda r: assemble_read_q(reads[r], weights[r], src_seq_length, src_seq_stride)  # noqa: E731
+        if mod_weights is not None:
+            mod_weights = list(mod_weights)
+            if len(mod_weights) != len(reads):
+                raise ValueError("one list of modification weights per read")
+            one = lambda r: assemble_read_m(reads[r], weights[r], mod_weights[r], src_seq_length,  # noqa: E731
+                                            src_seq_stride)
     if device is None or src_seq_stride >= src_seq_length:
         return [one(r) for r in range(len(reads))]
     R = len(reads)
     if weights is None:
         bases, chunk_off, read_off, host = pack_assembly_input(reads)
         out = [""] * R  # no bases at all: every device read is ""
-    else:
+    elif mod_weights is None:
         bases, chunk_off, read_off, host, qw = pack_assembly_input(reads, weights)
         out = [("", "")] * R
+    else:
+        bases, chunk_off, read_off, host, qw, mw = pack_assembly_input(reads, weights, mod_weights)
+        out = [("", "", np.zeros(0, np.uint8)) for _ in range(R)]
     todo = set(host)
     if bases.size:
         if weights is None:
             seq, seq_len, status = _assemble_device(bases, chunk_off, read_off, device)
-        else:
+        elif mod_weights is None:
             seq, seq_len, status, qual = _assemble_device(bases, chunk_off, read_off, device, qw)
+        else:
+            seq, seq_len, status, qual, ml = _assemble_device(bases, chunk_off, read_off, device, qw, mw)
         raw = seq.tobytes()
         start = chunk_off[read_off[:-1]]
         for r in range(R):
@@ -458,6 +620,8 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
                 out[r] = raw[start[r]: start[r] + seq_len[r]].decode("ascii")
                 if weights is not None:
                     out[r] = (out[r], quality_string(qual[start[r]: start[r] + seq_len[r]]))
+                if mod_weights is not None:
+                    out[r] = out[r] + (ml[start[r]: start[r] + seq_len[r]].copy(),)
     if stats is not None:
         stats["reads"] = stats.get("reads", 0) + R
         stats["fallback"] = stats.get("fallback", 0) + len(todo)

@@ -81,6 +81,11 @@ def translate_parser() -> argparse.ArgumentParser:
          help="also write result/<read>.fastq: per-base qualities 0..40 from the model's own probability of "
               "each called base, carried through the assembly vote (not recalibrated against error rates); "
               "the .fasta, segment and speed.txt outputs are unchanged; not together with -attn_debug")
+    _add(g, "mod_probs", action="store_true",
+         help="for a -cpg model (a vocabulary with C and M): also write result/<read>.mod.fastq, the read with M "
+              "written as C, the qualities of -fastq, and SAM MM:Z:C+m. / ML:B:C tags in the header with the "
+              "model's P(methylated | C) 0..255 of every C, carried through the assembly vote; the other outputs "
+              "are unchanged; not together with -attn_debug")
     return p
 
 

@@ -140,7 +140,9 @@ class Translator(object):
         self._pinned, self._pin_i = None, 0
         self.last_gold_scores = None  # per-chunk gold scores of the last translate(src, tgt=...)
 
-    def _check_supported(self, qualities: bool = False):
+    def _check_supported(self, qualities: bool = False, mods: bool = False):
+        if mods and not ("C" in self.cfg.itos and "M" in self.cfg.itos):
+            raise ValueError("methylation probabilities need a vocabulary with the tokens C and M (a -cpg model)")
         if qualities and self.beam_size > 1 and self.cfg.self_attn_type == "average":
             # the beam's qualities come from the scoring pass, which refuses such decoders
             raise NotImplementedError("qualities with beam search are not supported for average-attention decoders")
@@ -207,12 +209,13 @@ class Translator(object):
         return max(1, int(getattr(self.engine, "lanes", 1)))
 
     def _submit(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
-                attn: bool = False, qual: bool = False):
+                attn: bool = False, qual: bool = False, mods: bool = False):
         """Stage up to max_batch chunks with their reference spans (and, for
         the classic Beam, their reference batch ids) and enqueue the engine
         call.  Greedy and sampling calls return before the device finishes;
         ``_finish`` collects the results.  ``qual``: the token weights of each
-        chunk's best hypothesis are wanted too (see stream_reads)."""
+        chunk's best hypothesis are wanted too, ``mods`` (with ``qual``) their
+        modification weights as well (see stream_reads)."""
         n = len(chunks)
         lens = np.array([len(c) for c in chunks], np.int32)
         if (lens < 1).any():
@@ -228,18 +231,21 @@ class Translator(object):
         L[:n], S[:n] = lens, spans
         if dev_in is not None:
             sig, L, S = dev_in
-        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual)
-        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual)
+        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual, **({"mods": True} if mods else {}))
+        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual, mods)
         return job
 
-    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs, qual: bool = False):
+    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs, qual: bool = False,
+                 mods: bool = False):
         """The engine call for one staged batch (signal [B, T], chunk lengths
         and spans [B]; the first n rows are chunks), its results copied to
         pinned host buffers on the call's own stream.  ``qual``: a greedy or
         sampling call also returns its log-probs and the chosen tokens'
         weights (nd_token_weights) follow it on its stream; a beam call's
-        inputs are kept for the scoring pass of ``_beam_weights``."""
-        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual)
+        inputs are kept for the scoring pass of ``_beam_weights``.  ``mods``:
+        the tokens' modification weights (nd_token_mod_weights) follow the
+        weights, from the same log-probs."""
+        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual, mods=mods)
         # without qualities the engine sees exactly the arguments it always has
         want = dict(return_logp=True) if qual else {}
         if self.beam_size == 1:
@@ -254,8 +260,10 @@ class Translator(object):
                 r = self.engine.translate_greedy(sig, L, S, max_len=self.max_length, min_len=self.min_length,
                                                  return_attn=attn, **want)
             if qual:
-                r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"],
-                                                         **({"lane": r["lane"]} if "lane" in r else {}))
+                lane = {"lane": r["lane"]} if "lane" in r else {}
+                r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"], **lane)
+                if mods:
+                    r["mod_weights"] = self.engine.token_mod_weights(r["tokens"], r["logp"], *self._cm_ids(), **lane)
             job.update(kind="greedy", r=r)
         else:
             # reference batches: the chunks of one group, sorted by length
@@ -297,7 +305,11 @@ class Translator(object):
             self._copy_out(job)
         return job
 
-    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow", "weights")
+    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow", "weights", "mod_weights")
+
+    def _cm_ids(self):
+        """(id of "C", id of "M") in the target vocabulary."""
+        return self.cfg.itos.index("C"), self.cfg.itos.index("M")
 
     def _copy_out(self, job):
         """Enqueue the call's device-to-host copies (into pinned buffers) on
@@ -350,7 +362,7 @@ class Translator(object):
         the attention rows of each hypothesis ([steps, cut] arrays, cut as the
         reference's results["attention"] has it)."""
         n, lens, attn = job["n"], job["lens"], job["attn"]
-        qual = job.get("qual", False)
+        qual, mods = job.get("qual", False), job.get("mods", False)
         out = []
         if job["kind"] == "greedy":
             tok, sc, at, ov = self._host(job, "tokens", "scores", "attn", "overflow")
@@ -358,6 +370,10 @@ class Translator(object):
                 return self._rerun_exact(job)
             if qual:
                 w = self._host(job, "weights")[0].view(np.uint16)
+                if mods:
+                    mw = self._host(job, "mod_weights")[0].view(np.uint16)
+                    return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]),
+                             self._char_weights(tok[i].tolist(), mw[i])) for i in range(n)]
                 return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]))
                         for i in range(n)]
             for i in range(n):
@@ -371,11 +387,15 @@ class Translator(object):
         if self._overflowed(job, ov):
             return self._rerun_exact(job)
         w = self._beam_weights(job, tok, ln) if qual else None
+        if mods:
+            w, mw = w
         for i in range(n):
             o = ([float(sc[i, k]) for k in range(self.n_best)],
                  [tok[i, k, : ln[i, k]].tolist() for k in range(self.n_best)])
             if qual:
                 o = o + (self._char_weights(o[1][0], w[i]),)
+            if mods:
+                o = o + (self._char_weights(o[1][0], mw[i]),)
             if attn:
                 atts = []
                 for k in range(self.n_best):
@@ -396,9 +416,12 @@ class Translator(object):
         """The token weights [B, L] (uint16) of a finished beam call's best hypotheses: the existing
         teacher-forced scoring pass (score_targets) over the call's own inputs, each gold row the hypothesis'
         tokens as returned (EOS included when it finished) and gold_len its length, then nd_token_weights of
-        the pass's per-token log-probs.  The encoder runs a second time for this."""
+        the pass's per-token log-probs.  The encoder runs a second time for this.  A call submitted with
+        ``mods`` asks the same pass for its full log-probs too and returns (weights, modification weights), the
+        latter nd_token_mod_weights of those log-probs."""
         sig, ln_in, sp = job["eng_in"]
-        B = job["B"]
+        B, mods = job["B"], job.get("mods", False)
+        want = dict(return_logp=True) if mods else {}
         n_tok = np.clip(ln[:B, 0].astype(np.int32), 1, min(tok.shape[2], self.engine.max_steps))
         L = min(self.engine.max_steps, (int(n_tok.max()) + 7) // 8 * 8)  # one captured graph per (B, T, L)
         gold = np.full((B, L), self.cfg.pad_idx, np.int32)
@@ -408,7 +431,7 @@ class Translator(object):
         gold_t, len_t = torch.from_numpy(gold), torch.from_numpy(n_tok)
 
         def score():
-            r = self.engine.score_targets(sig, ln_in, sp, gold=gold_t, gold_len=len_t, return_tok_logp=True)
+            r = self.engine.score_targets(sig, ln_in, sp, gold=gold_t, gold_len=len_t, return_tok_logp=True, **want)
             if "event" in r:
                 r["event"].synchronize()
             ov = r.get("overflow")
@@ -421,9 +444,14 @@ class Translator(object):
                 r, _ = score()
             finally:
                 self.engine.set_exact_fp32(False)
-        w = self.engine.token_weights(gold_t, tok_logp=r["tok_logp"], **({"lane": r["lane"]} if "lane" in r else {}))
+        lane = {"lane": r["lane"]} if "lane" in r else {}
+        w = self.engine.token_weights(gold_t, tok_logp=r["tok_logp"], **lane)
+        # positions past a hypothesis' length hold pad_idx, which is neither C nor M: their weight is 0
+        mw = self.engine.token_mod_weights(gold_t, r["logp"], *self._cm_ids(), **lane) if mods else None
         if "lane" in r:
             self.engine.engines[r["lane"]].stream.synchronize()
+        if mods:
+            return w.cpu().numpy().view(np.uint16), mw.cpu().numpy().view(np.uint16)
         return w.cpu().numpy().view(np.uint16)
 
     def _char_weights(self, toks, w) -> np.ndarray:
@@ -575,15 +603,16 @@ class Translator(object):
             output += row_format.format(*row) + "\n"
         self.out_file_attn.write(output)
 
-    def _want_qualities(self, qualities: bool, attn_debug: bool = False) -> bool:
+    def _want_qualities(self, qualities: bool, attn_debug: bool = False, mods: bool = False) -> bool:
+        qualities = qualities or mods  # the methylation values travel beside the qualities
         if qualities:
             if attn_debug:
                 raise ValueError("qualities are not available together with attn_debug")
-            self._check_supported(qualities=True)
+            self._check_supported(qualities=True, **({"mods": True} if mods else {}))
         return bool(qualities)
 
     def stream_reads(self, reads: Iterable[Sequence], batch_size: int, attn_debug: bool = False,
-                     qualities: bool = False):
+                     qualities: bool = False, mods: bool = False):
         """Generator over many reads (any iterable of chunk lists): chunks are
         packed across reads into engine batches of max_batch, one batch (one
         per EnginePool lane) stays in flight on the device while the next is
@@ -596,9 +625,12 @@ class Translator(object):
         character of its string with the spaces removed (frontend.assemble_read_q
         turns them into a read's quality string).  Greedy and sampling take them
         from the call's own log-probs; beam search scores the best hypothesis in
-        a second, teacher-forced pass (_beam_weights)."""
+        a second, teacher-forced pass (_beam_weights).  ``mods`` (a vocabulary
+        with C and M; implies ``qualities``): a fourth entry follows, the uint16
+        modification weights of the same characters (frontend.assemble_read_m
+        turns them into a read's ML values), from the same log-probs."""
         import collections
-        qualities = self._want_qualities(qualities, attn_debug)
+        qualities = self._want_qualities(qualities, attn_debug, mods)
         cap = self.engine.max_batch
         depth = self._depth()
         pending, inflight = [], collections.deque()
@@ -617,7 +649,7 @@ class Translator(object):
 
         def submit(items):
             return self._submit([g[2] for g in items], [g[3] for g in items], [g[4] for g in items],
-                                attn=attn_debug, qual=qualities), items
+                                attn=attn_debug, qual=qualities, **({"mods": True} if mods else {})), items
 
         for ri, read in enumerate(reads):
             chunks = [parse_chunk(c) for c in read]
@@ -645,28 +677,34 @@ class Translator(object):
                 yield r, results.pop(r)
 
     def translate_reads(self, reads: Sequence[Sequence], batch_size: int, attn_debug: bool = False,
-                        qualities: bool = False):
+                        qualities: bool = False, mods: bool = False):
         """Translate many reads (stream_reads); returns per read
         (all_scores, all_predictions) as translate() does; with ``qualities``
         (all_scores, all_predictions, all_weights), all_weights per chunk the
-        uint16 weights of its best hypothesis (see stream_reads)."""
+        uint16 weights of its best hypothesis (see stream_reads); with ``mods``
+        (which implies ``qualities``) also all_mod_weights, laid out like all_weights."""
         results = [None] * len(reads)
-        for ri, res in self.stream_reads(reads, batch_size, attn_debug, **({"qualities": True} if qualities else {})):
+        qualities = bool(qualities or mods)
+        for ri, res in self.stream_reads(reads, batch_size, attn_debug, **({"qualities": True} if qualities else {}),
+                                         **({"mods": True} if mods else {})):
             results[ri] = res
-        return self._report(results, attn_debug, qualities=qualities)
+        return self._report(results, attn_debug, qualities=qualities, mods=mods)
 
     def translate_raw_reads(self, raws: Sequence[np.ndarray], batch_size: int, normalization: str = "median",
-                            src_seq_length: int = 512, src_seq_stride: int = 512, qualities: bool = False):
+                            src_seq_length: int = 512, src_seq_stride: int = 512, qualities: bool = False,
+                            mods: bool = False):
         """translate_reads on raw reads with the signal front end on the
         device (stream_raw_reads); returns per read (all_scores,
-        all_predictions), with ``qualities`` also all_weights."""
+        all_predictions), with ``qualities`` also all_weights, with ``mods`` also all_mod_weights."""
         results = [None] * len(raws)
+        qualities = bool(qualities or mods)
         for ri, res in self.stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
-                                             **({"qualities": True} if qualities else {})):
+                                             **({"qualities": True} if qualities else {}),
+                                             **({"mods": True} if mods else {})):
             results[ri] = res
-        return self._report(results, False, qualities=qualities)
+        return self._report(results, False, qualities=qualities, mods=mods)
 
-    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False):
+    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False, mods: bool = False):
         """Per read (all_scores, all_predictions) from per-chunk results, with
         the reference's verbose / -dump_beam / report_score side outputs
         (translate/translator.py:255-369).  gold (translate with tgt): per chunk
@@ -675,7 +713,7 @@ class Translator(object):
         counter = 0
         pred_score_total, pred_words_total = 0.0, 0
         for r in results:
-            all_scores, all_predictions, all_weights = [], [], []
+            all_scores, all_predictions, all_weights, all_mods = [], [], [], []
             for res in r:
                 scores, toks = res[0], res[1]
                 sents = [self._tokens_to_sent(t) for t in toks]
@@ -685,6 +723,8 @@ class Translator(object):
                 all_predictions.append([" ".join(s) for s in sents[: self.n_best]])
                 if qualities:
                     all_weights.append(res[2])
+                if mods:
+                    all_mods.append(res[3])
                 pred_score_total += scores[0]
                 pred_words_total += len(sents[0])
                 if self.verbose:
@@ -702,7 +742,8 @@ class Translator(object):
                         self.logger.info(msg)
                     else:
                         os.write(1, msg.encode("utf-8"))
-            ret.append((all_scores, all_predictions, all_weights) if qualities else (all_scores, all_predictions))
+            ret.append((all_scores, all_predictions) + ((all_weights,) if qualities else ()) +
+                       ((all_mods,) if mods else ()))
         if self.dump_beam:
             # translator.py:365-368 dumps the beam trace accumulator.  (The
             # reference reads it through a `self.translator` attribute the
@@ -724,7 +765,7 @@ class Translator(object):
             return self.engine.engines[self.engine._next].stream
         return torch.cuda.current_stream(self.engine.device)
 
-    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False):
+    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False, mods: bool = False):
         """One engine batch from raw reads: chunk descriptors ``items`` =
         (read, chunk, start, length, span, reference batch) and the reads
         they cut (``batch_reads``: read -> float64 samples).  The front end
@@ -750,13 +791,13 @@ class Translator(object):
                                               normalization, B, T, self.engine.device)
             ls_d = torch.from_numpy(ls).pin_memory().to(self.engine.device, non_blocking=True)
             job = self._enqueue(sig, ls_d[:B], ls_d[B:], B, n, lens, [it[5] for it in items], False,
-                                (sig, ls_d, keep), qual)
-        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual)
+                                (sig, ls_d, keep), qual, **({"mods": True} if mods else {}))
+        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual, mods)
         return job
 
     def stream_raw_reads(self, raws: Iterable, batch_size: int, normalization: str = "median",
                          src_seq_length: int = 512, src_seq_stride: int = 512, arrays: bool = False,
-                         qualities: bool = False):
+                         qualities: bool = False, mods: bool = False):
         """stream_reads on RAW reads (float64 sample arrays, as
         frontend.read_raw returns them) with extract_fast5_raw's
         normalisation and windowing (utils/labelop.py:194-243) on the device:
@@ -770,13 +811,16 @@ class Translator(object):
         max_length] int32, scores [n_chunks] float32) instead.  ``qualities``
         as in stream_reads; with ``arrays`` a fourth array follows, the
         tokens' weights [n_chunks, max_length] uint16 (one per token, EOS and
-        what follows it included)."""
+        what follows it included).  ``mods`` as in stream_reads; with
+        ``arrays`` a fifth array, the tokens' modification weights, laid out
+        like the fourth."""
         import collections
 
         from . import frontend
         if arrays and self.beam_size != 1:
             raise ValueError("arrays=True is for greedy / sampling decoding")
-        qualities = self._want_qualities(qualities)
+        qualities = self._want_qualities(qualities, mods=mods)
+        n_w = (2 if mods else 1) if qualities else 0  # uint16 arrays per read with ``arrays``
         cap = self.engine.max_batch
         depth = self._depth()
         pending, batch_reads, inflight = [], {}, collections.deque()
@@ -804,20 +848,21 @@ class Translator(object):
 
         def flush():
             nonlocal pending, batch_reads
-            inflight.append((self._submit_raw(pending, batch_reads, normalization, qualities), pending))
+            inflight.append((self._submit_raw(pending, batch_reads, normalization, qualities,
+                                              **({"mods": True} if mods else {})), pending))
             pending, batch_reads = [], {}
 
         for ri, raw in enumerate(raws):
             raw = np.asarray(raw, dtype=np.float64).reshape(-1)
             if raw.size == 0:
                 empty = (np.zeros((0, self.max_length), np.int32), np.zeros(0, np.float32)) + \
-                    ((np.zeros((0, self.max_length), np.uint16),) if qualities else ())
+                    tuple(np.zeros((0, self.max_length), np.uint16) for _ in range(n_w))
                 yield (ri,) + empty if arrays else (ri, [])
                 continue
             wins = frontend.windows(int(raw.size), src_seq_length, src_seq_stride)
             if arrays:
                 results[ri] = (np.empty((len(wins), self.max_length), np.int32), np.empty(len(wins), np.float32)) + \
-                    ((np.empty((len(wins), self.max_length), np.uint16),) if qualities else ())
+                    tuple(np.empty((len(wins), self.max_length), np.uint16) for _ in range(n_w))
             else:
                 results[ri] = [None] * len(wins)
             remaining[ri] = len(wins)
@@ -841,10 +886,13 @@ class Translator(object):
 
     def _finish_arrays(self, job):
         """(tokens [n, S], scores [n]) numpy of a greedy / sampling call; its tokens' weights [n, S] uint16
-        follow when the call was submitted with qualities."""
+        follow when the call was submitted with qualities, then their modification weights when with mods."""
         tok, sc, ov = self._host(job, "tokens", "scores", "overflow")
         if self._overflowed(job, ov):
             return self._rerun_exact(job, self._finish_arrays)
+        if job.get("mods"):
+            w, mw = self._host(job, "weights", "mod_weights")
+            return tok[: job["n"]], sc[: job["n"]], w.view(np.uint16)[: job["n"]], mw.view(np.uint16)[: job["n"]]
         if job.get("qual"):
             return tok[: job["n"]], sc[: job["n"]], self._host(job, "weights")[0].view(np.uint16)[: job["n"]]
         return tok[: job["n"]], sc[: job["n"]]
