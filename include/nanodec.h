@@ -585,6 +585,22 @@ int nd_op_fold_layernorm(const float* W, const float* bias, const float* ln_g, c
 int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B,
                         int32_t T, void* stream);
 
+/* Transformer encoder layer 0 up to (not including) W_o, as the engine runs
+ * it: in closed form from the scalar samples (no x, no q | k | v rows), after
+ * the same load-time preparation nd_finalize makes.  signal [B,T], span [B],
+ * w_in / b_in [256] (the Linear(1, d) embedding), nwqkv [768,256] / nbqkv [768]
+ * the layer's QKV with its LayerNorm affine folded (nd_op_fold_layernorm);
+ * out [B*T,256]: rows t < min(span, T) written, the others untouched.  Key
+ * mask signal == 0.0, keys >= span excluded.  Nullable device outputs of the
+ * preparation: ac_out [6*256] floats (a [768], then c [768]), scal_out [4]
+ * doubles (the means of w'^2, w' b_perp, b_perp^2, then s0: 0 while
+ * cos^2(w', b') <= 1/16, else -mean(w' b') / mean(w'^2) in fp32), coef_out [48]
+ * floats.  T outside 1..512, B < 1 or a null input: ND_ERR_ARG, nothing
+ * launched.  Synchronises the stream. */
+int nd_op_enc_layer0(const float* signal, const int32_t* span, const float* w_in, const float* b_in,
+                     const float* nwqkv, const float* nbqkv, float* out, int32_t B, int32_t T, float* ac_out,
+                     double* scal_out, float* coef_out, void* stream);
+
 /* Decoder self-attention for one step (multi_headed_attn.py:124-141):
  * qkv [R, 3*d] and out [R, d] P16-packed (R padded to a multiple of 16);
  * cache [R, max_steps, 2*d] row-major (this step's k|v is appended at

@@ -13,7 +13,9 @@
 // * dec_self_attention / dec_ctx_attention: the decoder's q_len = 1
 //   attention (multi_headed_attn.py:124-153 cache modes), bandwidth bound.
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <vector>
 
 #include "common.hpp"
 #include "head.hpp"
@@ -54,7 +56,15 @@ hipError_t launch_enc_embed(const float* signal, const float* w_in, const float*
   return hipGetLastError();
 }
 
-// EmbedQkv's a, c (thread n of 768) and means (block 0), accumulated in double
+// EmbedQkv's a, c (thread n of 768) and scalars (block 0), accumulated in double.
+// Every thread derives s0 itself (rounded to fp32: the value the attention
+// kernel subtracts, so s w' + b' = (s - s0) w' + b_perp holds exactly) and
+// projects b_perp = b' + s0 w', not b'.  s0 = -m_wb / m_ww once cos^2(w', b')
+// exceeds 1/16; below that the form about s = 0 loses at most a factor
+// 1 / (1 - cos^2) <= 16/15 to cancellation, and s0 = 0 keeps such a model's
+// results bit for bit what they were before the shift existed (s - 0 is s).
+// s0 = 0 also when m_ww = 0 or the quotient does not fit fp32.
+// scal: m_ww, mean(w' b_perp), mean(b_perp^2), s0.
 __global__ void __launch_bounds__(256)
 embed_qkv_prep_kernel(const float* __restrict__ w, const float* __restrict__ b, const float* __restrict__ W,
                       float* __restrict__ ac, double* __restrict__ scal) {
@@ -70,25 +80,35 @@ embed_qkv_prep_kernel(const float* __restrict__ w, const float* __restrict__ b, 
   }
   wm /= ND_D;
   bm /= ND_D;
+  double ww = 0.0, wb = 0.0, bb = 0.0;
+  for (int d = 0; d < ND_D; ++d) {
+    ww += (wd[d] - wm) * (wd[d] - wm);
+    wb += (wd[d] - wm) * (bd[d] - bm);
+    bb += (bd[d] - bm) * (bd[d] - bm);
+  }
+  float s0f = ww > 0.0 && 16.0 * wb * wb > ww * bb ? (float)(-wb / ww) : 0.0f;
+  if (!(fabsf(s0f) <= 3.0e38f)) s0f = 0.0f;
+  const double s0 = s0f;
   const int n = blockIdx.x * 256 + tid;
   double a = 0.0, c = 0.0;
   for (int d = 0; d < ND_D; ++d) {
     const double wt = W[(size_t)n * ND_D + d];
     a += (wd[d] - wm) * wt;
-    c += (bd[d] - bm) * wt;
+    c += ((bd[d] - bm) + s0 * (wd[d] - wm)) * wt;
   }
   ac[n] = (float)a;
   ac[3 * ND_D + n] = (float)c;
   if (blockIdx.x == 0 && tid == 0) {
-    double ww = 0.0, wb = 0.0, bb = 0.0;
+    double wp = 0.0, pp = 0.0;
     for (int d = 0; d < ND_D; ++d) {
-      ww += (wd[d] - wm) * (wd[d] - wm);
-      wb += (wd[d] - wm) * (bd[d] - bm);
-      bb += (bd[d] - bm) * (bd[d] - bm);
+      const double bp = (bd[d] - bm) + s0 * (wd[d] - wm);
+      wp += (wd[d] - wm) * bp;
+      pp += bp * bp;
     }
     scal[0] = ww / ND_D;
-    scal[1] = wb / ND_D;
-    scal[2] = bb / ND_D;
+    scal[1] = wp / ND_D;
+    scal[2] = pp / ND_D;
+    scal[3] = s0;
   }
 }
 
@@ -96,6 +116,41 @@ hipError_t launch_embed_qkv_prep(const float* w_in, const float* b_in, const flo
                                  hipStream_t s) {
   hipLaunchKernelGGL(embed_qkv_prep_kernel, dim3(3), dim3(256), 0, s, w_in, b_in, nwqkv, ac, scal);
   return hipGetLastError();
+}
+
+hipError_t prepare_embed_qkv(const float* w_in, const float* b_in, const float* nwqkv, const float* nbqkv, float* ac,
+                             double* scal, float* coef, EmbedQkv* eq, hipStream_t s) {
+  if (!w_in || !b_in || !nwqkv || !nbqkv || !ac || !scal || !coef || !eq) return hipErrorInvalidValue;
+  hipError_t e;
+  if ((e = launch_embed_qkv_prep(w_in, b_in, nwqkv, ac, scal, s)) != hipSuccess) return e;
+  double m[4];
+  std::vector<float> h_ac(6 * ND_D), nb(3 * ND_D), h_coef(ND_H * 6);
+  if ((e = hipMemcpyAsync(m, scal, sizeof(m), hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(h_ac.data(), ac, h_ac.size() * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipMemcpyAsync(nb.data(), nbqkv, nb.size() * 4, hipMemcpyDeviceToHost, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  // per head h: alpha = k0 y + k1 r + k2, beta = k3 y + k4 r + k5 with
+  // k = (a_q, c_q, b_q) . (a_k | c_k) log2(e) / sqrt(32), in double
+  const int dh = ND_D / ND_H;
+  const double sc = 1.4426950408889634 / std::sqrt((double)dh);
+  for (int h = 0; h < ND_H; ++h) {
+    double k[6] = {0, 0, 0, 0, 0, 0};
+    for (int d = 0; d < dh; ++d) {
+      const int i = h * dh + d;
+      const double aq = h_ac[i], ak = h_ac[ND_D + i], cq = h_ac[3 * ND_D + i], ck = h_ac[4 * ND_D + i], bq = nb[i];
+      k[0] += aq * ak;
+      k[1] += cq * ak;
+      k[2] += bq * ak;
+      k[3] += aq * ck;
+      k[4] += cq * ck;
+      k[5] += bq * ck;
+    }
+    for (int j = 0; j < 6; ++j) h_coef[h * 6 + j] = (float)(k[j] * sc);
+  }
+  if ((e = hipMemcpyAsync(coef, h_coef.data(), h_coef.size() * 4, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
+  if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
+  *eq = EmbedQkv{.ac = ac, .bias = nbqkv, .mww = (float)m[0], .mwb = (float)m[1], .mbb = (float)m[2], .s0 = (float)m[3]};
+  return hipSuccess;
 }
 
 __global__ void __launch_bounds__(256)
@@ -571,9 +626,9 @@ enc_attention_rank2_kernel(R2Args A, int T) {
 #pragma unroll
   for (int j = 0; j < ENC_MAXT / 64; ++j) {
     const int u = 64 * j + lane;
-    const float s = sig[max(min(u, L - 1), 0)];
-    kr[j] = ln_rsqrt(fmaf(s, fmaf(s, eq.mww, 2.0f * eq.mwb), eq.mbb) + ND_LN_EPS);
-    ky[j] = s * kr[j];
+    const float s = sig[max(min(u, L - 1), 0)], sp = s - eq.s0;  // the mask reads the raw sample
+    kr[j] = ln_rsqrt(fmaf(sp, fmaf(sp, eq.mww, 2.0f * eq.mwb), eq.mbb) + ND_LN_EPS);
+    ky[j] = sp * kr[j];
     bal[j] = __ballot(u < L && s != 0.0f);
   }
   int n_um = 0;
@@ -582,7 +637,10 @@ enc_attention_rank2_kernel(R2Args A, int T) {
     if ((bal[j] >> lane) & 1ull) kyr[n_um + __popcll(bal[j] & ((1ull << lane) - 1ull))] = make_float2(ky[j], kr[j]);
     n_um += __popcll(bal[j]);
   }
-  if (n_um == 0 && lane == 0) kyr[0] = make_float2(0.0f, ln_rsqrt(eq.mbb + ND_LN_EPS));  // all masked: s = 0
+  if (n_um == 0 && lane == 0) {  // all masked: s = 0, s' = -s0
+    const float sp = -eq.s0, r0 = ln_rsqrt(fmaf(sp, fmaf(sp, eq.mww, 2.0f * eq.mwb), eq.mbb) + ND_LN_EPS);
+    kyr[0] = make_float2(sp * r0, r0);
+  }
   const int nk = n_um > 0 ? n_um : 1;
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's slab written (its own reads follow in order)
   // this thread's query t: its (y, r) is key t's, held by lane t % 64 as key slot t / 64

@@ -168,7 +168,9 @@ static int alloc_workspaces(nd_ctx* c) {
 //
 // Layer 0 runs in the rank-2 closed form (EmbedQkv, launch_enc_attention_rank2):
 // no q | k | v rows at all for layer 0 (encoder 3.65 -> 3.40 ms per 256-chunk
-// call).  Its LDS is exactly 64 KB: the round-3 layout (67,584 B, wave 7's
+// call), evaluated about the sample s0 where the row variance is least
+// (m.eq, prepared at finalize), which keeps it within fp32 rounding of the
+// materialised layer however w' and b' lie.  Its LDS is exactly 64 KB: the round-3 layout (67,584 B, wave 7's
 // E[y] / E[r] rows read and written past byte 65,536 by ds_read2 / ds_write2)
 // returned wrong chunks whenever another engine's decoder GEMMs shared the CU;
 // every layout whose accesses stay below 65,536 is clean (tools/r2_lds.sh,
@@ -181,7 +183,6 @@ static int alloc_workspaces(nd_ctx* c) {
 static hipError_t enqueue_encode_transformer(nd_ctx* c, int B, int T, hipStream_t s) {
   const Model& m = c->m;
   const int M = B * T, D = c->D, F = c->F;
-  const nd::EmbedQkv eq{.ac = m.eq_ac, .bias = m.enc[0].nbqkv, .mww = m.eq_m[0], .mwb = m.eq_m[1], .mbb = m.eq_m[2]};
   LCHK(nd::launch_enc_embed(c->sig, m.enc_lin_w, m.enc_lin_b, c->x, c->x_part, B, T, s));
   int pnx = 1, pny = 0;
   bool qkv_done = false;  // this layer's q | k | v already in c->big
@@ -189,7 +190,7 @@ static hipError_t enqueue_encode_transformer(nd_ctx* c, int B, int T, hipStream_
     const EncLayer& L = m.enc[li];
     // encoder/transformer.py:36-54
     if (li == 0) {
-      LCHK(nd::launch_enc_attention_rank2({.signal = c->sig, .span = c->span, .eq = eq, .coef = m.eq_coef,
+      LCHK(nd::launch_enc_attention_rank2({.signal = c->sig, .span = c->span, .eq = m.eq, .coef = m.eq_coef,
                                            .out = c->att}, B, T, s));
     } else {
       if (!qkv_done) LCHK(G(c->x, D, L.nwqkv, 3 * D, D, L.nbqkv, c->big, 3 * D, M).h3(c).ln(c->x_part, pnx).run(s));

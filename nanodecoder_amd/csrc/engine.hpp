@@ -125,10 +125,11 @@ struct Model {
   float *bank_ln_g = nullptr, *bank_ln_b = nullptr;
   std::vector<float> bank_dim_scale;
   // encoder layer 0's QKV in the rank-2 form (kernels.hpp EmbedQkv): a | c on
-  // the device, the three means on the host (kernel arguments); set at finalize
+  // the device, the three means and s0 on the host in eq (the kernel argument);
+  // set at finalize (nd::prepare_embed_qkv)
   float* eq_ac = nullptr;
   double* eq_scal = nullptr;
-  float eq_m[3] = {0.f, 0.f, 0.f};
+  nd::EmbedQkv eq;
   // layer 0's attention in the same closed form: per head the 6 coefficients
   // of alpha_t, beta_t (launch_enc_attention_rank2), on the device
   float* eq_coef = nullptr;

@@ -110,21 +110,29 @@ struct SrcMask {
 // ---- encoder -------------------------------------------------------------
 // Layer 0 of the Transformer encoder reads x = s w + b (Linear(1, d) of the
 // sample s): with w' = w - mean(w), b' = b - mean(b) its LayerNorm'd
-// projection is the rank-2 form
-//   LN(x) W'^T + b'' = (s a + c) / sqrt(s^2 m_ww + 2 s m_wb + m_bb + eps) + b''
-// a = W' w', c = W' b', m_.. the means of w'^2, w'b', b'^2 (W', b'': the
-// LN-folded QKV weight and bias), so the layer needs no QKV GEMM.
+// projection is the rank-2 form, written about the variance's minimum
+// s0 = -mean(w'b') / mean(w'^2) (rounded to fp32; 0 while cos^2(w', b') <=
+// 1/16, embed_qkv_prep_kernel), s' = s - s0, and b_perp = b' + s0 w' (so
+// s w' + b' = s' w' + b_perp exactly):
+//   LN(x) W'^T + b'' = (s' a + c) / sqrt(s'^2 m_ww + 2 s' m_wb + m_bb + eps) + b''
+// a = W' w', c = W' b_perp, m_.. the means of w'^2, w' b_perp (0 up to s0's
+// rounding), b_perp^2 (W', b'': the LN-folded QKV weight and bias), so the
+// layer needs no QKV GEMM.  About s = 0 instead (c = W' b', the means of b')
+// the variance's minimum m_bb - m_wb^2 / m_ww and then s a + c both cancel
+// when w' and b' are nearly collinear (tests/test_enc_layer0_scheme.py);
+// b_perp is orthogonal to w', so neither does here.
 struct EmbedQkv {
   const float* ac = nullptr;  // [2][768]: a, c
   const float* bias = nullptr;
   float mww = 0.f, mwb = 0.f, mbb = 0.f;
+  float s0 = 0.f;
   float* qkv = nullptr;       // unread (the rows are never materialised); keeps R2Args' kernel-argument layout
 };
 // Layer 0's attention in the same closed form: per head h the query, key
 // and value of position t are u_h y_t + v_h r_t + w_h (y = s r, r the LN
 // scale of the row), so a score is y_u alpha_t + r_u beta_t + (a constant
 // of t that cancels in the softmax) with alpha_t, beta_t linear in
-// (y_t, r_t, 1) (coef [8 heads][6], log2 units), and the output is
+// (y_t, r_t, 1) (coef [8 heads][6], log2 units; y = s' r), and the output is
 // a_v E[y] + c_v E[r] + b_v over the softmax: out [M, 256] row-major.
 struct R2Args {
   const float* signal = nullptr;
@@ -134,9 +142,14 @@ struct R2Args {
   float* out = nullptr;
 };
 hipError_t launch_enc_attention_rank2(const R2Args& a, int B, int T, hipStream_t s);
-// ac and the three means (double scal[3]) from the LN-folded weight [768, 256]
+// ac and the scalars (double scal[4]: the three means and s0) from the LN-folded weight [768, 256]
 hipError_t launch_embed_qkv_prep(const float* w_in, const float* b_in, const float* nwqkv, float* ac, double* scal,
                                  hipStream_t s);
+// Layer 0's whole load-time preparation, for nd_finalize and nd_op_enc_layer0 alike: the prep launch into ac
+// [6][256] and scal [4], the 48 coef values (computed in double on the host) into coef, all three on the device,
+// and *eq filled for launch_enc_attention_rank2.  Synchronises s.
+hipError_t prepare_embed_qkv(const float* w_in, const float* b_in, const float* nwqkv, const float* nbqkv, float* ac,
+                             double* scal, float* coef, EmbedQkv* eq, hipStream_t s);
 // x[b*T+t][:] = signal[b][t] * w_in + b_in (Linear(1, d)); part: full-row stats
 hipError_t launch_enc_embed(const float* signal, const float* w_in, const float* b_in, float* x, float* part, int B,
                             int T, hipStream_t s);

@@ -543,35 +543,11 @@ int nd_finalize(nd_ctx* c) {
     }
     if (c->cfg.encoder_type == ND_ENC_TRANSFORMER && !c->m.enc.empty()) {
       if (!c->m.eq_ac && dalloc(c, &c->m.eq_ac, (size_t)6 * D) != hipSuccess) return fail(ND_ERR_HIP, "alloc");
-      if (!c->m.eq_scal && dalloc(c, &c->m.eq_scal, 3) != hipSuccess) return fail(ND_ERR_HIP, "alloc");
-      HIPCHK(nd::launch_embed_qkv_prep(c->m.enc_lin_w, c->m.enc_lin_b, c->m.enc[0].nwqkv, c->m.eq_ac, c->m.eq_scal, c->es));
-      double m[3];
-      HIPCHK(hipMemcpyAsync(m, c->m.eq_scal, sizeof(m), hipMemcpyDeviceToHost, c->es));
-      HIPCHK(hipStreamSynchronize(c->es));
-      for (int i = 0; i < 3; ++i) c->m.eq_m[i] = (float)m[i];
-      // per head h: alpha = k0 y + k1 r + k2, beta = k3 y + k4 r + k5 with
-      // k = (a_q, c_q, b_q) . (a_k | c_k) log2(e) / sqrt(32), in double
-      std::vector<float> ac(6 * D), nb(3 * D), coef(ND_H * 6);
-      HIPCHK(hipMemcpyAsync(ac.data(), c->m.eq_ac, ac.size() * 4, hipMemcpyDeviceToHost, c->es));
-      HIPCHK(hipMemcpyAsync(nb.data(), c->m.enc[0].nbqkv, nb.size() * 4, hipMemcpyDeviceToHost, c->es));
-      HIPCHK(hipStreamSynchronize(c->es));
-      const double sc = 1.4426950408889634 / std::sqrt((double)(D / ND_H));
-      for (int h = 0; h < ND_H; ++h) {
-        double k[6] = {0, 0, 0, 0, 0, 0};
-        for (int d = 0; d < D / ND_H; ++d) {
-          const int i = h * (D / ND_H) + d;
-          const double aq = ac[i], ak = ac[D + i], cq = ac[3 * D + i], ck = ac[4 * D + i], bq = nb[i];
-          k[0] += aq * ak;
-          k[1] += cq * ak;
-          k[2] += bq * ak;
-          k[3] += aq * ck;
-          k[4] += cq * ck;
-          k[5] += bq * ck;
-        }
-        for (int j = 0; j < 6; ++j) coef[h * 6 + j] = (float)(k[j] * sc);
-      }
-      if (!c->m.eq_coef && dalloc(c, &c->m.eq_coef, coef.size()) != hipSuccess) return fail(ND_ERR_HIP, "alloc");
-      HIPCHK(hipMemcpy(c->m.eq_coef, coef.data(), coef.size() * 4, hipMemcpyHostToDevice));
+      if (!c->m.eq_scal && dalloc(c, &c->m.eq_scal, 4) != hipSuccess) return fail(ND_ERR_HIP, "alloc");
+      if (!c->m.eq_coef && dalloc(c, &c->m.eq_coef, (size_t)ND_H * 6) != hipSuccess) return fail(ND_ERR_HIP, "alloc");
+      // a | c, the means, s0 and the per-head coefficients of the closed form (attention.hip)
+      HIPCHK(nd::prepare_embed_qkv(c->m.enc_lin_w, c->m.enc_lin_b, c->m.enc[0].nwqkv, c->m.enc[0].nbqkv, c->m.eq_ac,
+                                   c->m.eq_scal, c->m.eq_coef, &c->m.eq, c->es));
     }
     if (c->m.nctxkv_w)
       HIPCHK(fold(c->m.ctxkv_w, c->m.ctxkv_b, c->m.enc_ln_g, c->m.enc_ln_b, c->m.nctxkv_w, c->m.nctxkv_b,

@@ -165,6 +165,31 @@ int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* sp
                                                            .T = T}, (hipStream_t)stream));
 }
 
+int nd_op_enc_layer0(const float* signal, const int32_t* span, const float* w_in, const float* b_in,
+                     const float* nwqkv, const float* nbqkv, float* out, int32_t B, int32_t T, float* ac_out,
+                     double* scal_out, float* coef_out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!signal || !span || !w_in || !b_in || !nwqkv || !nbqkv || !out || B < 1 || T < 1 || T > 512)
+    return status("enc_layer0", hipErrorInvalidValue);  // launch_enc_attention_rank2's limit, checked before the prep launch
+  // the engine's own preparation (nd_finalize's) into a workspace of this call
+  const size_t n_ac = 6 * ND_D, n_coef = ND_H * 6;
+  char* ws = nullptr;
+  hipError_t e = hipMalloc((void**)&ws, 4 * sizeof(double) + (n_ac + n_coef) * sizeof(float));
+  if (e != hipSuccess) return status("enc_layer0", e, ND_ERR_HIP);
+  double* scal = reinterpret_cast<double*>(ws);
+  float *ac = reinterpret_cast<float*>(scal + 4), *coef = ac + n_ac;
+  nd::EmbedQkv eq;
+  e = nd::prepare_embed_qkv(w_in, b_in, nwqkv, nbqkv, ac, scal, coef, &eq, s);
+  if (e == hipSuccess) e = nd::launch_enc_attention_rank2({.signal = signal, .span = span, .eq = eq, .coef = coef,
+                                                           .out = out}, B, T, s);
+  if (e == hipSuccess && ac_out) e = hipMemcpyAsync(ac_out, ac, n_ac * sizeof(float), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && scal_out) e = hipMemcpyAsync(scal_out, scal, 4 * sizeof(double), hipMemcpyDeviceToDevice, s);
+  if (e == hipSuccess && coef_out) e = hipMemcpyAsync(coef_out, coef, n_coef * sizeof(float), hipMemcpyDeviceToDevice, s);
+  const hipError_t es = hipStreamSynchronize(s);  // the workspace is read until here
+  (void)hipFree(ws);
+  return status("enc_layer0", e != hipSuccess ? e : es, ND_ERR_HIP);
+}
+
 int nd_op_dec_self_attention(const float* qkv, float* cache, const int32_t* anc, int32_t anc_ld, int32_t step,
                              int32_t max_steps, float* out, int32_t R, void* stream) {
   return status("dec_self_attention",

@@ -595,6 +595,27 @@ def op_enc_attention(qkv: torch.Tensor, signal: torch.Tensor, span: torch.Tensor
     return out
 
 
+def op_enc_layer0(signal: torch.Tensor, span: torch.Tensor, w_in: torch.Tensor, b_in: torch.Tensor,
+                  wqkv: torch.Tensor, bqkv: torch.Tensor, ln_g: torch.Tensor, ln_b: torch.Tensor, fill: float = 0.0,
+                  guard_rows: int = 0):
+    """Encoder layer 0 up to W_o in the engine's closed form (nd_op_enc_layer0), the LayerNorm affine folded
+    first (nd_op_fold_layernorm) as the engine does.  Returns (out [B*T + guard_rows, 256] pre-filled with
+    `fill`, prep) with prep = dict(ac [6*256] f32, scal [4] f64: m_ww, m_wb, m_bb, s0; coef [48] f32)."""
+    B, T = signal.shape
+    dev = signal.device
+    nw, nb = op_fold_layernorm(wqkv, bqkv, ln_g, ln_b)
+    out = torch.full((B * T + guard_rows, 256), fill, dtype=torch.float32, device=dev)
+    ac = torch.zeros(6 * 256, dtype=torch.float32, device=dev)
+    scal = torch.zeros(4, dtype=torch.float64, device=dev)
+    coef = torch.zeros(48, dtype=torch.float32, device=dev)
+    span = span.to(torch.int32)
+    s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    _lib.check(_lib.lib().nd_op_enc_layer0(_ptr(signal), _ptr(span), _ptr(w_in), _ptr(b_in), _ptr(nw),
+                                           _ptr(nb), _ptr(out), B, T, _ptr(ac), _ptr(scal), _ptr(coef), s),
+               "nd_op_enc_layer0")
+    return out, dict(ac=ac, scal=scal, coef=coef)
+
+
 def pack_p16(x: torch.Tensor) -> torch.Tensor:
     """Row-major [M, N] -> the engine's P16 layout (include/nanodec.h,
     nd_op_gemm_p16), rows zero-padded to a multiple of 16.  Returned flat

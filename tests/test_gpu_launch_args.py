@@ -1,4 +1,4 @@
-"""Decoder attention, FFN, P16 GEMM and encoder attention op entries whose refusal comes from the launcher, most
+"""Decoder attention, FFN, P16 GEMM, encoder attention and encoder layer-0 op entries whose refusal comes from the launcher, most
 of them after the kernel attributes are set (needs an MI355X): each returns ND_ERR_ARG and launches nothing
 (the output keeps its sentinel)."""
 import ctypes
@@ -123,3 +123,20 @@ def test_enc_attention_refuses_long_chunk(bufs):
     b = bufs
     rc = _lib.lib().nd_op_enc_attention(_p(b["bank"]), _p(b["signal"]), _p(b["span"]), _p(b["out"]), C, 513, None)
     _refused(b, rc, b"enc_attention")
+
+
+@pytest.mark.parametrize("t,null", [(513, None), (0, None), (-1, None), (T, "signal"), (T, "span"), (T, "w_in"),
+                                    (T, "b_in"), (T, "nwqkv"), (T, "nbqkv"), (T, "out")])
+def test_enc_layer0_refuses(bufs, t, null):
+    """T outside 1..512 or a null input: refused before the preparation's launch (nothing written)."""
+    b = bufs
+    a = dict(signal=_p(b["signal"]), span=_p(b["span"]), w_in=_p(b["q"]), b_in=_p(b["q"]), nwqkv=_p(b["bank"]),
+             nbqkv=_p(b["q"]), out=_p(b["out"]))
+    if null:
+        a[null] = None
+    prep = torch.full((6 * 256 + 48,), -7.25, dtype=torch.float32, device=b["out"].device)
+    scal = torch.full((4,), -7.25, dtype=torch.float64, device=b["out"].device)
+    rc = _lib.lib().nd_op_enc_layer0(a["signal"], a["span"], a["w_in"], a["b_in"], a["nwqkv"], a["nbqkv"], a["out"],
+                                     C, t, _p(prep), _p(scal), ctypes.c_void_p(prep.data_ptr() + 6 * 256 * 4), None)
+    _refused(b, rc, b"enc_layer0")
+    assert bool((prep == -7.25).all()) and bool((scal == -7.25).all())

@@ -1292,6 +1292,40 @@ def test_transformer_encoder_vs_oracle_masks():
         assert np.abs(mem[i, :L] - exp_mem[i, :L]).max() < 1e-4, i
 
 
+@pytest.mark.parametrize("exact", [False, True])
+def test_transformer_encoder_vs_oracle_collinear_embedding(exact):
+    """The same comparison where layer 0's closed form is worst conditioned:
+    the embedding's bias replaced so that cos(w', b') = 0.9999, and a third of
+    every chunk's samples within +-0.05 of s0 = -m_wb / m_ww (the variance's
+    minimum; tests/test_enc_layer0_scheme.py), on the default path and in
+    exact fp32; a masked chunk and a ragged span among them."""
+    from tests import enc_layer0_util as U
+    ref = _oracle()
+    cfg = synth.ModelConfig()
+    W = dict(synth.make_weights(cfg, seed=21))
+    w = W["encoder.linear.weight"]
+    W["encoder.linear.bias"] = (U.collinear_bias(w, 0.9999, np.random.default_rng(3)) + 0.02).astype(np.float32)
+    got_cos, s0 = U.measured_cos_s0(dict(w_in=w.reshape(-1), b_in=W["encoder.linear.bias"]))
+    assert abs(got_cos - 0.9999) < 1e-7
+    B, T = 4, 512
+    sig = U.clustered_signal(B, T, s0, seed=17)
+    lens = np.full(B, T, np.int32)
+    spans = np.full(B, T, np.int32)
+    sig[1, ::7] = 0.0
+    lens[2], spans[2] = 300, 300
+    sig[2, 300:] = 0.0
+    eng = _engine(cfg, W, max_batch=B, max_steps=10)
+    eng.set_exact_fp32(exact)
+    mem = eng.encode(sig, lens, spans).cpu().numpy()
+    eng.close()
+    exp_mem = ref.RefModel(cfg, W).encode(torch.from_numpy(sig), lens).numpy()
+    for i in range(B):
+        L = spans[i]
+        err = np.abs(mem[i, :L] - exp_mem[i, :L]).max()
+        print(f"collinear embedding exact={exact} chunk {i}: err {err:.3e}")
+        assert err < 1e-4, i
+
+
 def test_nano_greedy_vs_oracle_ragged():
     """NanoEncoder packing: ragged lengths inside one batch (reverse LSTM
     starts at len-1), B not a multiple of the 16-sequence LSTM group."""
