@@ -754,6 +754,111 @@ int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldk
                        const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
                        int32_t Lk, int32_t causal, void* stream);
 
+/* ---- output head and search, one launch per call ------------------------
+ * The kernels that turn log-probs into output (search.hip, head.hpp), each on
+ * the caller's stream with caller-owned buffers, for op-level tests against a
+ * scripted model.  Decoder rows x and the next step's input ne_x are P16
+ * [R16, 256] (R16 = rows rounded up to 16; nd_op_pack_p16); ne_part holds
+ * R16 * 32 floats (each row's {mean, M2} at ne_part[row * 32]); ne_tok
+ * (nullable) [rows] i32.  The head: ln_g / ln_b [256] (LayerNorm, eps 1e-6),
+ * gw [V, 256] / gb [V] (generator), log_softmax; emb [V, 256], pe (nullable:
+ * no position encoding and no sqrt(d) scale) [>= S, 256].  A null buffer, a
+ * step outside [0, S), eos outside [0, V) or a count below 1 returns
+ * ND_ERR_ARG "<entry>: bad arguments" before any HIP call; the launchers'
+ * own refusals (named per entry below) follow, also before any launch. */
+
+/* The search state of the beam kernels (kernels.hpp BeamState, member for
+ * member; the classic Beam's members may be null for the --fast beam, cov /
+ * pen / prev_pen / attn / cut without a coverage penalty, blk without n-gram
+ * blocking).  C chunks of beam rows, row = c * beam + j. */
+typedef struct nd_beam_state {
+  float* cum;          /* [C, beam] */
+  int32_t* seq[2];     /* [C*beam, S] double buffered: step s reads [s & 1], writes the other */
+  int32_t* anc[2];     /* [C*beam, S] */
+  int32_t* tok;        /* [C*beam] */
+  int32_t* done;       /* [C] */
+  int32_t* top_fin;    /* [C] */
+  int32_t* n_hyp;      /* [C] */
+  float* hyp_score;    /* [C, n_best] */
+  int32_t* hyp_len;    /* [C, n_best] */
+  int32_t* hyp_tok;    /* [C, n_best, S] */
+  int32_t* n_alive;    /* [1] */
+  int32_t* steps_done; /* [1] */
+  int32_t* group;      /* [C] classic */
+  int32_t* grp_left;   /* [C] classic */
+  int32_t* grp_done;   /* [C] classic: 0 alive, else 1 + the step the batch finished in */
+  int32_t* steps_run;  /* [C] */
+  int32_t* hyp_anc;    /* [C, n_best, S] */
+  float* cov[2];       /* [C*beam, T] */
+  float* pen;          /* [C*beam] */
+  float* prev_pen;     /* [C*beam] */
+  int32_t* blk[2];     /* [C*beam] */
+  const float* attn;   /* [C*beam, S, T] */
+  const int32_t* cut;  /* [C] */
+  int32_t T;
+} nd_beam_state;
+
+/* One greedy head launch over R rows for `step` (translate/translator.py:
+ * 371-394, 455-483; models/model_builder.py:326-334): tok [R], out_tokens
+ * [R, S] (column step written), score [R], logp (nullable) [R, S, V] (row
+ * [r][step] written, before the min_len mask), and for step + 1 < S the next
+ * input rows ne_x / ne_part / ne_tok (embeddings.py:189-207).  d_seed
+ * (nullable, a device word): random sampling with temp and topk (-1: the
+ * whole distribution) from the counter-based generator of nd_translate_sample.
+ * Refused ("greedy_head: "): V outside [1, 32]; with d_seed, temp == 0,
+ * topk == 1 or topk > V. */
+int nd_op_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb, int32_t V,
+                      int32_t S, int32_t step, int32_t min_len, int32_t eos, int32_t R, const float* emb,
+                      const float* pe, float* ne_x, float* ne_part, int32_t* ne_tok, int32_t* tok,
+                      int32_t* out_tokens, float* score, float* logp, float temp, int32_t topk,
+                      const uint64_t* d_seed, void* stream);
+
+/* The --fast beam (translate/translator.py:619-825), no reference equivalent
+ * as separate calls: init (:691-693), one step (:701-823: head, length
+ * penalty ((5 + step + 1) / 6) ** alpha as the engine computes it, top-beam,
+ * reorder, finished-hypothesis bookkeeping, next input rows), finish (tokens
+ * [C, n_best, S] -1 padded, scores and lens [C, n_best]).  clist (nullable):
+ * the step runs the ccap listed chunks only (-1 = none).  Refused
+ * ("beam_step: "): V outside [1, 32], beam outside [1, 8], beam * V > 256,
+ * n_best outside [1, beam], ccap outside [1, C]. */
+int nd_op_beam_init(const nd_beam_state* st, int32_t C, int32_t beam, int32_t bos, void* stream);
+int nd_op_beam_step(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb, int32_t V,
+                    const float* emb, const float* pe, float* ne_x, float* ne_part, int32_t* ne_tok,
+                    const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best, int32_t step, int32_t S,
+                    int32_t min_len, int32_t eos, float alpha, const int32_t* clist, int32_t ccap, void* stream);
+int nd_op_beam_finish(const nd_beam_state* st, int32_t C, int32_t n_best, int32_t S, int32_t* tokens, float* scores,
+                      int32_t* lens, void* stream);
+
+/* The classic onmt Beam (translate/translator.py:827-926, onmt/translate/
+ * beam.py:6-243): init (group [C]: each chunk's reference batch), one step
+ * (Beam.advance for every chunk of a batch still alive, st->attn / cut / T
+ * read by the coverage penalties), finish (sort_finished(minimum = n_best)).
+ * Refused ("beam_classic_step: "): as beam_step, and V < beam, a coverage
+ * penalty without st->attn / cut / cov, n-gram blocking without st->blk;
+ * ("beam_classic_finish: ") n_best > beam. */
+int nd_op_beam_classic_init(const nd_beam_state* st, const int32_t* group, int32_t C, int32_t beam, int32_t bos,
+                            void* stream);
+int nd_op_beam_classic_step(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
+                            int32_t V, const float* emb, const float* pe, float* ne_x, float* ne_part,
+                            int32_t* ne_tok, const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best,
+                            int32_t step, int32_t S, int32_t min_len, int32_t eos, const nd_classic_opts* opts,
+                            void* stream);
+int nd_op_beam_classic_finish(const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best, int32_t S,
+                              const nd_classic_opts* opts, int32_t* tokens, float* scores, int32_t* lens,
+                              void* stream);
+
+/* -attn_debug / coverage capture.  nd_op_attn_step_softmax: in place, row r
+ * of R (chunk r / rpc) at a[r * ld + t]: softmax over keys t < min(span[chunk],
+ * T), zero for the other t < T (multi_headed_attn.py:175).
+ * nd_op_beam_attn_gather: out [C, n_best, max_len, T], row t of hypothesis k =
+ * st->attn[hyp_anc[c][k][t]][t][0 .. T) for t < hyp_len[c][k], zero after
+ * (translate/translator.py:745-751); refused when st->attn is null,
+ * T > st->T or max_len > S. */
+int nd_op_attn_step_softmax(float* a, int64_t ld, const int32_t* span, int32_t R, int32_t rpc, int32_t T,
+                            void* stream);
+int nd_op_beam_attn_gather(const nd_beam_state* st, int32_t C, int32_t n_best, int32_t S, int32_t max_len, int32_t T,
+                           float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -40,6 +40,19 @@ _P = ctypes.c_void_p
 _I = ctypes.c_int32
 _F = ctypes.c_float
 
+
+class NdBeamState(ctypes.Structure):
+    """include/nanodec.h nd_beam_state (device pointers; the [2] members are double buffers)."""
+    _fields_ = [("cum", _P), ("seq", _P * 2), ("anc", _P * 2), ("tok", _P), ("done", _P), ("top_fin", _P),
+                ("n_hyp", _P), ("hyp_score", _P), ("hyp_len", _P), ("hyp_tok", _P), ("n_alive", _P),
+                ("steps_done", _P), ("group", _P), ("grp_left", _P), ("grp_done", _P), ("steps_run", _P),
+                ("hyp_anc", _P), ("cov", _P * 2), ("pen", _P), ("prev_pen", _P), ("blk", _P * 2), ("attn", _P),
+                ("cut", _P), ("T", _I)]
+
+
+_BS = ctypes.POINTER(NdBeamState)
+_CO = ctypes.POINTER(NdClassicOpts)
+
 # name -> (restype, argtypes); every symbol include/nanodec.h declares
 SIGNATURES = {
     "nd_create": (_I, [ctypes.POINTER(NdConfig), ctypes.POINTER(_P)]),
@@ -119,6 +132,18 @@ SIGNATURES = {
     "nd_op_dec_ctx_attention_q24": (_I, [_P, _P, _I, _I, _P, _P, _F, _P, _I, _I, _I, _P]),
     "nd_op_alive_list": (_I, [_P, _I, _P, _I, _P, _P]),
     "nd_op_dec_ctx_attention_list": (_I, [_P, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _I, _P, _I, _I, _P, _P, _P]),
+    "nd_op_greedy_head": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I,
+                               _P, _P]),
+    "nd_op_beam_init": (_I, [_BS, _I, _I, _I, _P]),
+    "nd_op_beam_step": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _BS, _I, _I, _I, _I, _I, _I, _I, _F, _P, _I,
+                             _P]),
+    "nd_op_beam_finish": (_I, [_BS, _I, _I, _I, _P, _P, _P, _P]),
+    "nd_op_beam_classic_init": (_I, [_BS, _P, _I, _I, _I, _P]),
+    "nd_op_beam_classic_step": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _BS, _I, _I, _I, _I, _I, _I, _I, _CO,
+                                     _P]),
+    "nd_op_beam_classic_finish": (_I, [_BS, _I, _I, _I, _I, _CO, _P, _P, _P, _P]),
+    "nd_op_attn_step_softmax": (_I, [_P, ctypes.c_int64, _P, _I, _I, _I, _P]),
+    "nd_op_beam_attn_gather": (_I, [_BS, _I, _I, _I, _I, _I, _P, _P]),
 }
 
 _lib = None

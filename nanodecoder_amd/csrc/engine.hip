@@ -556,8 +556,7 @@ static hipError_t enqueue_beam_steps(nd_ctx* c, int B, int T, int beam, int n_be
   for (int step = s0; step < s1; ++step) {
     LCHK(enqueue_dec_step(c, bc.rows, T, step, {.anc = c->bs.anc[step & 1], .anc_ld = S}, s));
     LCHK(enqueue_attn_step(c, B, beam, T, step, s));
-    const float lenpen = (float)std::pow((5.0 + (step + 1)) / 6.0, (double)alpha);
-    LCHK(nd::launch_beam_step(next_embed(c), generator(c, c->dx), st, bc, step, lenpen, s));
+    LCHK(nd::launch_beam_step(next_embed(c), generator(c, c->dx), st, bc, step, nd::fast_beam_lenpen(step, alpha), s));
   }
   return hipSuccess;
 }

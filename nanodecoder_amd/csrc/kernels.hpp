@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cmath>
+
 namespace nd {
 
 struct GemmArgs {
@@ -500,7 +502,7 @@ struct BeamState {
   // every one of them is done
   int* group;        // [C] reference batch id
   int* grp_left;     // [C] chunks of the batch not done yet
-  int* grp_done;     // [C] batch finished (its beams stop advancing)
+  int* grp_done;     // [C] 0 while the batch is alive, else 1 + the step it finished in (its beams run that step, none after)
   int* steps_run;    // [C] advance() calls made on the chunk's beam (--fast: the step count when it was dropped)
   int* hyp_anc;      // [C, n_best, S] decoder row that ran each step of the hypothesis (its attention rows)
   // classic Beam: GNMTGlobalScorer state (onmt/translate/beam.py:181-243) and n-gram blocking (:100-119)
@@ -537,6 +539,12 @@ struct BeamCall {
   int n_best = 1, S = 0, min_len = 0, eos = 0;
 };
 hipError_t launch_beam_init(const BeamState& st, int C, int beam, int bos, hipStream_t s);
+// the --fast beam's length penalty of a step (translate/translator.py:718-720: ((5 + step + 1) / 6) ** alpha, a
+// Python float the reference's division rounds to fp32): launch_beam_step's lenpen, for the engine and
+// nd_op_beam_step alike
+inline float fast_beam_lenpen(int step, float alpha) {
+  return (float)std::pow((5.0 + (step + 1)) / 6.0, (double)alpha);
+}
 hipError_t launch_beam_step(const NextEmbed& ne, const Generator& g, const BeamState& st, const BeamCall& b, int step,
                             float lenpen, hipStream_t s);
 hipError_t launch_beam_finish(const BeamState& st, int C, int n_best, int S, int* tokens, float* scores, int* lens,

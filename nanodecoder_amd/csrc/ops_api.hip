@@ -451,3 +451,145 @@ int nd_op_dec_ctx_attention_q24(const float* q, const void* kvq, int32_t layers,
                                               .out = out, .mask = {signal, span, pad_val},
                                               .rows = {.C = C, .rpc = rpc}}, (hipStream_t)stream));
 }
+
+// ---- output head and search (search.hip, head.hpp), one launch per call ----
+static nd::BeamState beam_state(const nd_beam_state& a) {
+  nd::BeamState st{};
+  st.cum = a.cum;
+  for (int i = 0; i < 2; ++i) {
+    st.seq[i] = a.seq[i];
+    st.anc[i] = a.anc[i];
+    st.cov[i] = a.cov[i];
+    st.blk[i] = a.blk[i];
+  }
+  st.tok = a.tok;
+  st.done = a.done;
+  st.top_fin = a.top_fin;
+  st.n_hyp = a.n_hyp;
+  st.hyp_score = a.hyp_score;
+  st.hyp_len = a.hyp_len;
+  st.hyp_tok = a.hyp_tok;
+  st.n_alive = a.n_alive;
+  st.steps_done = a.steps_done;
+  st.group = a.group;
+  st.grp_left = a.grp_left;
+  st.grp_done = a.grp_done;
+  st.steps_run = a.steps_run;
+  st.hyp_anc = a.hyp_anc;
+  st.pen = a.pen;
+  st.prev_pen = a.prev_pen;
+  st.attn = a.attn;
+  st.cut = a.cut;
+  st.T = a.T;
+  return st;
+}
+// the members every beam kernel touches
+static bool beam_state_ok(const nd_beam_state* a) {
+  return a && a->cum && a->seq[0] && a->seq[1] && a->anc[0] && a->anc[1] && a->tok && a->done && a->top_fin &&
+         a->n_hyp && a->hyp_score && a->hyp_len && a->hyp_tok && a->hyp_anc && a->n_alive && a->steps_done &&
+         a->steps_run;
+}
+static bool classic_state_ok(const nd_beam_state* a) {
+  return beam_state_ok(a) && a->group && a->grp_left && a->grp_done;
+}
+static nd::ClassicOpts classic_opts(const nd_classic_opts& op) {
+  return {op.length_penalty, op.alpha, op.beta, op.coverage_penalty, op.stepwise_penalty, op.block_ngram_repeat,
+          op.ignore_mask};
+}
+static bool classic_opts_ok(const nd_classic_opts* op) {
+  return op && op->length_penalty >= 0 && op->length_penalty <= 2 && op->coverage_penalty >= 0 &&
+         op->coverage_penalty <= 2;
+}
+
+int nd_op_greedy_head(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb, int32_t V,
+                      int32_t S, int32_t step, int32_t min_len, int32_t eos, int32_t R, const float* emb,
+                      const float* pe, float* ne_x, float* ne_part, int32_t* ne_tok, int32_t* tok,
+                      int32_t* out_tokens, float* score, float* logp, float temp, int32_t topk,
+                      const uint64_t* d_seed, void* stream) {
+  if (!x || !ln_g || !ln_b || !gw || !gb || !emb || !ne_x || !ne_part || !tok || !out_tokens || !score || R < 1 ||
+      S < 1 || step < 0 || step >= S || eos < 0 || (V >= 1 && eos >= V))
+    return fail(ND_ERR_ARG, "greedy_head: bad arguments");
+  const nd::GreedyHead h{.x = x, .ln_g = ln_g, .ln_b = ln_b, .gw = gw, .gb = gb, .V = V, .S = S, .min_len = min_len,
+                         .eos = eos, .tok = tok, .out_tokens = out_tokens, .score = score, .logp_dump = logp,
+                         .ne = {.emb = emb, .pe = pe, .x = ne_x, .part = ne_part, .tok = ne_tok},
+                         .smp = {.temp = temp, .topk = topk,
+                                 .seed = reinterpret_cast<const unsigned long long*>(d_seed)}};
+  return status("greedy_head", nd::launch_dec_greedy_head(h, step, R, (hipStream_t)stream));
+}
+
+int nd_op_beam_init(const nd_beam_state* st, int32_t C, int32_t beam, int32_t bos, void* stream) {
+  if (!beam_state_ok(st) || C < 1 || beam < 1 || beam > 8) return fail(ND_ERR_ARG, "beam_init: bad arguments");
+  return status("beam_init", nd::launch_beam_init(beam_state(*st), C, beam, bos, (hipStream_t)stream));
+}
+
+int nd_op_beam_step(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb, int32_t V,
+                    const float* emb, const float* pe, float* ne_x, float* ne_part, int32_t* ne_tok,
+                    const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best, int32_t step, int32_t S,
+                    int32_t min_len, int32_t eos, float alpha, const int32_t* clist, int32_t ccap, void* stream) {
+  if (!x || !ln_g || !ln_b || !gw || !gb || !emb || !ne_x || !ne_part || !beam_state_ok(st) || C < 1 || S < 1 ||
+      step < 0 || step >= S || eos < 0 || (V >= 1 && eos >= V))
+    return fail(ND_ERR_ARG, "beam_step: bad arguments");
+  const nd::BeamCall bc{.rows = {.C = C, .rpc = beam, .clist = clist, .ccap = ccap}, .n_best = n_best, .S = S,
+                        .min_len = min_len, .eos = eos};
+  return status("beam_step",
+                nd::launch_beam_step({.emb = emb, .pe = pe, .x = ne_x, .part = ne_part, .tok = ne_tok},
+                                     {.x = x, .ln_g = ln_g, .ln_b = ln_b, .gw = gw, .gb = gb, .V = V},
+                                     beam_state(*st), bc, step, nd::fast_beam_lenpen(step, alpha),
+                                     (hipStream_t)stream));
+}
+
+int nd_op_beam_finish(const nd_beam_state* st, int32_t C, int32_t n_best, int32_t S, int32_t* tokens, float* scores,
+                      int32_t* lens, void* stream) {
+  if (!beam_state_ok(st) || !tokens || !scores || !lens || C < 1 || n_best < 1 || S < 1)
+    return fail(ND_ERR_ARG, "beam_finish: bad arguments");
+  return status("beam_finish",
+                nd::launch_beam_finish(beam_state(*st), C, n_best, S, tokens, scores, lens, (hipStream_t)stream));
+}
+
+int nd_op_beam_classic_init(const nd_beam_state* st, const int32_t* group, int32_t C, int32_t beam, int32_t bos,
+                            void* stream) {
+  if (!classic_state_ok(st) || !group || C < 1 || beam < 1 || beam > 8)
+    return fail(ND_ERR_ARG, "beam_classic_init: bad arguments");
+  return status("beam_classic_init",
+                nd::launch_beam_classic_init(beam_state(*st), group, C, beam, bos, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_op_beam_classic_step(const float* x, const float* ln_g, const float* ln_b, const float* gw, const float* gb,
+                            int32_t V, const float* emb, const float* pe, float* ne_x, float* ne_part,
+                            int32_t* ne_tok, const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best,
+                            int32_t step, int32_t S, int32_t min_len, int32_t eos, const nd_classic_opts* opts,
+                            void* stream) {
+  if (!x || !ln_g || !ln_b || !gw || !gb || !emb || !ne_x || !ne_part || !classic_state_ok(st) ||
+      !classic_opts_ok(opts) || C < 1 || S < 1 || step < 0 || step >= S || eos < 0 || (V >= 1 && eos >= V))
+    return fail(ND_ERR_ARG, "beam_classic_step: bad arguments");
+  const nd::BeamCall bc{.rows = {.C = C, .rpc = beam}, .n_best = n_best, .S = S, .min_len = min_len, .eos = eos};
+  return status("beam_classic_step",
+                nd::launch_beam_classic_step({.emb = emb, .pe = pe, .x = ne_x, .part = ne_part, .tok = ne_tok},
+                                             {.x = x, .ln_g = ln_g, .ln_b = ln_b, .gw = gw, .gb = gb, .V = V},
+                                             beam_state(*st), bc, step, classic_opts(*opts), (hipStream_t)stream));
+}
+
+int nd_op_beam_classic_finish(const nd_beam_state* st, int32_t C, int32_t beam, int32_t n_best, int32_t S,
+                              const nd_classic_opts* opts, int32_t* tokens, float* scores, int32_t* lens,
+                              void* stream) {
+  if (!classic_state_ok(st) || !classic_opts_ok(opts) || !tokens || !scores || !lens || C < 1 || beam < 1 ||
+      beam > 8 || n_best < 1 || S < 1)
+    return fail(ND_ERR_ARG, "beam_classic_finish: bad arguments");
+  return status("beam_classic_finish",
+                nd::launch_beam_classic_finish(beam_state(*st), C, beam, n_best, S, classic_opts(*opts), tokens,
+                                               scores, lens, (hipStream_t)stream));
+}
+
+int nd_op_attn_step_softmax(float* a, int64_t ld, const int32_t* span, int32_t R, int32_t rpc, int32_t T,
+                            void* stream) {
+  if (!a || !span || ld < T) return fail(ND_ERR_ARG, "attn_step_softmax: bad arguments");
+  return status("attn_step_softmax", nd::launch_attn_step_softmax(a, (size_t)ld, span, R, rpc, T, (hipStream_t)stream));
+}
+
+int nd_op_beam_attn_gather(const nd_beam_state* st, int32_t C, int32_t n_best, int32_t S, int32_t max_len, int32_t T,
+                           float* out, void* stream) {
+  if (!st || !st->hyp_len || !st->hyp_anc || !out || C < 1 || n_best < 1 || S < 1 || max_len < 0 || T < 1)
+    return fail(ND_ERR_ARG, "beam_attn_gather: bad arguments");
+  return status("beam_attn_gather",
+                nd::launch_beam_attn_gather(beam_state(*st), C, n_best, S, max_len, T, out, (hipStream_t)stream));
+}

@@ -180,7 +180,9 @@ hipError_t launch_beam_step(const NextEmbed& ne, const Generator& g, const BeamS
                             float lenpen, hipStream_t s) {
   const int beam = b.rows.rpc, C = b.rows.C, V = g.V, ccap = b.rows.ccap;
   const int* clist = b.rows.clist;
-  if (beam > BEAM_MAX || beam * V > 256 || V > ND_MAXV || !ne.emb || !ne.x || !ne.part) return hipErrorInvalidValue;
+  if (beam < 1 || beam > BEAM_MAX || beam * V > 256 || V < 1 || V > ND_MAXV || !ne.emb || !ne.x || !ne.part)
+    return hipErrorInvalidValue;
+  if (b.n_best < 1 || b.n_best > beam) return hipErrorInvalidValue;
   if (clist && (ccap < 1 || ccap > C)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_step_kernel, dim3(clist ? ccap : C), dim3(256), 0, s, ne, g.x, g.ln_g, g.ln_b, g.gw, g.gb, V,
                      st, beam, b.n_best, step, b.S, b.min_len, b.eos, lenpen, clist);
@@ -321,7 +323,11 @@ beam_classic_step_kernel(NextEmbed ne, const float* __restrict__ x, const float*
   __shared__ int fin[BEAM_MAX];
   const int c = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
   const int g = st.group[c];
-  if (st.grp_done[g]) return;  // translator.py:884-885: the whole batch is done
+  // translator.py:884-908: a batch advances every one of its beams in a step and only then tests all(done), so a
+  // chunk done earlier still runs the step in which its batch's last chunk finishes (grp_done = that step + 1,
+  // written during this launch by another workgroup), and no step after it
+  const int gd = st.grp_done[g];
+  if (gd > 0 && gd <= step) return;
   const int cur = step & 1, nxt = cur ^ 1;
   const int row0 = c * beam;
   const bool cov_on = o.cov_kind != 0 && st.attn;
@@ -456,7 +462,7 @@ beam_classic_step_kernel(NextEmbed ne, const float* __restrict__ x, const float*
     if (!st.done[c] && st.top_fin[c] && st.n_hyp[c] >= n_best) {  // done() (:146-147)
       st.done[c] = 1;
       if (atomicSub(&st.grp_left[g], 1) == 1) {
-        st.grp_done[g] = 1;
+        st.grp_done[g] = step + 1;
         if (atomicSub(st.n_alive, 1) == 1) *st.steps_done = step + 1;
       }
     }
@@ -467,8 +473,9 @@ hipError_t launch_beam_classic_step(const NextEmbed& ne, const Generator& g, con
                                     int step, const ClassicOpts& o, hipStream_t s) {
   const int beam = b.rows.rpc, V = g.V, S = b.S;
   if (b.rows.done || b.rows.clist) return hipErrorInvalidValue;  // the --fast beam's
-  if (beam > BEAM_MAX || beam * V > 256 || V > ND_MAXV || V < beam || !ne.emb || !ne.x || !ne.part)
+  if (beam < 1 || beam > BEAM_MAX || beam * V > 256 || V > ND_MAXV || V < beam || !ne.emb || !ne.x || !ne.part)
     return hipErrorInvalidValue;
+  if (b.n_best < 1 || b.n_best > beam) return hipErrorInvalidValue;
   if (o.cov_kind != 0 && (!st.attn || !st.cut || !st.cov[0] || !st.cov[1])) return hipErrorInvalidValue;
   if (o.ngram < 0 || o.ngram > S || (o.ngram > 0 && (!st.blk[0] || !st.blk[1]))) return hipErrorInvalidValue;
   hipLaunchKernelGGL(beam_classic_step_kernel, dim3(b.rows.C), dim3(256), 0, s, ne, g.x, g.ln_g, g.ln_b, g.gw, g.gb, V,

@@ -993,6 +993,157 @@ def op_lstm_layer(whh, lens, T, xp=None, signal=None, wih0=None, bsum=None, bn_s
     return out
 
 
+# ---- output head and search, one launch per call (include/nanodec.h nd_op_greedy_head .. nd_op_beam_attn_gather)
+class SearchHead:
+    """The output head's weights and the embedding on the device: ln_g / ln_b [256], gw [V, 256], gb [V],
+    emb [V, 256], pe (None: no position encoding) [>= S, 256]."""
+
+    def __init__(self, ln_g, ln_b, gw, gb, emb, pe=None, device="cuda"):
+        f = lambda a: None if a is None else torch.as_tensor(a, dtype=torch.float32).to(device).contiguous()
+        self.ln_g, self.ln_b, self.gw, self.gb, self.emb, self.pe = map(f, (ln_g, ln_b, gw, gb, emb, pe))
+        self.V = int(self.gw.shape[0])
+
+    def args(self):
+        return _ptr(self.ln_g), _ptr(self.ln_b), _ptr(self.gw), _ptr(self.gb), self.V
+
+
+class NextRows:
+    """The next step's input rows a search kernel writes: x (P16 [R16, 256]), part [R16, 16, 2], tok [R16]."""
+
+    def __init__(self, R, device, fill=0.0):
+        R16 = (R + 15) // 16 * 16
+        self.R = R
+        self.x = torch.full((R16, 256), fill, dtype=torch.float32, device=device)
+        self.part = torch.full((R16, 16, 2), fill, dtype=torch.float32, device=device)
+        self.tok = torch.full((R16,), -1, dtype=torch.int32, device=device)
+
+    def rows(self):
+        """x row-major [R, 256]"""
+        return unpack_p16(self.x, self.R)
+
+
+def _cur_stream(dev):
+    return ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+def op_greedy_head(head: SearchHead, x, step, S, min_len, eos, out=None, ne=None, temp=1.0, topk=-1, seed=None):
+    """One greedy head launch (nd_op_greedy_head) over the rows of x [R, 256] row-major.  out: dict of tok [R],
+    out_tokens [R, S], score [R], logp [R, S, V] (made when None); ne: NextRows; seed: a device int64 word (None:
+    argmax).  Returns (out, ne)."""
+    R, dev, V = x.shape[0], x.device, head.V
+    if out is None:
+        out = dict(tok=torch.full((R,), -1, dtype=torch.int32, device=dev),
+                   out_tokens=torch.full((R, S), -1, dtype=torch.int32, device=dev),
+                   score=torch.zeros(R, dtype=torch.float32, device=dev),
+                   logp=torch.zeros(R, S, max(V, 1), dtype=torch.float32, device=dev))
+    ne = ne or NextRows(R, dev)
+    xp = pack_p16(x)
+    _lib.check(_lib.lib().nd_op_greedy_head(_ptr(xp), *head.args(), S, step, min_len, eos, R, _ptr(head.emb),
+                                            _ptr(head.pe), _ptr(ne.x), _ptr(ne.part), _ptr(ne.tok), _ptr(out["tok"]),
+                                            _ptr(out["out_tokens"]), _ptr(out["score"]), _ptr(out.get("logp")),
+                                            float(temp), int(topk), _ptr(seed), _cur_stream(dev)),
+               "nd_op_greedy_head")
+    return out, ne
+
+
+class BeamOpState:
+    """Every buffer of nd_beam_state as a torch tensor (members by the struct's names; seq / anc / cov / blk are
+    [2, ...]), so a test reads any field.  T > 0 allocates the classic Beam's coverage state and attn [C * beam, S,
+    T]; cut [C]."""
+
+    INT = dict(tok="R", done="C", top_fin="C", n_hyp="C", hyp_len="CN", n_alive="1", steps_done="1", group="C",
+               grp_left="C", grp_done="C", steps_run="C")
+
+    def __init__(self, C, beam, n_best, S, device, T=0, fill=0):
+        self.C, self.beam, self.n_best, self.S, self.T = C, beam, n_best, S, T
+        R = C * beam
+        n = {"R": R, "C": C, "CN": C * n_best, "1": 1}
+        i32 = lambda *s: torch.full(s, fill, dtype=torch.int32, device=device)
+        f32 = lambda *s: torch.full(s, float(fill), dtype=torch.float32, device=device)
+        t = {k: i32(n[v]) for k, v in self.INT.items()}
+        t.update(cum=f32(R), seq=i32(2, R, S), anc=i32(2, R, S), hyp_score=f32(C * n_best),
+                 hyp_tok=i32(C * n_best, S), hyp_anc=i32(C * n_best, S), pen=f32(R), prev_pen=f32(R), blk=i32(2, R),
+                 cov=f32(2, R, max(T, 1)), attn=f32(R, S, max(T, 1)), cut=i32(C))
+        self.t = t
+        c = _lib.NdBeamState()
+        for k, v in t.items():
+            if T == 0 and k in ("attn", "cut", "cov"):
+                continue  # null: no attention captured
+            if k in ("seq", "anc", "cov", "blk"):
+                getattr(c, k)[0], getattr(c, k)[1] = v[0].data_ptr(), v[1].data_ptr()
+            else:
+                setattr(c, k, v.data_ptr())
+        c.T = T
+        self.c = c
+
+    def __getitem__(self, k):
+        return self.t[k]
+
+    def snapshot(self):
+        return {k: v.clone() for k, v in self.t.items()}
+
+    def ref(self):
+        return ctypes.byref(self.c)
+
+
+def op_beam_init(st: BeamOpState, bos, group=None):
+    """nd_op_beam_init, or with group [C] nd_op_beam_classic_init."""
+    dev = st["cum"].device
+    if group is None:
+        _lib.check(_lib.lib().nd_op_beam_init(st.ref(), st.C, st.beam, bos, _cur_stream(dev)), "nd_op_beam_init")
+    else:
+        _lib.check(_lib.lib().nd_op_beam_classic_init(st.ref(), _ptr(group), st.C, st.beam, bos, _cur_stream(dev)),
+                   "nd_op_beam_classic_init")
+
+
+def op_beam_step(head: SearchHead, x, st: BeamOpState, ne: NextRows, step, min_len, eos, alpha=0.0, clist=None,
+                 ccap=0, opts=None):
+    """One search step over x [C * beam, 256] row-major: nd_op_beam_step, or with opts (an NdClassicOpts)
+    nd_op_beam_classic_step."""
+    dev = x.device
+    xp = pack_p16(x)
+    a = (_ptr(xp), *head.args(), _ptr(head.emb), _ptr(head.pe), _ptr(ne.x), _ptr(ne.part), _ptr(ne.tok), st.ref(),
+         st.C, st.beam, st.n_best, step, st.S, min_len, eos)
+    if opts is None:
+        _lib.check(_lib.lib().nd_op_beam_step(*a, float(alpha), _ptr(clist), ccap, _cur_stream(dev)),
+                   "nd_op_beam_step")
+    else:
+        _lib.check(_lib.lib().nd_op_beam_classic_step(*a, ctypes.byref(opts), _cur_stream(dev)),
+                   "nd_op_beam_classic_step")
+
+
+def op_beam_finish(st: BeamOpState, opts=None):
+    """nd_op_beam_finish (opts: nd_op_beam_classic_finish) -> tokens [C, n_best, S], scores, lens [C, n_best]."""
+    dev = st["cum"].device
+    tokens = torch.full((st.C, st.n_best, st.S), -9, dtype=torch.int32, device=dev)
+    scores = torch.zeros(st.C, st.n_best, dtype=torch.float32, device=dev)
+    lens = torch.zeros(st.C, st.n_best, dtype=torch.int32, device=dev)
+    if opts is None:
+        _lib.check(_lib.lib().nd_op_beam_finish(st.ref(), st.C, st.n_best, st.S, _ptr(tokens), _ptr(scores),
+                                                _ptr(lens), _cur_stream(dev)), "nd_op_beam_finish")
+    else:
+        _lib.check(_lib.lib().nd_op_beam_classic_finish(st.ref(), st.C, st.beam, st.n_best, st.S, ctypes.byref(opts),
+                                                        _ptr(tokens), _ptr(scores), _ptr(lens), _cur_stream(dev)),
+                   "nd_op_beam_classic_finish")
+    return tokens, scores, lens
+
+
+def op_attn_step_softmax(a: torch.Tensor, span: torch.Tensor, rpc: int, T: int):
+    """In place on a [R, ld]: row r's first T entries -> softmax over keys < min(span[r // rpc], T), zero after."""
+    _lib.check(_lib.lib().nd_op_attn_step_softmax(_ptr(a), a.stride(0), _ptr(span), a.shape[0], rpc, T,
+                                                  _cur_stream(a.device)), "nd_op_attn_step_softmax")
+    return a
+
+
+def op_beam_attn_gather(st: BeamOpState, max_len: int, T: int):
+    """out [C, n_best, max_len, T]: each hypothesis' attention rows along its ancestry (nd_op_beam_attn_gather)."""
+    dev = st["cum"].device
+    out = torch.full((st.C, st.n_best, max_len, T), -7.25, dtype=torch.float32, device=dev)
+    _lib.check(_lib.lib().nd_op_beam_attn_gather(st.ref(), st.C, st.n_best, st.S, max_len, T, _ptr(out),
+                                                 _cur_stream(dev)), "nd_op_beam_attn_gather")
+    return out
+
+
 def pad_chunks(chunks: Sequence[np.ndarray], T: Optional[int] = None):
     """make_nano (inputters/inputter.py:86-95): zero pad to [B, T]."""
     lens = np.array([len(c) for c in chunks], np.int32)

@@ -119,6 +119,26 @@ static void null_paths() {
   char small[3];
   CHECK(nd_switches(small, (int32_t)sizeof small) >= 0 && strlen(small) < sizeof small);
   CHECK(nd_switches(nullptr, 0) >= 0);
+  // the search op entries: a null state, a state whose members are null, a step at S, EOS outside the vocabulary
+  nd_beam_state st{};
+  nd_classic_opts co{};
+  CHECK(nd_op_beam_init(nullptr, 1, 2, 0, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_init(&st, 1, 2, 0, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_step(buf, buf, buf, buf, buf, 4, buf, nullptr, buf, buf, nullptr, &st, 1, 2, 1, 0, 4, 0, 3, 0.f,
+                        nullptr, 0, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_finish(&st, 1, 1, 4, i4, buf, i4, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_classic_init(&st, i4, 1, 2, 0, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_classic_step(buf, buf, buf, buf, buf, 4, buf, nullptr, buf, buf, nullptr, &st, 1, 2, 1, 0, 4, 0, 3,
+                                &co, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_classic_finish(&st, 1, 2, 1, 4, &co, i4, buf, i4, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_greedy_head(buf, buf, buf, buf, buf, 4, 4, 4, 0, 3, 1, buf, nullptr, buf, buf, nullptr, i4, i4, buf,
+                          nullptr, 1.f, -1, nullptr, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_greedy_head(buf, buf, buf, buf, buf, 4, 4, 0, 0, 4, 1, buf, nullptr, buf, buf, nullptr, i4, i4, buf,
+                          nullptr, 1.f, -1, nullptr, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_greedy_head(buf, buf, buf, buf, buf, 33, 4, 0, 0, 3, 1, buf, nullptr, buf, buf, nullptr, i4, i4, buf,
+                          nullptr, 1.f, -1, nullptr, nullptr) == ND_ERR_ARG);  // the launcher's: V > 32
+  CHECK(nd_op_attn_step_softmax(nullptr, 4, i4, 1, 1, 4, nullptr) == ND_ERR_ARG);
+  CHECK(nd_op_beam_attn_gather(&st, 1, 1, 4, 4, 4, buf, nullptr) == ND_ERR_ARG);
   nd_destroy(nullptr);
   CHECK(strlen(nd_version()) > 0);
   CHECK(strlen(nd_last_error()) > 0);

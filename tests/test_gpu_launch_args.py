@@ -140,3 +140,91 @@ def test_enc_layer0_refuses(bufs, t, null):
                                      C, t, _p(prep), _p(scal), ctypes.c_void_p(prep.data_ptr() + 6 * 256 * 4), None)
     _refused(b, rc, b"enc_layer0")
     assert bool((prep == -7.25).all()) and bool((scal == -7.25).all())
+
+
+# ----------------------------------------------------------------- output head and search entries
+SV, SS, SC = 9, 4, 3  # vocabulary, steps, chunks of the search refusals
+
+
+def _search_state(b, beam=4, n_best=2, T=0):
+    from nanodecoder_amd.engine import BeamOpState
+    return BeamOpState(SC, min(beam, 8), n_best, SS, b["out"].device, T=T)
+
+
+def _head_args(b, V):
+    w = _p(b["q"])
+    return (_p(b["kv"]), w, w, w, w, V)
+
+
+def _next_args(b):
+    return (_p(b["bank"]), None, _p(b["out"]), _p(b["part"]), None)  # emb, pe, ne_x, ne_part, ne_tok
+
+
+@pytest.mark.parametrize("V,temp,topk,sample", [
+    (0, 1.0, -1, False), (33, 1.0, -1, False),                        # V outside [1, 32]
+    (SV, 0.0, -1, True), (SV, 1.0, 1, True), (SV, 1.0, SV + 1, True),  # sampling that is argmax, or keeps > V
+])
+def test_greedy_head_refuses(bufs, V, temp, topk, sample):
+    b = bufs
+    seed = torch.ones(1, dtype=torch.int64, device=b["out"].device)
+    rc = _lib.lib().nd_op_greedy_head(*_head_args(b, V), SS, 0, 0, 0, 4, *_next_args(b), _p(b["em"]), _p(b["clist"]),
+                                      _p(b["ks"]), None, temp, topk, _p(seed) if sample else None, None)
+    _refused(b, rc, b"greedy_head")
+
+
+@pytest.mark.parametrize("V,beam,n_best,ccap", [
+    (0, 4, 2, None), (33, 4, 2, None),  # V outside [1, 32]
+    (SV, 9, 2, None),                   # beam > 8
+    (32, 9, 2, None),                   # beam * V > 256
+    (SV, 4, 5, None),                   # n_best > beam
+    (SV, 4, 2, 0), (SV, 4, 2, SC + 1),  # ccap outside [1, C]
+])
+def test_beam_step_refuses(bufs, V, beam, n_best, ccap):
+    b = bufs
+    st = _search_state(b, beam, n_best)
+    rc = _lib.lib().nd_op_beam_step(*_head_args(b, V), *_next_args(b), st.ref(), SC, beam, n_best, 0, SS, 0, 0, 0.0,
+                                    _p(b["clist"]) if ccap is not None else None, ccap or 0, None)
+    _refused(b, rc, b"beam_step")
+
+
+@pytest.mark.parametrize("V,beam,n_best,cov,T,ngram", [
+    (6, 8, 2, 0, 0, 0),    # V < beam: step 0 has V candidates only
+    (SV, 9, 2, 0, 0, 0),   # beam > 8
+    (SV, 4, 5, 0, 0, 0),   # n_best > beam
+    (SV, 4, 2, 1, 0, 0),   # a coverage penalty without attn / cut / cov
+    (SV, 4, 2, 0, 0, SS + 1),  # an n-gram longer than the run
+])
+def test_beam_classic_step_refuses(bufs, V, beam, n_best, cov, T, ngram):
+    b = bufs
+    st = _search_state(b, beam, n_best, T)
+    opts = _lib.NdClassicOpts(coverage_penalty=cov, beta=0.1, block_ngram_repeat=ngram)
+    rc = _lib.lib().nd_op_beam_classic_step(*_head_args(b, V), *_next_args(b), st.ref(), SC, beam, n_best, 0, SS, 0,
+                                            0, ctypes.byref(opts), None)
+    _refused(b, rc, b"beam_classic_step")
+
+
+def test_beam_classic_finish_refuses_more_hypotheses_than_beams(bufs):
+    b = bufs
+    st = _search_state(b, 4, 2)
+    opts = _lib.NdClassicOpts()
+    tokens = torch.full((SC * 5 * SS,), -7, dtype=torch.int32, device=b["out"].device)
+    rc = _lib.lib().nd_op_beam_classic_finish(st.ref(), SC, 4, 5, SS, ctypes.byref(opts), _p(tokens), _p(b["out"]),
+                                              _p(b["em"]), None)
+    _refused(b, rc, b"beam_classic_finish")
+    assert bool((tokens == -7).all())
+
+
+@pytest.mark.parametrize("attn,T,max_len", [(False, 4, SS), (True, 9, SS), (True, 4, SS + 1)])
+def test_beam_attn_gather_refuses(bufs, attn, T, max_len):
+    """no captured attention; rows wider than the capture's; more steps than the state holds"""
+    b = bufs
+    st = _search_state(b, 4, 2, T=8 if attn else 0)
+    rc = _lib.lib().nd_op_beam_attn_gather(st.ref(), SC, 2, SS, max_len, T, _p(b["out"]), None)
+    _refused(b, rc, b"beam_attn_gather")
+
+
+@pytest.mark.parametrize("R,rpc,t", [(0, 1, 4), (4, 0, 4), (4, 1, 0)])
+def test_attn_step_softmax_refuses(bufs, R, rpc, t):
+    b = bufs
+    rc = _lib.lib().nd_op_attn_step_softmax(_p(b["out"]), 16, _p(b["span"]), R, rpc, t, None)
+    _refused(b, rc, b"attn_step_softmax")

@@ -70,3 +70,99 @@ def test_lstm_layer_refuses(L, wih0, bn_scale, bn_shift):
     rc = L.nd_op_lstm_layer(None, _buf(), opt(wih0), _buf(), _buf(), _buf(), 1, 4, _buf(), opt(bn_scale),
                             opt(bn_shift), 1, None)
     _refused(L, rc, b"lstm_layer: ")
+
+
+# ----------------------------------------------------------------- output head and search entries
+def _state(null=None):
+    """An nd_beam_state whose members all point at one small host array (never read by a refused call)."""
+    keep = (ctypes.c_float * 16)()
+    p = ctypes.cast(keep, ctypes.c_void_p).value
+    st = _lib.NdBeamState()
+    for name, kind in _lib.NdBeamState._fields_:
+        if name == "T":
+            st.T = 4
+        elif name in ("seq", "anc", "cov", "blk"):
+            getattr(st, name)[0] = getattr(st, name)[1] = p
+        else:
+            setattr(st, name, p)
+    if null:
+        setattr(st, null, None)
+    st._keep = keep
+    return st
+
+
+def _greedy_head(L, V=9, S=4, step=0, eos=3, R=2, x=True, temp=1.0, topk=-1, seed=False):
+    b = _buf()
+    return L.nd_op_greedy_head(b if x else None, b, b, b, b, V, S, step, 0, eos, R, b, None, b, b, None, b, b, b,
+                               None, temp, topk, b if seed else None, None)
+
+
+@pytest.mark.parametrize("kw", [dict(step=4), dict(step=-1), dict(eos=9), dict(eos=-1), dict(R=0), dict(S=0),
+                                dict(x=False)])
+def test_greedy_head_refuses_bad_arguments(L, kw):
+    """a step outside [0, S), EOS outside the vocabulary (the mask would write past the row's log-probs), no rows,
+    a null input: the entry's own checks"""
+    _refused(L, _greedy_head(L, **kw), b"greedy_head: bad arguments")
+
+
+@pytest.mark.parametrize("kw", [dict(V=0), dict(V=33, eos=3), dict(seed=True, temp=0.0), dict(seed=True, topk=1),
+                                dict(seed=True, topk=10)])
+def test_greedy_head_launcher_refuses(L, kw):
+    _refused(L, _greedy_head(L, **kw), b"greedy_head: ")
+    assert b"bad arguments" not in L.nd_last_error()
+
+
+def _beam_step(L, classic, V=9, beam=4, n_best=2, step=0, S=4, eos=3, C=3, null=None, ccap=None, opts=None):
+    b, st = _buf(), _state(null)
+    head = (b, b, b, b, b, V, b, None, b, b, None, ctypes.byref(st), C, beam, n_best, step, S, 0, eos)
+    if classic:
+        o = opts if opts is not None else _lib.NdClassicOpts()
+        return L.nd_op_beam_classic_step(*head, ctypes.byref(o), None)
+    return L.nd_op_beam_step(*head, 0.6, b if ccap is not None else None, ccap or 0, None)
+
+
+@pytest.mark.parametrize("classic", [False, True])
+@pytest.mark.parametrize("kw", [dict(step=4), dict(eos=9), dict(C=0), dict(null="cum"), dict(null="hyp_anc")])
+def test_beam_step_refuses_bad_arguments(L, classic, kw):
+    what = b"beam_classic_step: bad arguments" if classic else b"beam_step: bad arguments"
+    _refused(L, _beam_step(L, classic, **kw), what)
+
+
+def test_beam_classic_step_refuses_bad_arguments(L):
+    _refused(L, _beam_step(L, True, null="grp_done"), b"beam_classic_step: bad arguments")
+    _refused(L, _beam_step(L, True, opts=_lib.NdClassicOpts(length_penalty=3)), b"beam_classic_step: bad arguments")
+    _refused(L, _beam_step(L, True, opts=_lib.NdClassicOpts(coverage_penalty=-1)), b"beam_classic_step: bad arguments")
+
+
+@pytest.mark.parametrize("classic,kw", [
+    (False, dict(V=33)), (False, dict(beam=9)), (False, dict(V=32, beam=9)), (False, dict(n_best=5)),
+    (False, dict(ccap=0)), (False, dict(ccap=4)),
+    (True, dict(V=6, beam=8)), (True, dict(n_best=5)), (True, dict(null="attn", opts=_lib.NdClassicOpts(coverage_penalty=1))),
+])
+def test_beam_step_launcher_refuses(L, classic, kw):
+    _refused(L, _beam_step(L, classic, **kw), b"beam_classic_step: " if classic else b"beam_step: ")
+    assert b"bad arguments" not in L.nd_last_error()
+
+
+def test_beam_init_and_finish_refuse_bad_arguments(L):
+    b, st, o = _buf(), _state(), _lib.NdClassicOpts()
+    _refused(L, L.nd_op_beam_init(ctypes.byref(st), 3, 9, 2, None), b"beam_init: bad arguments")
+    _refused(L, L.nd_op_beam_init(None, 3, 4, 2, None), b"beam_init: bad arguments")
+    _refused(L, L.nd_op_beam_classic_init(ctypes.byref(st), None, 3, 4, 2, None), b"beam_classic_init: bad arguments")
+    _refused(L, L.nd_op_beam_finish(ctypes.byref(st), 3, 0, 4, b, b, b, None), b"beam_finish: bad arguments")
+    _refused(L, L.nd_op_beam_finish(ctypes.byref(st), 3, 2, 4, None, b, b, None), b"beam_finish: bad arguments")
+    _refused(L, L.nd_op_beam_classic_finish(ctypes.byref(st), 3, 4, 2, 4, None, b, b, b, None),
+             b"beam_classic_finish: bad arguments")
+    _refused(L, L.nd_op_beam_classic_finish(ctypes.byref(st), 3, 4, 5, 4, ctypes.byref(o), b, b, b, None),
+             b"beam_classic_finish: ")
+    assert b"bad arguments" not in L.nd_last_error()  # n_best > beam: the launcher's
+
+
+def test_attention_capture_entries_refuse(L):
+    b, st = _buf(), _state()
+    _refused(L, L.nd_op_attn_step_softmax(None, 16, b, 4, 1, 4, None), b"attn_step_softmax: bad arguments")
+    _refused(L, L.nd_op_attn_step_softmax(b, 3, b, 4, 1, 4, None), b"attn_step_softmax: bad arguments")  # ld < T
+    _refused(L, L.nd_op_attn_step_softmax(b, 16, b, 0, 1, 4, None), b"attn_step_softmax: ")
+    _refused(L, L.nd_op_beam_attn_gather(ctypes.byref(st), 3, 2, 4, 4, 4, None, None), b"beam_attn_gather: bad arguments")
+    _refused(L, L.nd_op_beam_attn_gather(ctypes.byref(st), 3, 2, 4, 4, 5, b, None), b"beam_attn_gather: ")  # T > st.T
+    _refused(L, L.nd_op_beam_attn_gather(ctypes.byref(_state("attn")), 3, 2, 4, 4, 4, b, None), b"beam_attn_gather: ")
