@@ -349,6 +349,61 @@ int nd_assemble_reads_m(const uint8_t* d_bases, const uint16_t* d_qw, const uint
                         int64_t total_bases, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_ml, int32_t* d_seq_len,
                         int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* Per-base signal positions.  The reference has no such output; these three
+ * entry points turn the last decoder layer's head-0 context attention (what
+ * nd_translate_greedy_attn, nd_translate_sample, nd_translate_beam_attn and
+ * nd_translate_beam_classic_ex return in d_attn) into one sample index per
+ * token and carry it through the assembly vote.  Integers throughout, so the
+ * values do not depend on the order of any sum.  No context needed.
+ *
+ * Token position of one attention row a[0..T) (fp32) of a chunk with span sp:
+ * only t < min(sp, T) is read.  q_t = 0 when !(a[t] > 0) (NaN, negatives and
+ * -0), 2^24 when a[t] >= 1, else floor((double)a[t] * 16777216.0 + 0.5)
+ * (exact in fp64).  Q = sum q_t and M = sum q_t * t in 64-bit unsigned
+ * integers; c = (2 M + Q) div (2 Q), the centroid rounded half up, c = 0 when
+ * Q == 0.  Per chunk the positions are made monotone over the steps:
+ * m[0] = c[0], m[s] = max(m[s-1], c[s]); a zero row keeps the position before
+ * it.
+ * nd_token_positions writes d_pos [B, S] i32 = m from d_span [B] and d_attn:
+ * row s of chunk b is at d_attn + b * ld_chunk + s * T (the greedy and
+ * sampling output [B, max_len, T]: ld_chunk = max_len * T; the beam output
+ * [B, n_best, max_len, T]: ld_chunk = n_best * max_len * T, which selects
+ * hypothesis 0, whose rows past its length are zero rows).  One launch on
+ * `stream`, no allocation, no synchronisation.  Negative sizes, T < 1,
+ * T > 2^19 (2 M + Q then stays inside 64 bits whatever a row holds),
+ * ld_chunk < S * T, B * S >= 2^31 or a null buffer return ND_ERR_ARG before
+ * any HIP call.
+ *
+ * Every char of a token's word carries the token's m; the absolute position
+ * of a char of chunk ci of a read (its index among all of the read's chunks,
+ * empty ones included) is ci * src_seq_stride + m, a uint32.
+ *
+ * Column position of one column of a read's vote: n = its votes of all
+ * classes (exactly the votes nd_assemble_reads counts, those that lost the
+ * call included), P = the 64-bit sum of their absolute positions; the column
+ * gets P div n, and 0 when n = 0.  Read positions are the running maximum of
+ * the column positions along the read: r[0] = col[0], r[x] = max(r[x-1],
+ * col[x]).
+ *
+ * nd_assemble_reads_p is nd_assemble_reads with
+ *   d_bp   [total_bases] u32 (in):  the absolute position of each byte of
+ *          d_bases
+ *   d_rpos [total_bases] u32 (out): the read positions of the assembled
+ *          reads, laid out like d_seq; 0 past a read's length
+ * Overlap, placement, d_seq, d_seq_len and d_status are those of
+ * nd_assemble_reads on the same input.  d_work holds
+ * nd_assemble_reads_p_work_bytes(C, total_bases) bytes (nd_assemble_reads'
+ * plus total_bases * 8); argument checks and the R == 0 and C == 0 paths as
+ * nd_assemble_reads.  One more launch than nd_assemble_reads: the per-read
+ * running maximum, in blocks of 256 columns with a carry. */
+int nd_token_positions(const float* d_attn, int64_t ld_chunk, const int32_t* d_span, int32_t B, int32_t S, int32_t T,
+                       int32_t* d_pos, void* stream);
+int64_t nd_assemble_reads_p_work_bytes(int32_t C, int64_t total_bases);
+int nd_assemble_reads_p(const uint8_t* d_bases, const uint32_t* d_bp, const int32_t* d_chunk_off,
+                        const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
+                        uint32_t* d_rpos, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
+                        void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

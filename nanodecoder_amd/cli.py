@@ -112,7 +112,8 @@ def _extract(args):
         return ["!" + prefix, repr(e)]
 
 
-def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None, mods=None):
+def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None, mods=None,
+                 moves=None):
     """translate.py:81-98.  ``sequence``: the read already assembled
     (-assembly gpu); None assembles it here.  ``weights`` (-fastq): the
     chunks' per-base weights; ``sequence`` is then (sequence, quality string),
@@ -120,9 +121,17 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
     ``mods`` (-mod_probs, beside ``weights``): the chunks' per-base
     modification weights; ``sequence`` is then (sequence, quality string, ml),
     result/<read>.mod.fastq is written before the .fasta too, and the .fastq
-    only with -fastq."""
+    only with -fastq.  ``moves`` (-moves): the chunks' per-base chunk-relative
+    signal positions; ``sequence`` then carries the read positions as its
+    last entry ((sequence, positions) without ``weights``), and
+    result/<read>.moves is written before the .fasta too."""
     try:
         name = file_src.split(".txt")[0]
+        rpos = None
+        if moves is not None and sequence is not None:
+            rpos, sequence = sequence[-1], (sequence[:-1] if weights is not None else sequence[0])
+        elif moves is not None and weights is not None:  # a second host assembly: the forms are not multiplied
+            rpos = frontend.assemble_read_p(all_predictions, moves, opt.src_seq_length, opt.src_seq_stride)[1]
         if mods is not None:
             c_bpread, quality, ml = sequence if sequence is not None else \
                 frontend.assemble_read_m(all_predictions, weights, mods, opt.src_seq_length, opt.src_seq_stride)
@@ -136,9 +145,14 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
                 frontend.assemble_read_q(all_predictions, weights, opt.src_seq_length, opt.src_seq_stride)
             with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
                 f.write("@%s\n%s\n+\n%s\n" % (name, c_bpread, quality))
+        elif moves is not None and sequence is None:
+            c_bpread, rpos = frontend.assemble_read_p(all_predictions, moves, opt.src_seq_length, opt.src_seq_stride)
         else:
             c_bpread = sequence if sequence is not None else \
                 frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
+        if moves is not None:
+            with open(os.path.join(opt.save_data, "result", name + ".moves"), "w") as f:
+                f.write(frontend.moves_record(name, c_bpread, rpos))
         with open(os.path.join(opt.save_data, "result", name + ".fasta"), "w") as f:
             f.writelines(">%s\n%s" % (name, c_bpread))
         with open(os.path.join(opt.save_data, "segment", file_src), "w+") as f:
@@ -160,6 +174,8 @@ def main(opt=None):
         raise ValueError("-fastq is not available together with -attn_debug")
     if getattr(opt, "mod_probs", False) and opt.attn_debug:
         raise ValueError("-mod_probs is not available together with -attn_debug")
+    if getattr(opt, "moves", False) and opt.attn_debug:
+        raise ValueError("-moves is not available together with -attn_debug")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
@@ -218,6 +234,9 @@ def _translate_group(opt, translator, group, raw=False):
     want = dict(qualities=True) if fastq else {}
     if mod_probs:
         want["mods"] = True
+    moves = bool(getattr(opt, "moves", False))
+    if moves:
+        want["moves"] = True
     try:
         if opt.attn_debug:
             outs = _translate_attn(opt, translator, group)
@@ -237,6 +256,8 @@ def _translate_group(opt, translator, group, raw=False):
     seqs = [None] * len(outs)
     weights = [o[2] for o in outs] if fastq else [None] * len(outs)  # -fastq: per chunk, its bases' weights
     mods = [o[3] for o in outs] if mod_probs else [None] * len(outs)  # -mod_probs: their modification weights
+    # -moves: their chunk-relative signal positions, the last entry
+    positions = [o[2 + int(fastq) + int(mod_probs)] for o in outs] if moves else [None] * len(outs)
     if getattr(opt, "assembly", "cpu") == "gpu":
         # the whole group in one device call; a read left None (its host fallback raised) is assembled
         # again by write_output, which reports that read's error as -assembly cpu does
@@ -244,14 +265,15 @@ def _translate_group(opt, translator, group, raw=False):
             seqs = frontend.assemble_reads([o[1] for o in outs], opt.src_seq_length, opt.src_seq_stride,
                                            device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True,
                                            **(dict(weights=weights) if fastq else {}),
-                                           **(dict(mod_weights=mods) if mod_probs else {}))
+                                           **(dict(mod_weights=mods) if mod_probs else {}),
+                                           **(dict(positions=positions) if moves else {}))
         except Exception as e:
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    for g, o, seq, w, mw in zip(group, outs, seqs, weights, mods):
+    for g, o, seq, w, mw, ps in zip(group, outs, seqs, weights, mods, positions):
         write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
-                     **(dict(mods=mw) if mod_probs else {}))
+                     **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}))
     return len(group)
 
 

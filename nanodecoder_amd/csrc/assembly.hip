@@ -41,6 +41,12 @@
 // C) the vote kernel also adds the uint16 mw of every vote of class C or M into msum[total_bases] (one more
 // 64-bit plane), and the call kernel gives a column called C or M the byte
 // ML = min(255, (256 W) div (65535 n_cm)), W its msum and n_cm its C plus M votes; 0 for every other column.
+//
+// With per-base signal positions (nd_assemble_reads_p, the plain form's kernels with the POS flag) the vote
+// kernel adds each vote's absolute position bp[.] (uint32) into psum[total_bases] (one 64-bit plane, integer
+// atomics as above), the call kernel gives a column of n >= 1 votes P div n (0 with no vote), and a fifth
+// launch, one workgroup per read, takes the running maximum along the read in blocks of 256 columns with a
+// carry.  nd_token_positions (one launch) turns a call's attention rows into the chunk-relative positions.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -185,14 +191,16 @@ asm_place_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read
 }
 
 // one wave per chunk: its chars vote at pos[c] + x of the read's columns; QUAL: each vote's weight qw[.] is
-// added to wsum of its class and column; MOD: a C or M vote's modification weight mw[.] to msum of its column
-template <bool QUAL, bool MOD = false>
+// added to wsum of its class and column; MOD: a C or M vote's modification weight mw[.] to msum of its column;
+// POS: each vote's absolute signal position bp[.] to psum of its column
+template <bool QUAL, bool MOD = false, bool POS = false>
 __global__ void __launch_bounds__(ASM_THREADS)
 asm_vote_kernel(const unsigned char* __restrict__ bases, const unsigned short* __restrict__ qw,
                 const unsigned short* __restrict__ mw, const int* __restrict__ chunk_off,
                 const int* __restrict__ read_off, const int* __restrict__ pos, const int* __restrict__ rd,
                 const int* __restrict__ status, int C, int total, int* __restrict__ count,
-                unsigned long long* __restrict__ wsum, unsigned long long* __restrict__ msum) {
+                unsigned long long* __restrict__ wsum, unsigned long long* __restrict__ msum,
+                const unsigned* __restrict__ bp, unsigned long long* __restrict__ psum) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -205,20 +213,23 @@ asm_vote_kernel(const unsigned char* __restrict__ bases, const unsigned short* _
       atomicAdd(&count[(size_t)cls * total + r0 + col], 1);
       if (QUAL) atomicAdd(&wsum[(size_t)cls * total + r0 + col], (unsigned long long)qw[o + x]);
       if (MOD && (cls == 1 || cls == 4)) atomicAdd(&msum[r0 + col], (unsigned long long)mw[o + x]);
+      if (POS) atomicAdd(&psum[r0 + col], (unsigned long long)bp[o + x]);
     }
   }
 }
 
 // one wave per chunk's span of the output: column g - r0 of read rd[c], 0 past the read's length; QUAL: the
 // column's Q from its votes and the winning class's weight sum; MOD: ML of a column called C or M from its C
-// and M votes and their modification weight sum
-template <bool QUAL, bool MOD = false>
+// and M votes and their modification weight sum; POS: the column's position, its votes' position sum over
+// their number (asm_pos_scan_kernel then makes the positions monotone along the read)
+template <bool QUAL, bool MOD = false, bool POS = false>
 __global__ void __launch_bounds__(ASM_THREADS)
 asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_off, const int* __restrict__ rd,
                 const int* __restrict__ seq_len, const int* __restrict__ count,
                 const unsigned long long* __restrict__ wsum, const unsigned long long* __restrict__ msum, int C,
                 int total, unsigned char* __restrict__ seq, unsigned char* __restrict__ qual,
-                unsigned char* __restrict__ ml) {
+                unsigned char* __restrict__ ml, const unsigned long long* __restrict__ psum,
+                unsigned* __restrict__ rpos) {
   const int c = blockIdx.x * (ASM_THREADS / 64) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (c >= C) return;
   const int r = rd[c];
@@ -228,6 +239,7 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
     const int g = o + x;
     if (g >= total) break;
     unsigned char out = 0, q = 0, mod = 0;
+    unsigned cp = 0;
     if (g - r0 < n) {
       int best = count[g], cls = 0;
       long long votes = best;
@@ -245,6 +257,7 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
         const double e = (double)(full - wsum[(size_t)cls * total + g]), f = (double)full;  // both exact
         for (int k = 1; k < PHRED_LEVELS && e * d_phred_ratio[k] <= f; ++k) q = (unsigned char)k;
       }
+      if (POS && votes > 0) cp = (unsigned)(psum[g] / (unsigned long long)votes);  // a mean of uint32 values
       if (MOD && (cls == 1 || cls == 4)) {
         const unsigned long long n_cm =
             (unsigned long long)count[(size_t)total + g] + (unsigned long long)count[(size_t)4 * total + g];
@@ -257,24 +270,54 @@ asm_call_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_
     seq[g] = out;
     if (QUAL) qual[g] = q;
     if (MOD) ml[g] = mod;
+    if (POS) rpos[g] = cp;
   }
 }
 
-size_t assemble_work_bytes(int C, long long total, bool qual, bool mod) {
+// rpos of read r, in place: the running maximum of its column positions, r[x] = max(r[x-1], col[x]) over its
+// seq_len[r] columns, in blocks of ASM_THREADS columns with a carry (as asm_place_kernel scans disp)
+__global__ void __launch_bounds__(ASM_THREADS)
+asm_pos_scan_kernel(const int* __restrict__ chunk_off, const int* __restrict__ read_off,
+                    const int* __restrict__ seq_len, int total, unsigned* __restrict__ rpos) {
+  __shared__ unsigned sm[ASM_THREADS];
+  const int r = blockIdx.x, tid = threadIdx.x;
+  const int r0 = chunk_off[read_off[r]];
+  // a read's columns are its own bytes
+  const int n = min(min(seq_len[r], chunk_off[read_off[r + 1]] - r0), total - r0);
+  unsigned carry = 0;
+  for (int base = 0; base < n; base += ASM_THREADS) {
+    const int x = base + tid;
+    sm[tid] = x < n ? rpos[r0 + x] : 0u;
+    __syncthreads();
+    for (int o = 1; o < ASM_THREADS; o <<= 1) {
+      const unsigned a = tid >= o ? sm[tid - o] : 0u;
+      __syncthreads();
+      sm[tid] = max(sm[tid], a);
+      __syncthreads();
+    }
+    if (x < n) rpos[r0 + x] = max(carry, sm[tid]);
+    carry = max(carry, sm[ASM_THREADS - 1]);
+    __syncthreads();
+  }
+}
+
+size_t assemble_work_bytes(int C, long long total, bool qual, bool mod, bool pos) {
   return (size_t)2 * C * sizeof(int) + (size_t)5 * total * sizeof(int) +
          (qual ? (size_t)5 * total * sizeof(unsigned long long) : 0) +
-         (mod ? (size_t)total * sizeof(unsigned long long) : 0);
+         (mod ? (size_t)total * sizeof(unsigned long long) : 0) +
+         (pos ? (size_t)total * sizeof(unsigned long long) : 0);
 }
 
 hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
                                  const int* read_off, int R, int C, int total, unsigned char* seq,
                                  unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
-                                 const unsigned short* mw, unsigned char* ml) {
+                                 const unsigned short* mw, unsigned char* ml, const unsigned* bp, unsigned* rpos) {
   const bool q = qual != nullptr;  // with qualities: qw and qual both given
   const bool m = ml != nullptr;    // with modification values (only beside qualities): mw and ml both given
+  const bool p = rpos != nullptr;  // with signal positions (the plain form only): bp and rpos both given
   if (R < 0 || C < 0 || total < 0 || !chunk_off || !read_off || (R > 0 && (!seq_len || !status)) ||
       (C > 0 && !work) || (total > 0 && (!bases || !seq)) || (qw != nullptr) != q || (mw != nullptr) != m ||
-      (m && !q))
+      (m && !q) || (bp != nullptr) != p || (p && q))
     return hipErrorInvalidValue;
   if (R == 0) return hipSuccess;
   hipError_t e = hipMemsetAsync(status, 0, (size_t)R * sizeof(int), s);
@@ -283,13 +326,17 @@ hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned shor
   // the 64-bit weight sums first, so they are 8-byte aligned whatever C is: wsum's five planes, then msum's one
   unsigned long long* wsum = static_cast<unsigned long long*>(work);
   unsigned long long* msum = wsum + (size_t)5 * total;
-  int* pos = q ? reinterpret_cast<int*>(wsum + (size_t)(m ? 6 : 5) * total) : static_cast<int*>(work);
+  unsigned long long* psum = static_cast<unsigned long long*>(work);  // POS: the one 64-bit plane, first as well
+  int* pos = q   ? reinterpret_cast<int*>(wsum + (size_t)(m ? 6 : 5) * total)
+             : p ? reinterpret_cast<int*>(psum + (size_t)total)
+                 : static_cast<int*>(work);
   int* rd = pos + C;
   int* count = rd + C;
   if (total > 0) {
     e = hipMemsetAsync(count, 0, (size_t)5 * total * sizeof(int), s);
     if (e == hipSuccess && q)
       e = hipMemsetAsync(wsum, 0, (size_t)(m ? 6 : 5) * total * sizeof(unsigned long long), s);
+    if (e == hipSuccess && p) e = hipMemsetAsync(psum, 0, (size_t)total * sizeof(unsigned long long), s);
     if (e != hipSuccess) return e;
   }
   const int per = ASM_THREADS / 64;
@@ -298,19 +345,25 @@ hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned shor
   hipLaunchKernelGGL(asm_place_kernel, dim3(R), block, 0, s, chunk_off, read_off, pos, status, seq_len);
   if (total > 0 && m) {
     hipLaunchKernelGGL((asm_vote_kernel<true, true>), grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd,
-                       status, C, total, count, wsum, msum);
+                       status, C, total, count, wsum, msum, bp, psum);
     hipLaunchKernelGGL((asm_call_kernel<true, true>), grid, block, 0, s, chunk_off, read_off, rd, seq_len, count,
-                       wsum, msum, C, total, seq, qual, ml);
+                       wsum, msum, C, total, seq, qual, ml, psum, rpos);
   } else if (total > 0 && q) {
     hipLaunchKernelGGL(asm_vote_kernel<true>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
-                       C, total, count, wsum, msum);
+                       C, total, count, wsum, msum, bp, psum);
     hipLaunchKernelGGL(asm_call_kernel<true>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
-                       C, total, seq, qual, ml);
+                       C, total, seq, qual, ml, psum, rpos);
+  } else if (total > 0 && p) {
+    hipLaunchKernelGGL((asm_vote_kernel<false, false, true>), grid, block, 0, s, bases, qw, mw, chunk_off, read_off,
+                       pos, rd, status, C, total, count, wsum, msum, bp, psum);
+    hipLaunchKernelGGL((asm_call_kernel<false, false, true>), grid, block, 0, s, chunk_off, read_off, rd, seq_len,
+                       count, wsum, msum, C, total, seq, qual, ml, psum, rpos);
+    hipLaunchKernelGGL(asm_pos_scan_kernel, dim3(R), block, 0, s, chunk_off, read_off, seq_len, total, rpos);
   } else if (total > 0) {
     hipLaunchKernelGGL(asm_vote_kernel<false>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
-                       C, total, count, wsum, msum);
+                       C, total, count, wsum, msum, bp, psum);
     hipLaunchKernelGGL(asm_call_kernel<false>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
-                       C, total, seq, qual, ml);
+                       C, total, seq, qual, ml, psum, rpos);
   }
   return hipGetLastError();
 }
@@ -376,6 +429,64 @@ hipError_t launch_token_mod_weights(const int* tokens, const float* logp, int n,
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(token_mod_weights_kernel, dim3((n + TW_THREADS - 1) / TW_THREADS), dim3(TW_THREADS), 0, s,
                      tokens, logp, n, V, canon, mod, mw);
+  return hipGetLastError();
+}
+
+// pos[b][s] = m[s] of chunk b: the centroid c[s] = (2 M + Q) div (2 Q) of attention row s over t < min(span[b],
+// T), with q_t = 0 unless a[t] > 0, 2^24 when a[t] >= 1, else floor((double)a[t] * 2^24 + 0.5), Q = sum q_t and
+// M = sum q_t t in 64-bit integers (c = 0 when Q = 0), then m[s] = max(m[s-1], c[s]).  One workgroup per chunk:
+// the waves take the rows of a block of TP_THREADS steps, the lanes stride over t, Q and M are reduced over the
+// wave, c goes to LDS, and the block is max-scanned with a carry.
+#define TP_THREADS 256
+__global__ void __launch_bounds__(TP_THREADS)
+token_positions_kernel(const float* __restrict__ attn, long long ld_chunk, const int* __restrict__ span, int S, int T,
+                       int* __restrict__ pos) {
+  __shared__ int sc[TP_THREADS];
+  const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int n = min(max(span[b], 0), T);
+  const float* a0 = attn + (size_t)b * (size_t)ld_chunk;
+  int carry = 0;
+  for (int base = 0; base < S; base += TP_THREADS) {
+    const int rows = min(TP_THREADS, S - base);
+    sc[tid] = 0;
+    __syncthreads();
+    for (int i = wave; i < rows; i += TP_THREADS / 64) {
+      const float* a = a0 + (size_t)(base + i) * T;
+      unsigned long long Q = 0, M = 0;
+      for (int t = lane; t < n; t += 64) {
+        const float v = a[t];
+        unsigned long long q = 0;
+        if (v > 0.f)  // false for NaN, negatives and -0
+          q = v >= 1.f ? 1ull << 24 : (unsigned long long)floor((double)v * 16777216.0 + 0.5);  // exact in fp64
+        Q += q;
+        M += q * (unsigned long long)t;
+      }
+      for (int o = 32; o > 0; o >>= 1) {
+        Q += __shfl_xor(Q, o, 64);
+        M += __shfl_xor(M, o, 64);
+      }
+      if (lane == 0) sc[i] = Q ? (int)((2 * M + Q) / (2 * Q)) : 0;
+    }
+    __syncthreads();
+    for (int o = 1; o < TP_THREADS; o <<= 1) {
+      const int v = tid >= o ? sc[tid - o] : 0;
+      __syncthreads();
+      sc[tid] = max(sc[tid], v);
+      __syncthreads();
+    }
+    if (tid < rows) pos[(size_t)b * S + base + tid] = max(carry, sc[tid]);
+    carry = max(carry, sc[TP_THREADS - 1]);
+    __syncthreads();
+  }
+}
+
+hipError_t launch_token_positions(const float* attn, long long ld_chunk, const int* span, int B, int S, int T,
+                                  int* pos, hipStream_t s) {
+  if (B < 0 || S < 0 || T < 1 || T > TOKEN_POS_MAX_T || ld_chunk < (long long)S * T ||
+      (long long)B * S >= 1ll << 31 || (B > 0 && !span) || ((long long)B * S > 0 && (!attn || !pos)))
+    return hipErrorInvalidValue;
+  if (B == 0 || S == 0) return hipSuccess;
+  hipLaunchKernelGGL(token_positions_kernel, dim3(B), dim3(TP_THREADS), 0, s, attn, ld_chunk, span, S, T, pos);
   return hipGetLastError();
 }
 

@@ -417,12 +417,17 @@ hipError_t launch_read_window(const float* sig, const long long* off, const int*
 // the columns' qualities Q in 0..40 go to qual, laid out like seq.  work holds assemble_work_bytes(C, total,
 // qual != nullptr, ml != nullptr) bytes.  With mw (each base's uint16 modification weight) and ml too, both or
 // neither and only beside qw / qual, a column called C or M gets ML = min(255, (256 W) div (65535 n_cm)) in ml
-// (laid out like seq; W the mw sum of its C and M votes, n_cm their number), every other byte of ml 0
-size_t assemble_work_bytes(int C, long long total, bool qual = false, bool mod = false);
+// (laid out like seq; W the mw sum of its C and M votes, n_cm their number), every other byte of ml 0.  With bp
+// (each base's absolute signal position, uint32) and rpos, both or neither and only without qw / qual, a column
+// of n >= 1 votes gets the 64-bit sum of its votes' positions div n (0 with no vote) and rpos (laid out like seq)
+// the running maximum of the column positions along each read, 0 past its length; work then holds
+// assemble_work_bytes(C, total, false, false, true)
+size_t assemble_work_bytes(int C, long long total, bool qual = false, bool mod = false, bool pos = false);
 hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
                                  const int* read_off, int R, int C, int total, unsigned char* seq,
                                  unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
-                                 const unsigned short* mw = nullptr, unsigned char* ml = nullptr);
+                                 const unsigned short* mw = nullptr, unsigned char* ml = nullptr,
+                                 const unsigned* bp = nullptr, unsigned* rpos = nullptr);
 // the column quality's table, the doubles 10.0 ** (k / 10.0) for k < PHRED_LEVELS
 #define PHRED_LEVELS 41
 const double* phred_ratios();
@@ -435,6 +440,13 @@ hipError_t launch_token_weights(const int* tokens, const float* logp, const floa
 // the hard call (65535 for mod, 0 for canon)
 hipError_t launch_token_mod_weights(const int* tokens, const float* logp, int n, int V, int canon, int mod,
                                     unsigned short* mw, hipStream_t s);
+// token positions: pos[b][s] (int32, [B, S]) = the running maximum over the steps of the rounded centroid of
+// attention row s of chunk b (attn + b * ld_chunk + s * T, f32 probabilities) over t < min(span[b], T), in 24-bit
+// fixed point and 64-bit integer sums (include/nanodec.h nd_token_positions has the rule); T <= TOKEN_POS_MAX_T
+// keeps 2 M + Q inside 64 bits whatever the row holds
+#define TOKEN_POS_MAX_T (1 << 19)
+hipError_t launch_token_positions(const float* attn, long long ld_chunk, const int* span, int B, int S, int T,
+                                  int* pos, hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

@@ -1,5 +1,5 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_token_weights, nd_token_mod_weights): launches on the caller's stream, with no context.
+// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions): launches on the caller's stream, with no context.
 // The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
@@ -361,6 +361,45 @@ int nd_assemble_reads_m(const uint8_t* d_bases, const uint16_t* d_qw, const uint
                 nd::launch_assemble_reads(d_bases, d_qw, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
                                           d_qual, d_seq_len, d_status, d_work, (hipStream_t)stream, d_mw, d_ml),
                 ND_ERR_HIP);
+}
+
+int nd_token_positions(const float* d_attn, int64_t ld_chunk, const int32_t* d_span, int32_t B, int32_t S, int32_t T,
+                       int32_t* d_pos, void* stream) {
+  if (B < 0 || S < 0 || T < 1 || T > TOKEN_POS_MAX_T || (int64_t)B * S >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "token_positions: B and S must be >= 0, T in [1, 2^19] and B * S < 2^31");
+  if (ld_chunk < (int64_t)S * T) return fail(ND_ERR_ARG, "token_positions: ld_chunk below S * T");
+  if ((B > 0 && !d_span) || ((int64_t)B * S > 0 && (!d_attn || !d_pos)))
+    return fail(ND_ERR_ARG, "token_positions: null buffer");
+  return status("token_positions", nd::launch_token_positions(d_attn, ld_chunk, d_span, B, S, T, d_pos,
+                                                              (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int64_t nd_assemble_reads_p_work_bytes(int32_t C, int64_t total_bases) {
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, false, false, true) : -1;
+}
+
+int nd_assemble_reads_p(const uint8_t* d_bases, const uint32_t* d_bp, const int32_t* d_chunk_off,
+                        const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
+                        uint32_t* d_rpos, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
+                        void* stream) {
+  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "assemble_reads_p: R, C and total_bases must be >= 0 and total_bases < 2^31");
+  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, false, false, true);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "assemble_reads_p: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_assemble_reads_p_work_bytes asks for");
+  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
+      (total_bases > 0 && (!d_bases || !d_bp || !d_seq || !d_rpos)))
+    return fail(ND_ERR_ARG, "assemble_reads_p: null buffer");
+  if (R == 0) return ND_OK;
+  if (total_bases == 0)  // no base has a position: the plain call's paths (no chunks, or only empty ones)
+    return status("assemble_reads_p",
+                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
+                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+  return status("assemble_reads_p",
+                nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
+                                          nullptr, d_seq_len, d_status, d_work, (hipStream_t)stream, nullptr, nullptr,
+                                          d_bp, d_rpos), ND_ERR_HIP);
 }
 
 int nd_phred_ratios(double* out, int32_t n) {

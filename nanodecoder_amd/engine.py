@@ -344,6 +344,26 @@ class Engine:
                                                 _ptr(mw), self._stream()), "nd_token_mod_weights")
         return mw
 
+    def token_positions(self, attn, spans, hyp0: Optional[bool] = None):
+        """The signal positions of a call's tokens (nd_token_positions, on the current stream): per chunk and
+        step the centroid of the attention row over t < min(span, T) in 24-bit fixed point, rounded half up, then
+        the running maximum over the steps (frontend.token_positions is the same rule).  ``attn``: what a
+        translate call returns with return_attn, [B, S, T] (greedy, sampling) or, with ``hyp0``, the beam's
+        [B, n_best, S, T], of which hypothesis 0's rows are read (default: by the number of axes).  ``spans``
+        [B]: the call's spans.  Returns an int32 device tensor [B, S]."""
+        attn = torch.as_tensor(attn).to(self.device, torch.float32, non_blocking=True).contiguous()
+        hyp0 = attn.dim() == 4 if hyp0 is None else bool(hyp0)
+        if attn.dim() != (4 if hyp0 else 3):
+            raise ValueError("attn must be [B, S, T], or [B, n_best, S, T] with hyp0")
+        B, S, T = attn.shape[0], attn.shape[-2], attn.shape[-1]
+        spans = torch.as_tensor(spans).to(self.device, torch.int32, non_blocking=True).contiguous()
+        if spans.shape != (B,):
+            raise ValueError("spans must be [B]")
+        pos = torch.empty(B, S, dtype=torch.int32, device=self.device)
+        _lib.check(self._L.nd_token_positions(_ptr(attn), int(attn.stride(0)) if B else S * T, _ptr(spans), B, S, T,
+                                              _ptr(pos), self._stream()), "nd_token_positions")
+        return pos
+
     def encode(self, signal, lengths, spans=None):
         """Memory bank [B, T, d] of the encoder (rows >= span unspecified)."""
         signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
@@ -483,6 +503,12 @@ class EnginePool:
         eng = self.engines[lane]
         with torch.cuda.stream(eng.stream):
             return eng.token_mod_weights(tokens, logp, canon_id, mod_id)
+
+    def token_positions(self, attn, spans, hyp0: Optional[bool] = None, lane: int = 0):
+        """Engine.token_positions on the stream of ``lane`` (see token_weights)."""
+        eng = self.engines[lane]
+        with torch.cuda.stream(eng.stream):
+            return eng.token_positions(attn, spans, hyp0=hyp0)
 
     def encode(self, signal, lengths, spans=None):
         """Engine.encode on the next lane's context, joined to the current

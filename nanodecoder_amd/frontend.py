@@ -430,12 +430,133 @@ def mod_fastq_record(name: str, sequence: str, quality: str, ml) -> str:
     return "%s\n%s\n+\n%s\n" % (head, sequence.replace("M", "C").replace("m", "c"), quality)
 
 
+# ---------------------------------------------------------------- per-base signal positions (-moves)
+# Where in the signal each base was called, from the last decoder layer's head-0 context attention (DESIGN.md
+# §1.6).  A token's position is the centroid of its attention row in 24-bit fixed point, rounded half up, made
+# monotone over the chunk's steps (nd_token_positions); every char of a token's word carries it; a char of chunk
+# ci of a read sits at ci * src_seq_stride + m.  A column of the vote gets the mean (integer division) of its
+# votes' positions, and the read the running maximum of its columns.  Integers throughout, so the device
+# (assembly.hip, nd_assemble_reads_p) gives the same values.  The call itself is never changed.
+POS_ONE = 1 << 24  # the fixed-point weight of probability 1
+
+
+def token_positions(attn_rows, span) -> np.ndarray:
+    """The positions m [..., S] (int32) of the attention rows ``attn_rows`` [..., S, T] (float32 probabilities,
+    as a translate call returns them with return_attn) of chunks with ``span`` (an int, or an array over the
+    leading axes): per row, with q_t = 0 unless a[t] > 0, 2^24 when a[t] >= 1, else
+    floor(float64(a[t]) * 2^24 + 0.5) over t < min(span, T), Q = sum q_t and M = sum q_t t, the centroid
+    c = (2 M + Q) // (2 Q) (0 when Q is 0); then the running maximum of c over the steps."""
+    a = np.asarray(attn_rows, np.float32)
+    if a.ndim < 2:
+        raise ValueError("attention rows must be [..., S, T]")
+    T = a.shape[-1]
+    t = np.arange(T, dtype=np.uint64)
+    n = np.minimum(np.maximum(np.asarray(span, np.int64), 0), T)
+    inside = np.arange(T) < n[..., None, None]
+    with np.errstate(invalid="ignore"):
+        live = inside & (a > 0)  # False for NaN, negatives and -0
+        one = live & (a >= 1)
+    v = np.where(live & ~one, a, np.float32(0)).astype(np.float64)
+    q = np.where(one, np.uint64(POS_ONE), np.floor(v * 16777216.0 + 0.5).astype(np.uint64))
+    Q = q.sum(-1, dtype=np.uint64)
+    M = (q * t).sum(-1, dtype=np.uint64)
+    c = np.where(Q > 0, (np.uint64(2) * M + Q) // np.maximum(np.uint64(2) * Q, np.uint64(1)), np.uint64(0))
+    return np.maximum.accumulate(c.astype(np.int64), axis=-1).astype(np.int32)
+
+
+def column_position(n, P):
+    """The position of columns with ``n`` votes whose absolute positions sum to ``P`` (ints or integer arrays):
+    P // n, and 0 where n is 0; int or int64 array."""
+    n64, p64 = np.asarray(n, np.int64), np.asarray(P, np.int64)
+    col = np.where(n64 > 0, p64 // np.maximum(n64, 1), 0).astype(np.int64)
+    return int(col) if col.ndim == 0 else col
+
+
+def _valid_positions(bpreads, positions, src_seq_stride: int):
+    """The absolute positions of simple_assembly's ``valid`` chunks, one int64 array per chunk: chunk ci of
+    ``bpreads`` (empty ones counted) adds ci * src_seq_stride to its chunk-relative ``positions[ci]``."""
+    if len(positions) != len(bpreads):
+        raise ValueError("one position array per chunk")
+    return [np.asarray(p, np.int64).reshape(-1) + ci * int(src_seq_stride)
+            for ci, (x, p) in enumerate(zip(bpreads, positions)) if x[0] != ""]
+
+
+def _add_count_p(consensus, psum, start, segment, p):
+    """_add_count, each vote's position added to ``psum`` of its column."""
+    if len(p) != len(segment):
+        raise ValueError("a chunk of %d bases with %d positions" % (len(segment), len(p)))
+    if start < 0:
+        segment, p = segment[-start:], p[-start:]
+        start = 0
+    for i, base in enumerate(segment):
+        consensus[BASE_DICT[base.upper()]][start + i] += 1
+        psum[start + i] += p[i]
+
+
+def simple_assembly_p(bpreads, positions, src_seq_stride: int):
+    """simple_assembly with flag_intersection, line for line, with the sums [length] (int64) of the votes'
+    absolute positions beside the counts: (consensus, psum)."""
+    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
+    vp = _valid_positions(bpreads, positions, src_seq_stride)
+    consensus = np.zeros([len(BASE_KEYS), 1000])
+    psum = np.zeros(1000, np.int64)
+    pos = 0
+    length = 0
+    census_len = 1000
+    for indx, bpread in enumerate(valid):
+        if indx == 0:
+            _add_count_p(consensus, psum, 0, bpread, vp[0])
+            continue
+        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
+        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
+        disp = match_block[0] - match_block[1]
+        if disp + pos + len(valid[indx]) > census_len:
+            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
+            psum = np.pad(psum, (0, 1000), mode="constant", constant_values=0)
+            census_len += 1000
+        _add_count_p(consensus, psum, pos + disp, valid[indx], vp[indx])
+        pos += disp
+        length = max(length, pos + len(valid[indx]))
+    return consensus[:, :length], psum[:length]
+
+
+def assemble_read_p(all_predictions, positions, src_seq_length: int, src_seq_stride: int):
+    """assemble_read with per-base signal positions: (sequence, read positions uint32 [len(sequence)]).
+    ``positions``: per chunk, the chunk-relative position (Translator.translate_reads(..., moves=True)) of
+    every char of its x[0] with the spaces removed; chunk ci's offset ci * src_seq_stride is added here, ci
+    counting the empty chunks too.  A column's position is the sum of its votes' positions // their number (0
+    with no vote), a read's the running maximum of its columns.  The sequence is assemble_read's, and what
+    assemble_read raises is raised here."""
+    if src_seq_stride < src_seq_length:
+        consensus, psum = simple_assembly_p(all_predictions, positions, src_seq_stride)
+        win = np.argmax(consensus, axis=0)
+        n = consensus.sum(axis=0).astype(np.int64)
+        col = column_position(n, psum)
+        return index2base(win), np.maximum.accumulate(col).astype(np.uint32)
+    # the concatenation branch: every base is its own column, n = 1 and P = its position
+    seq = simple_assembly(all_predictions, flag_intersection=False)
+    vp = _valid_positions(all_predictions, positions, src_seq_stride)
+    p = np.concatenate(vp) if vp else np.zeros(0, np.int64)
+    if p.size != len(seq):
+        raise ValueError("a read of %d bases with %d positions" % (len(seq), p.size))
+    return seq, np.maximum.accumulate(p).astype(np.uint32)
+
+
+def moves_record(name: str, sequence: str, rpos) -> str:
+    """The three lines of result/<read>.moves: the header, the sequence (the .fasta's) and the read positions
+    as comma-separated decimals, one per base (an empty line for an empty read)."""
+    rpos = np.asarray(rpos).reshape(-1)
+    if rpos.size != len(sequence):
+        raise ValueError("a read of %d bases with %d positions" % (len(sequence), rpos.size))
+    return ">%s\n%s\n%s\n" % (name, sequence, ",".join("%d" % int(v) for v in rpos))
+
+
 # ---------------------------------------------------------------- assembly on the device (-assembly gpu)
 ASM_STATUS_LONG = 1   # include/nanodec.h nd_assemble_reads: a chunk of 200 or more chars (difflib autojunk)
 ASM_STATUS_CHAR = 2   # a char whose upper case is not in BASE_KEYS
 
 
-def pack_assembly_input(reads, weights=None, mod_weights=None):
+def pack_assembly_input(reads, weights=None, mod_weights=None, positions=None, src_seq_stride=None):
     """The input of nd_assemble_reads for a group of reads (each the
     all_predictions assemble_read takes): every chunk's x[0] with the spaces
     removed, as ASCII bytes, concatenated.  Returns (bases uint8 [total],
@@ -448,8 +569,14 @@ def pack_assembly_input(reads, weights=None, mod_weights=None):
     With ``weights`` (per read, per chunk, the uint16 weight of every char of that string) a fifth value
     follows: qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q).  With
     ``mod_weights`` too (laid out like ``weights``, which it needs) a sixth: mw uint16 [total], each byte's
-    modification weight (nd_assemble_reads_m)."""
-    lens, parts, host, wparts, mparts = [], [], [], [], []
+    modification weight (nd_assemble_reads_m).  With ``positions`` instead (per read, per chunk, the
+    chunk-relative position of every char; not beside ``weights``) and ``src_seq_stride`` a fifth value follows:
+    bp uint32 [total], each byte's absolute position, chunk ci of its read at ci * src_seq_stride
+    (nd_assemble_reads_p)."""
+    lens, parts, host, wparts, mparts, pparts, pci = [], [], [], [], [], [], []
+    if positions is not None:
+        if weights is not None or src_seq_stride is None or len(positions) != len(reads):
+            raise ValueError("one list of positions per read, with src_seq_stride and without weights")
     if weights is not None and len(weights) != len(reads):
         raise ValueError("one list of weights per read")
     if mod_weights is not None and (weights is None or len(mod_weights) != len(reads)):
@@ -481,6 +608,15 @@ def pack_assembly_input(reads, weights=None, mod_weights=None):
                 if w.size != len(st):
                     raise ValueError("a chunk of %d bases with %d modification weights" % (len(st), w.size))
                 mparts.append(w)
+        if positions is not None:
+            if len(positions[r]) != len(strs):
+                raise ValueError("one position array per chunk")
+            for ci, (st, w) in enumerate(zip(strs, positions[r])):
+                w = np.asarray(w).reshape(-1)
+                if w.size != len(st):
+                    raise ValueError("a chunk of %d bases with %d positions" % (len(st), w.size))
+                pparts.append(w)
+                pci.append(ci)
         parts.append(raw)
         lens.extend(len(s) for s in strs)
         read_off[r + 1] = read_off[r] + len(strs)
@@ -489,6 +625,11 @@ def pack_assembly_input(reads, weights=None, mod_weights=None):
     if chunk_off[-1] >= 2 ** 31:
         raise ValueError("more than 2^31 - 1 bases in one assembly group")
     bases = np.frombuffer(bytearray(b"").join(parts), np.uint8)  # a bytearray: writable, as torch.from_numpy wants
+    if positions is not None:
+        # the chunks' offsets in one pass: ci * stride repeated over each chunk's chars
+        off = np.repeat(np.asarray(pci, np.int64) * int(src_seq_stride), [w.size for w in pparts])
+        bp = (np.concatenate(pparts).astype(np.int64) + off).astype(np.uint32) if pparts else np.zeros(0, np.uint32)
+        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, bp
     if weights is None:
         return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
     qw = np.concatenate(wparts) if wparts else np.zeros(0, np.uint16)
@@ -498,11 +639,13 @@ def pack_assembly_input(reads, weights=None, mod_weights=None):
     return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw, mw
 
 
-def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
+def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None, bp=None):
     """One nd_assemble_reads call on the CURRENT stream of ``device``:
     (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host.  With ``qw`` (uint16 [total], each
     base's weight) the call is nd_assemble_reads_q and qual uint8 [total] follows; with ``mw`` too (uint16 [total],
-    each base's modification weight) it is nd_assemble_reads_m and ml uint8 [total] follows qual."""
+    each base's modification weight) it is nd_assemble_reads_m and ml uint8 [total] follows qual.  With ``bp``
+    instead (uint32 [total], each base's absolute position) it is nd_assemble_reads_p and rpos uint32 [total]
+    follows status."""
     import ctypes
 
     import torch
@@ -513,7 +656,10 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
     L = _lib.lib()
     if mw is not None and qw is None:
         raise ValueError("mw needs qw")
-    work_bytes = int((L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes
+    if bp is not None and qw is not None:
+        raise ValueError("bp goes with the plain call only")
+    work_bytes = int((L.nd_assemble_reads_p_work_bytes if bp is not None else
+                      L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes
                       if mw is None else L.nd_assemble_reads_m_work_bytes)(C, total))
     with torch.cuda.device(dev):
         off_d = _pinned(np.concatenate([chunk_off, read_off])).to(dev, non_blocking=True)
@@ -523,7 +669,15 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        if qw is None:
+        if bp is not None:
+            if bp.dtype != np.uint32 or bp.size != total:
+                raise ValueError("bp must hold one uint32 per base")
+            bp_d = _pinned(bp.view(np.int32)).to(dev, non_blocking=True)  # the bits
+            rpos_d = torch.empty(total, dtype=torch.int32, device=dev)
+            _lib.check(L.nd_assemble_reads_p(p(bases_d), p(bp_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
+                                             p(rpos_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
+                       "nd_assemble_reads_p")
+        elif qw is None:
             _lib.check(L.nd_assemble_reads(p(bases_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
                                            p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
                        "nd_assemble_reads")
@@ -546,6 +700,8 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
                                                  work_bytes, stream), "nd_assemble_reads_m")
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         seq = seq_d.cpu().numpy()
+        if bp is not None:
+            return seq, out[0], out[1], rpos_d.cpu().numpy().view(np.uint32)
         if mw is not None:
             return seq, out[0], out[1], qual_d.cpu().numpy(), ml_d.cpu().numpy()
         if qw is not None:
@@ -554,7 +710,7 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None):
 
 
 def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None, stats=None,
-                   defer_errors: bool = False, weights=None, mod_weights=None):
+                   defer_errors: bool = False, weights=None, mod_weights=None, positions=None):
     """assemble_read for a group of reads: one string per read.
 
     ``device=None``, or ``src_seq_stride >= src_seq_length`` (translate.py's
@@ -574,8 +730,52 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
     nd_assemble_reads_q, and the host path and the fallback are assemble_read_q.
     ``mod_weights`` (beside ``weights``, laid out like them; see assemble_read_m): every read yields (sequence,
     quality string, ml uint8 array), the device call is nd_assemble_reads_m, and the host path and the fallback
-    are assemble_read_m."""
+    are assemble_read_m.
+    ``positions`` (per read, per chunk, the chunk-relative signal position of every char of the chunk's string;
+    see assemble_read_p): every read yields (sequence, read positions uint32 array), the device call is
+    nd_assemble_reads_p, and the host path and the fallback are assemble_read_p.  Beside ``weights`` the
+    positions follow as the last entry, (sequence, quality string[, ml], read positions), from a second pass
+    over the same reads (a second device call: the forms are not multiplied); ``stats`` counts the reads once."""
     reads = list(reads)
+    if positions is not None and weights is not None:
+        first = assemble_reads(reads, src_seq_length, src_seq_stride, device, stats, defer_errors, weights,
+                               mod_weights)
+        second = assemble_reads(reads, src_seq_length, src_seq_stride, device, None, defer_errors,
+                                positions=positions)
+        return [None if a is None or b is None else a + (b[1],) for a, b in zip(first, second)]
+    if positions is not None:
+        positions = list(positions)
+        if len(positions) != len(reads):
+            raise ValueError("one list of positions per read")
+        one = lambda r: assemble_read_p(reads[r], positions[r], src_seq_length, src_seq_stride)  # noqa: E731
+        if device is None or src_seq_stride >= src_seq_length:
+            return [one(r) for r in range(len(reads))]
+        R = len(reads)
+        bases, chunk_off, read_off, host, bp = pack_assembly_input(reads, positions=positions,
+                                                                   src_seq_stride=src_seq_stride)
+        out = [("", np.zeros(0, np.uint32)) for _ in range(R)]
+        todo = set(host)
+        if bases.size:
+            seq, seq_len, status, rpos = _assemble_device(bases, chunk_off, read_off, device, bp=bp)
+            raw = seq.tobytes()
+            start = chunk_off[read_off[:-1]]
+            for r in range(R):
+                if status[r] != 0:
+                    todo.add(r)
+                elif seq_len[r] > 0:
+                    out[r] = (raw[start[r]: start[r] + seq_len[r]].decode("ascii"),
+                              rpos[start[r]: start[r] + seq_len[r]].copy())
+        if stats is not None:
+            stats["reads"] = stats.get("reads", 0) + R
+            stats["fallback"] = stats.get("fallback", 0) + len(todo)
+        for r in sorted(todo):
+            try:
+                out[r] = one(r)
+            except Exception:
+                if not defer_errors:
+                    raise
+                out[r] = None
+        return out
     if mod_weights is not None and weights is None:
         raise ValueError("mod_weights need weights")
     if weights is None:

@@ -86,6 +86,11 @@ def translate_parser() -> argparse.ArgumentParser:
               "written as C, the qualities of -fastq, and SAM MM:Z:C+m. / ML:B:C tags in the header with the "
               "model's P(methylated | C) 0..255 of every C, carried through the assembly vote; the other outputs "
               "are unchanged; not together with -attn_debug")
+    _add(g, "moves", action="store_true",
+         help="also write result/<read>.moves: the header, the sequence and, comma separated, the signal sample "
+              "each base was called at (the centroid of the last decoder layer's head-0 context attention, carried "
+              "through the assembly vote and made monotone along the read); combines with -fastq, -mod_probs, "
+              "-frontend gpu and -assembly gpu; the other outputs are unchanged; not together with -attn_debug")
     return p
 
 

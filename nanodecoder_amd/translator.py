@@ -209,13 +209,14 @@ class Translator(object):
         return max(1, int(getattr(self.engine, "lanes", 1)))
 
     def _submit(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
-                attn: bool = False, qual: bool = False, mods: bool = False):
+                attn: bool = False, qual: bool = False, mods: bool = False, moves: bool = False):
         """Stage up to max_batch chunks with their reference spans (and, for
         the classic Beam, their reference batch ids) and enqueue the engine
         call.  Greedy and sampling calls return before the device finishes;
         ``_finish`` collects the results.  ``qual``: the token weights of each
         chunk's best hypothesis are wanted too, ``mods`` (with ``qual``) their
-        modification weights as well (see stream_reads)."""
+        modification weights as well, ``moves`` the tokens' signal positions
+        (see stream_reads)."""
         n = len(chunks)
         lens = np.array([len(c) for c in chunks], np.int32)
         if (lens < 1).any():
@@ -231,12 +232,13 @@ class Translator(object):
         L[:n], S[:n] = lens, spans
         if dev_in is not None:
             sig, L, S = dev_in
-        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual, **({"mods": True} if mods else {}))
-        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual, mods)
+        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual, **({"mods": True} if mods else {}),
+                            **({"moves": True} if moves else {}))
+        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual, mods, moves)
         return job
 
     def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs, qual: bool = False,
-                 mods: bool = False):
+                 mods: bool = False, moves: bool = False):
         """The engine call for one staged batch (signal [B, T], chunk lengths
         and spans [B]; the first n rows are chunks), its results copied to
         pinned host buffers on the call's own stream.  ``qual``: a greedy or
@@ -244,8 +246,13 @@ class Translator(object):
         weights (nd_token_weights) follow it on its stream; a beam call's
         inputs are kept for the scoring pass of ``_beam_weights``.  ``mods``:
         the tokens' modification weights (nd_token_mod_weights) follow the
-        weights, from the same log-probs."""
-        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual, mods=mods)
+        weights, from the same log-probs.  ``moves``: the call also returns
+        its attention, the tokens' positions (nd_token_positions, of
+        hypothesis 0 for a beam call) follow it on its stream, and only those
+        [B, S] positions are copied out, not the attention."""
+        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual, mods=mods, moves=moves)
+        if moves:
+            attn = True  # the engine call's return_attn; job["attn"] stays what the caller asked for
         # without qualities the engine sees exactly the arguments it always has
         want = dict(return_logp=True) if qual else {}
         if self.beam_size == 1:
@@ -264,6 +271,8 @@ class Translator(object):
                 r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"], **lane)
                 if mods:
                     r["mod_weights"] = self.engine.token_mod_weights(r["tokens"], r["logp"], *self._cm_ids(), **lane)
+            if moves:
+                self._positions(r, S)
             job.update(kind="greedy", r=r)
         else:
             # reference batches: the chunks of one group, sorted by length
@@ -298,6 +307,8 @@ class Translator(object):
                     alpha=gs.alpha, max_len=self.max_length, min_len=self.min_length,
                     coverage_penalty=gs.coverage_penalty, beta=gs.beta, stepwise_penalty=self.stepwise_penalty,
                     block_ngram_repeat=self.block_ngram_repeat, ignore_ids=exclusion, cut=cut, return_attn=attn)
+            if moves:
+                self._positions(r, S, hyp0=True)
             job.update(kind="beam", r=r, grp=grp, sorted_rows=sorted_rows, cut=cut)
             if qual:
                 job["eng_in"] = (sig, L, S)
@@ -305,7 +316,15 @@ class Translator(object):
             self._copy_out(job)
         return job
 
-    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow", "weights", "mod_weights")
+    _HOST_KEYS = ("tokens", "scores", "lens", "attn", "done_step", "overflow", "weights", "mod_weights", "positions")
+
+    def _positions(self, r, spans, hyp0: bool = False):
+        """The token positions [B, S] of a call's result ``r`` (Engine.token_positions on the call's stream, its
+        EnginePool lane), in r["positions"]; the attention they came from is dropped from the result, so it is
+        not copied to the host."""
+        lane = {"lane": r["lane"]} if "lane" in r else {}
+        r["positions"] = self.engine.token_positions(r["attn"], spans, hyp0=hyp0, **lane)
+        r["attn"] = None
 
     def _cm_ids(self):
         """(id of "C", id of "M") in the target vocabulary."""
@@ -368,14 +387,19 @@ class Translator(object):
             tok, sc, at, ov = self._host(job, "tokens", "scores", "attn", "overflow")
             if self._overflowed(job, ov):
                 return self._rerun_exact(job)
+            moves = job.get("moves", False)
+            ps = self._host(job, "positions")[0] if moves else None
+            tail = (lambda i: (self._char_weights(tok[i].tolist(), ps[i], np.int32),)) if moves else (lambda i: ())
             if qual:
                 w = self._host(job, "weights")[0].view(np.uint16)
                 if mods:
                     mw = self._host(job, "mod_weights")[0].view(np.uint16)
                     return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]),
-                             self._char_weights(tok[i].tolist(), mw[i])) for i in range(n)]
-                return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]))
+                             self._char_weights(tok[i].tolist(), mw[i])) + tail(i) for i in range(n)]
+                return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i])) + tail(i)
                         for i in range(n)]
+            if moves:
+                return [([float(sc[i])], [tok[i].tolist()]) + tail(i) for i in range(n)]
             for i in range(n):
                 if attn:  # results["attention"]: rows cut at the chunk's length (translator.py:491-501)
                     out.append(([float(sc[i])], [tok[i].tolist()], [at[i, :, : lens[i]]]))
@@ -389,6 +413,7 @@ class Translator(object):
         w = self._beam_weights(job, tok, ln) if qual else None
         if mods:
             w, mw = w
+        ps = self._host(job, "positions")[0] if job.get("moves") else None
         for i in range(n):
             o = ([float(sc[i, k]) for k in range(self.n_best)],
                  [tok[i, k, : ln[i, k]].tolist() for k in range(self.n_best)])
@@ -396,6 +421,8 @@ class Translator(object):
                 o = o + (self._char_weights(o[1][0], w[i]),)
             if mods:
                 o = o + (self._char_weights(o[1][0], mw[i]),)
+            if ps is not None:
+                o = o + (self._char_weights(o[1][0], ps[i], np.int32),)
             if attn:
                 atts = []
                 for k in range(self.n_best):
@@ -454,17 +481,17 @@ class Translator(object):
             return w.cpu().numpy().view(np.uint16), mw.cpu().numpy().view(np.uint16)
         return w.cpu().numpy().view(np.uint16)
 
-    def _char_weights(self, toks, w) -> np.ndarray:
+    def _char_weights(self, toks, w, dtype=np.uint16) -> np.ndarray:
         """The weight of every character of a hypothesis' string with the spaces removed (uint16): the
         tokens up to the first EOS as _tokens_to_sent cuts them, each character of a token's word carrying
-        the token's weight."""
+        the token's weight.  The tokens' positions (int32) are spread the same way."""
         out = []
         for t, wt in zip(toks, w):
             word = self.cfg.itos[t]
             if t == self.cfg.eos_idx:
                 break
             out.extend([int(wt)] * len(word.replace(" ", "")))
-        return np.asarray(out, np.uint16)
+        return np.asarray(out, dtype)
 
     def _run(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
              attn: bool = False):
@@ -611,8 +638,13 @@ class Translator(object):
             self._check_supported(qualities=True, **({"mods": True} if mods else {}))
         return bool(qualities)
 
+    def _want_moves(self, moves: bool, attn_debug: bool = False) -> bool:
+        if moves and attn_debug:
+            raise ValueError("signal positions are not available together with attn_debug")
+        return bool(moves)
+
     def stream_reads(self, reads: Iterable[Sequence], batch_size: int, attn_debug: bool = False,
-                     qualities: bool = False, mods: bool = False):
+                     qualities: bool = False, mods: bool = False, moves: bool = False):
         """Generator over many reads (any iterable of chunk lists): chunks are
         packed across reads into engine batches of max_batch, one batch (one
         per EnginePool lane) stays in flight on the device while the next is
@@ -628,9 +660,15 @@ class Translator(object):
         a second, teacher-forced pass (_beam_weights).  ``mods`` (a vocabulary
         with C and M; implies ``qualities``): a fourth entry follows, the uint16
         modification weights of the same characters (frontend.assemble_read_m
-        turns them into a read's ML values), from the same log-probs."""
+        turns them into a read's ML values), from the same log-probs.  ``moves``:
+        one more trailing entry, the chunk-relative signal position (int32) of
+        the same characters (frontend.assemble_read_p turns them into a read's
+        positions): the call returns its head-0 context attention and
+        nd_token_positions reduces it on the call's stream, in every search
+        mode (a beam call's hypothesis 0; no scoring pass)."""
         import collections
         qualities = self._want_qualities(qualities, attn_debug, mods)
+        moves = self._want_moves(moves, attn_debug)
         cap = self.engine.max_batch
         depth = self._depth()
         pending, inflight = [], collections.deque()
@@ -649,7 +687,8 @@ class Translator(object):
 
         def submit(items):
             return self._submit([g[2] for g in items], [g[3] for g in items], [g[4] for g in items],
-                                attn=attn_debug, qual=qualities, **({"mods": True} if mods else {})), items
+                                attn=attn_debug, qual=qualities, **({"mods": True} if mods else {}),
+                                **({"moves": True} if moves else {})), items
 
         for ri, read in enumerate(reads):
             chunks = [parse_chunk(c) for c in read]
@@ -677,34 +716,38 @@ class Translator(object):
                 yield r, results.pop(r)
 
     def translate_reads(self, reads: Sequence[Sequence], batch_size: int, attn_debug: bool = False,
-                        qualities: bool = False, mods: bool = False):
+                        qualities: bool = False, mods: bool = False, moves: bool = False):
         """Translate many reads (stream_reads); returns per read
         (all_scores, all_predictions) as translate() does; with ``qualities``
         (all_scores, all_predictions, all_weights), all_weights per chunk the
         uint16 weights of its best hypothesis (see stream_reads); with ``mods``
-        (which implies ``qualities``) also all_mod_weights, laid out like all_weights."""
+        (which implies ``qualities``) also all_mod_weights, laid out like all_weights; with ``moves`` a last
+        entry all_positions, per chunk the int32 chunk-relative signal positions of the same characters."""
         results = [None] * len(reads)
         qualities = bool(qualities or mods)
         for ri, res in self.stream_reads(reads, batch_size, attn_debug, **({"qualities": True} if qualities else {}),
-                                         **({"mods": True} if mods else {})):
+                                         **({"mods": True} if mods else {}), **({"moves": True} if moves else {})):
             results[ri] = res
-        return self._report(results, attn_debug, qualities=qualities, mods=mods)
+        return self._report(results, attn_debug, qualities=qualities, mods=mods, **({"moves": True} if moves else {}))
 
     def translate_raw_reads(self, raws: Sequence[np.ndarray], batch_size: int, normalization: str = "median",
                             src_seq_length: int = 512, src_seq_stride: int = 512, qualities: bool = False,
-                            mods: bool = False):
+                            mods: bool = False, moves: bool = False):
         """translate_reads on raw reads with the signal front end on the
         device (stream_raw_reads); returns per read (all_scores,
-        all_predictions), with ``qualities`` also all_weights, with ``mods`` also all_mod_weights."""
+        all_predictions), with ``qualities`` also all_weights, with ``mods`` also all_mod_weights, with ``moves``
+        a last entry all_positions."""
         results = [None] * len(raws)
         qualities = bool(qualities or mods)
         for ri, res in self.stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
                                              **({"qualities": True} if qualities else {}),
-                                             **({"mods": True} if mods else {})):
+                                             **({"mods": True} if mods else {}),
+                                             **({"moves": True} if moves else {})):
             results[ri] = res
-        return self._report(results, False, qualities=qualities, mods=mods)
+        return self._report(results, False, qualities=qualities, mods=mods, **({"moves": True} if moves else {}))
 
-    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False, mods: bool = False):
+    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False, mods: bool = False,
+                moves: bool = False):
         """Per read (all_scores, all_predictions) from per-chunk results, with
         the reference's verbose / -dump_beam / report_score side outputs
         (translate/translator.py:255-369).  gold (translate with tgt): per chunk
@@ -713,7 +756,7 @@ class Translator(object):
         counter = 0
         pred_score_total, pred_words_total = 0.0, 0
         for r in results:
-            all_scores, all_predictions, all_weights, all_mods = [], [], [], []
+            all_scores, all_predictions, all_weights, all_mods, all_moves = [], [], [], [], []
             for res in r:
                 scores, toks = res[0], res[1]
                 sents = [self._tokens_to_sent(t) for t in toks]
@@ -725,6 +768,8 @@ class Translator(object):
                     all_weights.append(res[2])
                 if mods:
                     all_mods.append(res[3])
+                if moves:  # after the weights and modification weights when those are present
+                    all_moves.append(res[2 + int(bool(qualities)) + int(bool(mods))])
                 pred_score_total += scores[0]
                 pred_words_total += len(sents[0])
                 if self.verbose:
@@ -743,7 +788,7 @@ class Translator(object):
                     else:
                         os.write(1, msg.encode("utf-8"))
             ret.append((all_scores, all_predictions) + ((all_weights,) if qualities else ()) +
-                       ((all_mods,) if mods else ()))
+                       ((all_mods,) if mods else ()) + ((all_moves,) if moves else ()))
         if self.dump_beam:
             # translator.py:365-368 dumps the beam trace accumulator.  (The
             # reference reads it through a `self.translator` attribute the
@@ -765,7 +810,8 @@ class Translator(object):
             return self.engine.engines[self.engine._next].stream
         return torch.cuda.current_stream(self.engine.device)
 
-    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False, mods: bool = False):
+    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False, mods: bool = False,
+                    moves: bool = False):
         """One engine batch from raw reads: chunk descriptors ``items`` =
         (read, chunk, start, length, span, reference batch) and the reads
         they cut (``batch_reads``: read -> float64 samples).  The front end
@@ -791,13 +837,14 @@ class Translator(object):
                                               normalization, B, T, self.engine.device)
             ls_d = torch.from_numpy(ls).pin_memory().to(self.engine.device, non_blocking=True)
             job = self._enqueue(sig, ls_d[:B], ls_d[B:], B, n, lens, [it[5] for it in items], False,
-                                (sig, ls_d, keep), qual, **({"mods": True} if mods else {}))
-        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual, mods)
+                                (sig, ls_d, keep), qual, **({"mods": True} if mods else {}),
+                                **({"moves": True} if moves else {}))
+        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual, mods, moves)
         return job
 
     def stream_raw_reads(self, raws: Iterable, batch_size: int, normalization: str = "median",
                          src_seq_length: int = 512, src_seq_stride: int = 512, arrays: bool = False,
-                         qualities: bool = False, mods: bool = False):
+                         qualities: bool = False, mods: bool = False, moves: bool = False):
         """stream_reads on RAW reads (float64 sample arrays, as
         frontend.read_raw returns them) with extract_fast5_raw's
         normalisation and windowing (utils/labelop.py:194-243) on the device:
@@ -813,14 +860,17 @@ class Translator(object):
         tokens' weights [n_chunks, max_length] uint16 (one per token, EOS and
         what follows it included).  ``mods`` as in stream_reads; with
         ``arrays`` a fifth array, the tokens' modification weights, laid out
-        like the fourth."""
+        like the fourth.  ``moves`` as in stream_reads; with ``arrays`` a last
+        array follows, the tokens' positions [n_chunks, max_length] int32."""
         import collections
 
         from . import frontend
         if arrays and self.beam_size != 1:
             raise ValueError("arrays=True is for greedy / sampling decoding")
         qualities = self._want_qualities(qualities, mods=mods)
+        moves = self._want_moves(moves)
         n_w = (2 if mods else 1) if qualities else 0  # uint16 arrays per read with ``arrays``
+        n_p = 1 if moves else 0  # int32 position arrays behind them
         cap = self.engine.max_batch
         depth = self._depth()
         pending, batch_reads, inflight = [], {}, collections.deque()
@@ -849,20 +899,23 @@ class Translator(object):
         def flush():
             nonlocal pending, batch_reads
             inflight.append((self._submit_raw(pending, batch_reads, normalization, qualities,
-                                              **({"mods": True} if mods else {})), pending))
+                                              **({"mods": True} if mods else {}),
+                                              **({"moves": True} if moves else {})), pending))
             pending, batch_reads = [], {}
 
         for ri, raw in enumerate(raws):
             raw = np.asarray(raw, dtype=np.float64).reshape(-1)
             if raw.size == 0:
                 empty = (np.zeros((0, self.max_length), np.int32), np.zeros(0, np.float32)) + \
-                    tuple(np.zeros((0, self.max_length), np.uint16) for _ in range(n_w))
+                    tuple(np.zeros((0, self.max_length), np.uint16) for _ in range(n_w)) + \
+                    tuple(np.zeros((0, self.max_length), np.int32) for _ in range(n_p))
                 yield (ri,) + empty if arrays else (ri, [])
                 continue
             wins = frontend.windows(int(raw.size), src_seq_length, src_seq_stride)
             if arrays:
                 results[ri] = (np.empty((len(wins), self.max_length), np.int32), np.empty(len(wins), np.float32)) + \
-                    tuple(np.empty((len(wins), self.max_length), np.uint16) for _ in range(n_w))
+                    tuple(np.empty((len(wins), self.max_length), np.uint16) for _ in range(n_w)) + \
+                    tuple(np.empty((len(wins), self.max_length), np.int32) for _ in range(n_p))
             else:
                 results[ri] = [None] * len(wins)
             remaining[ri] = len(wins)
@@ -886,16 +939,19 @@ class Translator(object):
 
     def _finish_arrays(self, job):
         """(tokens [n, S], scores [n]) numpy of a greedy / sampling call; its tokens' weights [n, S] uint16
-        follow when the call was submitted with qualities, then their modification weights when with mods."""
+        follow when the call was submitted with qualities, then their modification weights when with mods, then
+        their positions [n, S] int32 when with moves."""
         tok, sc, ov = self._host(job, "tokens", "scores", "overflow")
         if self._overflowed(job, ov):
             return self._rerun_exact(job, self._finish_arrays)
+        tail = (self._host(job, "positions")[0][: job["n"]],) if job.get("moves") else ()
         if job.get("mods"):
             w, mw = self._host(job, "weights", "mod_weights")
-            return tok[: job["n"]], sc[: job["n"]], w.view(np.uint16)[: job["n"]], mw.view(np.uint16)[: job["n"]]
+            return (tok[: job["n"]], sc[: job["n"]], w.view(np.uint16)[: job["n"]],
+                    mw.view(np.uint16)[: job["n"]]) + tail
         if job.get("qual"):
-            return tok[: job["n"]], sc[: job["n"]], self._host(job, "weights")[0].view(np.uint16)[: job["n"]]
-        return tok[: job["n"]], sc[: job["n"]]
+            return (tok[: job["n"]], sc[: job["n"]], self._host(job, "weights")[0].view(np.uint16)[: job["n"]]) + tail
+        return (tok[: job["n"]], sc[: job["n"]]) + tail
 
     def translate_batch(self, batch, data=None, attn_debug=False, fast=False):
         """translate/translator.py:505-540 on a batch object with
