@@ -123,6 +123,7 @@ SIGNATURES = {
     "nd_op_dec_bank_d8": (_I, [_P, _P, _P, _P, _P, _P, ctypes.c_float, _P, _I, _I, _P, _I, _P]),
     "nd_bank_form": (_I, [_P]),
     "nd_op_lstm_layer": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
+    "nd_op_lstm_layer_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
     "nd_op_enc_attention": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "nd_op_enc_layer0": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "nd_op_dec_self_attention": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P]),

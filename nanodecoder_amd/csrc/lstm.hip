@@ -1,10 +1,13 @@
 // NanoEncoder BiLSTM recurrence on gfx950 (encoder/nano_encoder.py:79-124,
 // nn.LSTM through onmt/utils/rnn_factory.py:8-17, packed sequences).
 //
-// One workgroup = NS sequences (16, 8 or 4; default 4, ND_LSTM_SEQ) x one
-// direction, for ALL time steps: the recurrence never leaves the CU, so a
-// step costs one 16x512x128 product + one LDS exchange of h instead of a
-// kernel launch.  W_hh^T (512 x 128) is held in REGISTERS across the waves:
+// One workgroup = NS sequences x one direction, for ALL time steps: the
+// recurrence never leaves the CU, so a step costs one 16x512x128 product +
+// one LDS exchange of h instead of a kernel launch.  The launcher (lstm_form
+// below) runs NS = 4 in split-fp16 and NS = 16 in exact fp32; the template's
+// NS = 8 and split NS = 16 mappings are instantiated nowhere, and no
+// environment switch selects a form.
+// W_hh^T (512 x 128) is held in REGISTERS across the waves:
 // with 16 waves, wave w owns the four gates (i, f, g, o) of units
 // 8w .. 8w + 7 as two 16-column tiles (i | f, g | o) of MFMA B operands (8
 // waves: 16 units, four tiles), split-fp16 hi/lo on v_mfma_f32_16x16x32_f16
@@ -17,7 +20,8 @@
 
 // Packing semantics (pack_padded_sequence / pad_packed_sequence):
 // sequence b only processes its valid steps; the reverse direction starts
-// at t = len_b - 1.  Outputs at t >= len_b are left as the caller zeroed them.
+// at t = len_b - 1.  Outputs at t >= len_b keep what the caller put there
+// (zeros) or are rewritten with exactly 0 (the FULL loop's unconditional stores).
 //
 // The input projection x_t W_ih^T + b_ih + b_hh is precomputed for all t by a
 // GEMM (layers 1, 2) or computed in-kernel from the scalar sample (layer 0,
@@ -40,7 +44,7 @@ __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x))
 // the cell's activations on the hardware exp (v_exp_f32) and reciprocal
 // (v_rcp_f32, 1 ulp; __frcp_rn lowers to the ~10-instruction IEEE division
 // sequence, and five of them sat on every step's dependent chain); a few ulp
-// from the libm forms; ND_LSTM_LIBM=1 keeps expf / tanhf
+// from the libm forms, which the exact-fp32 form keeps (FAST = false)
 __device__ __forceinline__ float sigm_fast(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float tanh_fast(float x) {
   const float t = __expf(-2.0f * fabsf(x));
@@ -129,7 +133,9 @@ lstm_dir_kernel(const float* __restrict__ xp,      // [B*T, 1024] input projecti
       for (int w = 0; w < NWAVE; ++w) m = fmaxf(m, s_max[w]);
       int ex = 0;
       frexpf(m, &ex);  // m = f * 2^ex, f in [0.5, 1)
-      const int sh = m > 0.f ? 14 - ex : 0;
+      // sh <= 116 keeps 2^sh and 2^-sh / 2^10 finite and normal whatever max |W| is (below 2^-102 the scaled
+      // maximum then falls short of 2^13: such weights move no gate by an fp32 ulp)
+      const int sh = m > 0.f ? min(14 - ex, 116) : 0;
       wsc = ldexpf(1.f, sh);
       unscale = ldexpf(1.f, -sh) / LSTM_HSCALE;
     }

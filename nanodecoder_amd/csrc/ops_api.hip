@@ -239,9 +239,9 @@ int nd_op_dec_mem_attention(const float* qp, const float* mem, const float* sign
                                               .rpc = rpc, .T = T, .ldT = ldT, .grid = grid}, (hipStream_t)stream));
 }
 
-int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
-                     const int32_t* len, int32_t B, int32_t T, float* out, const float* bn_scale,
-                     const float* bn_shift, int32_t layer0, void* stream) {
+static int lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
+                      const int32_t* len, int32_t B, int32_t T, float* out, const float* bn_scale,
+                      const float* bn_shift, int32_t layer0, bool exact, void* stream) {
   if (B < 1 || T < 1 || !whh || !len || !out || (layer0 ? (!signal || !wih0 || !bsum) : !xp))
     return fail(ND_ERR_ARG, "lstm_layer: bad arguments");
   if ((bn_scale == nullptr) != (bn_shift == nullptr))
@@ -249,7 +249,19 @@ int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, co
   return status("lstm_layer",
                 nd::launch_lstm_layer({.xp = xp, .signal = signal, .wih0 = wih0, .bsum = bsum, .whh = whh, .len = len,
                                        .B = B, .T = T, .out = out, .bn_scale = bn_scale, .bn_shift = bn_shift,
-                                       .layer0 = layer0 != 0}, (hipStream_t)stream));
+                                       .layer0 = layer0 != 0, .exact = exact}, (hipStream_t)stream));
+}
+
+int nd_op_lstm_layer(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
+                     const int32_t* len, int32_t B, int32_t T, float* out, const float* bn_scale,
+                     const float* bn_shift, int32_t layer0, void* stream) {
+  return lstm_layer(xp, signal, wih0, bsum, whh, len, B, T, out, bn_scale, bn_shift, layer0, false, stream);
+}
+
+int nd_op_lstm_layer_f32(const float* xp, const float* signal, const float* wih0, const float* bsum, const float* whh,
+                         const int32_t* len, int32_t B, int32_t T, float* out, const float* bn_scale,
+                         const float* bn_shift, int32_t layer0, void* stream) {
+  return lstm_layer(xp, signal, wih0, bsum, whh, len, B, T, out, bn_scale, bn_shift, layer0, true, stream);
 }
 
 int nd_normalize_reads(const double* d_raw, const int64_t* d_offsets, int32_t R, int32_t method, float* d_out,

@@ -1003,19 +1003,21 @@ def op_dec_bank_d8(qp, bank, signal, span, pad_val, out=None, ovf=None, grid=0):
 
 
 def op_lstm_layer(whh, lens, T, xp=None, signal=None, wih0=None, bsum=None, bn_scale=None, bn_shift=None,
-                  out=None):
-    """One BiLSTM layer (both directions) through nd_op_lstm_layer:
+                  out=None, exact=False):
+    """One BiLSTM layer (both directions) through nd_op_lstm_layer, or with
+    exact=True nd_op_lstm_layer_f32 (the exact-fp32 form):
     whh [2, 512, 128], lens [B] int32 on the device.  Layer 0: signal [B, T],
     wih0 / bsum [2, 512]; otherwise xp [B*T, 1024] = x W_ih^T + b_ih + b_hh
-    (fwd | bwd).  Returns out [B*T, 256] (zeros at t >= len)."""
+    (fwd | bwd).  Returns out [B*T, 256] (zeros at t >= len; a given `out`
+    keeps its own values there, or holds exactly 0)."""
     B = lens.shape[0]
     dev = whh.device
     if out is None:
         out = torch.zeros(B * T, 256, dtype=torch.float32, device=dev)
     s = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(_lib.lib().nd_op_lstm_layer(_ptr(xp), _ptr(signal), _ptr(wih0), _ptr(bsum), _ptr(whh), _ptr(lens), B,
-                                           T, _ptr(out), _ptr(bn_scale), _ptr(bn_shift), int(xp is None), s),
-               "nd_op_lstm_layer")
+    name = "nd_op_lstm_layer_f32" if exact else "nd_op_lstm_layer"
+    _lib.check(getattr(_lib.lib(), name)(_ptr(xp), _ptr(signal), _ptr(wih0), _ptr(bsum), _ptr(whh), _ptr(lens), B,
+                                         T, _ptr(out), _ptr(bn_scale), _ptr(bn_shift), int(xp is None), s), name)
     return out
 
 

@@ -1326,9 +1326,11 @@ def test_transformer_encoder_vs_oracle_collinear_embedding(exact):
         assert err < 1e-4, i
 
 
-def test_nano_greedy_vs_oracle_ragged():
+@pytest.mark.parametrize("exact", [False, True])
+def test_nano_greedy_vs_oracle_ragged(exact):
     """NanoEncoder packing: ragged lengths inside one batch (reverse LSTM
-    starts at len-1), B not a multiple of the 16-sequence LSTM group."""
+    starts at len-1), B a multiple neither of the split-fp16 form's 4-sequence
+    LSTM group nor of the 16-sequence one of exact fp32 (exact=True)."""
     ref = _oracle()
     cfg = synth.ModelConfig(encoder_type="nano")
     W = synth.make_weights(cfg, seed=14, eos_bias=-2.0)
@@ -1339,6 +1341,7 @@ def test_nano_greedy_vs_oracle_ragged():
         lens[i] = L
         sig[i, L:] = 0.0
     eng = _engine(cfg, W, max_batch=B, max_steps=30)
+    eng.set_exact_fp32(exact)
     mem = eng.encode(sig, lens, np.full(B, 512, np.int32)).cpu().numpy()
     m = ref.RefModel(cfg, W)
     exp_mem = m.encode(torch.from_numpy(sig), lens).numpy()

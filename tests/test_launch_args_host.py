@@ -67,9 +67,22 @@ def test_gemm_split_refuses_null_image(L):
 ])
 def test_lstm_layer_refuses(L, wih0, bn_scale, bn_shift):
     opt = lambda on: _buf() if on else None
-    rc = L.nd_op_lstm_layer(None, _buf(), opt(wih0), _buf(), _buf(), _buf(), 1, 4, _buf(), opt(bn_scale),
-                            opt(bn_shift), 1, None)
-    _refused(L, rc, b"lstm_layer: ")
+    for entry in (L.nd_op_lstm_layer, L.nd_op_lstm_layer_f32):  # the split-fp16 form and the exact-fp32 one
+        rc = entry(None, _buf(), opt(wih0), _buf(), _buf(), _buf(), 1, 4, _buf(), opt(bn_scale), opt(bn_shift), 1, None)
+        _refused(L, rc, b"lstm_layer: ")
+
+
+@pytest.mark.parametrize("entry", ["nd_op_lstm_layer", "nd_op_lstm_layer_f32"])
+@pytest.mark.parametrize("kw", [dict(B=0), dict(T=0), dict(xp=False), dict(whh=False), dict(len=False),
+                                dict(out=False)])
+def test_lstm_layer_refuses_bad_arguments(L, entry, kw):
+    """no rows, no steps, a null among the projected form's required pointers"""
+    a = dict(xp=True, whh=True, len=True, out=True, B=1, T=4)
+    a.update(kw)
+    opt = lambda on: _buf() if on else None
+    rc = getattr(L, entry)(opt(a["xp"]), None, None, None, opt(a["whh"]), opt(a["len"]), a["B"], a["T"],
+                           opt(a["out"]), None, None, 0, None)
+    _refused(L, rc, b"lstm_layer: bad arguments")
 
 
 # ----------------------------------------------------------------- output head and search entries

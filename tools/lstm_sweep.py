@@ -6,7 +6,8 @@ holds (rows past them are padding), so if a layer's time stays flat as the
 batch (and so the number of workgroups, B / 4 x 2 directions) grows, the
 per-step latency of ONE workgroup is the bound and spreading 256 sequences
 over more workgroups cannot shorten it.  Times one layer (layer-1 form) at
-B = 32 .. 1024 (16 .. 512 workgroups); run once per ND_LSTM_SEQ value.
+B = 32 .. 1024 (16 .. 512 workgroups) in the split-fp16 form, 4 sequences per
+workgroup: the only mapping that form runs (no switch selects another).
     python tools/lstm_sweep.py
 """
 import os
@@ -21,7 +22,7 @@ dev = torch.device("cuda", 0)
 T = 512
 g = torch.Generator(device="cpu").manual_seed(3)
 whh = ((torch.rand(2, 512, 128, generator=g) - 0.5) * 0.2).to(dev)
-ns = int(os.environ.get("ND_LSTM_SEQ", "4"))
+ns = 4  # sequences per workgroup (lstm_form, csrc/lstm.hip)
 for B in (32, 64, 128, 256, 512, 1024):
     xp = torch.randn(B * T, 1024, generator=g).to(dev)
     lens = torch.full((B,), T, dtype=torch.int32, device=dev)
