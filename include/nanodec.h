@@ -216,6 +216,19 @@ int nd_score_targets(nd_ctx* ctx, const float* d_signal, const int32_t* d_len, c
                      const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
                      float* d_score, float* d_tok_logp, float* d_logp, void* stream);
 
+/* nd_score_targets that also returns where each target position looked (forced alignment, DESIGN.md
+ * section 1.7): the same pass with the last decoder layer's context attention in its tapped form.
+ *   d_attn [B, L, T] f32, required: row (b, i) = the head-0 probabilities of that attention at target
+ *          position i, the quantity the translate calls return as attention; entries t >= min(span[b], T)
+ *          are zero; rows i >= gold_len[b] are unspecified, as d_logp's are
+ * Everything else is nd_score_targets: the outputs (bit for bit), the argument checks before the first HIP
+ * call, the ND_SELF_AVERAGE refusal.  The attention buffer the translate_*_attn calls use is allocated by
+ * the first call if the context has none; its own captured graph per (B, T, L).  nd_token_positions turns
+ * d_attn (ld_chunk = L * T) into one signal sample per target position. */
+int nd_score_targets_attn(nd_ctx* ctx, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                          const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
+                          float* d_score, float* d_tok_logp, float* d_logp, float* d_attn, void* stream);
+
 /* Signal front end (utils/labelop.py:194-243, extract_fast5_raw): R raw
  * reads concatenated in d_raw (float64, read r at d_offsets[r] ..
  * d_offsets[r+1]) normalised per read into d_out (float32, same offsets).
@@ -815,6 +828,15 @@ int nd_op_dec_ctx_attention_list(const float* q, const void* kv, int32_t ld, int
 int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
                        const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
                        int32_t Lk, int32_t causal, void* stream);
+/* nd_op_tf_attention of the context attention (causal must be 0: ND_ERR_ARG otherwise) that also stores
+ * head 0's scores after the mask and before the softmax: tap[(c * Lq + i) * ld_tap + t] for i < Lq and
+ * t < min(span[c], Lk) (and up to the end of that key's block of 32, below Lk) = the fp32 score, -1e18 for
+ * a masked key, -inf for a key at or past span[c].  ld_tap >= Lk floats (ND_ERR_ARG otherwise); columns at
+ * or past Lk are never written.  16-byte stores when ld_tap and the buffer's address are multiples of 4
+ * floats, scalar stores otherwise.  out is bit for bit nd_op_tf_attention's. */
+int nd_op_tf_attention_tap(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
+                           const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
+                           int32_t Lk, int32_t causal, float* tap, int32_t ld_tap, void* stream);
 
 /* ---- output head and search, one launch per call ------------------------
  * The kernels that turn log-probs into output (search.hip, head.hpp), each on

@@ -1048,7 +1048,10 @@ static int alloc_score_ws(nd_ctx* c) {
 // (decoder/transformer.py:53-95 with step = None): the row-major GEMMs of the encoder side (split-fp16
 // images of the decoder's fp32 weights, or fp32 MFMA in exact mode: the same G calls) around the two
 // attentions of score.hip; the FFN is the two GEMMs (its hidden in tf_big), in both product modes.
-static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, bool want_logp, hipStream_t s) {
+// want_attn (nd_score_targets_attn): the last layer's context attention is the tapped form, its head-0
+// scores dense [B * L, T] in attn_raw (ensure_attn), turned into probabilities right behind it.
+static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, bool want_logp, bool want_attn,
+                                hipStream_t s) {
   const Model& m = c->m;
   const int M = B * L, D = c->D, F = c->F, Ld = (int)m.dec.size();
   const float pad = (float)c->cfg.pad_idx;
@@ -1057,6 +1060,7 @@ static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, b
   LCHK(nd::launch_tf_embed(c->tf_gold, c->cfg.bos_idx, c->V, m.emb, c->cfg.position_encoding ? m.pe : nullptr, c->tf_x,
                            c->tf_x_part, B, L, s));
   int pnx = 1, pnq = 0, pnm = 0;
+  const auto tap_here = [&](int layer) { return want_attn && layer == Ld - 1; };
   for (int i = 0; i < Ld; ++i) {
     const DecLayer& Y = m.dec[i];
     LCHK(G(c->tf_x, D, Y.nwqkv, 3 * D, D, Y.nbqkv, c->tf_big, 3 * D, M).h3(c).ln(c->tf_x_part, pnx).run(s));
@@ -1066,7 +1070,9 @@ static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, b
     LCHK(G(c->tf_q1, D, Y.ncwq, D, D, Y.ncbq, c->tf_cq, D, M).h3(c).ln(c->tf_q1_part, pnq).run(s));
     LCHK(nd::launch_tf_attention({.q = c->tf_cq, .ldq = D, .kv = c->ctxkv, .ldkv = Ld * 2 * D, .koff = i * 2 * D,
                                   .voff = i * 2 * D + D, .mask = {.signal = c->sig, .span = c->span, .pad_val = pad},
-                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = T}, s));
+                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = T,
+                                  .tap = tap_here(i) ? c->attn_raw : nullptr, .ld_tap = tap_here(i) ? T : 0}, s));
+    if (tap_here(i)) LCHK(nd::launch_attn_rows_softmax(c->attn_raw, c->span, B, L, T, s));
     LCHK(G(c->tf_att, D, Y.cwo, D, D, Y.cbo, c->tf_mid, D, M).h3(c).res(c->tf_q1, D).stats(c->tf_mid_part).run(s, &pnm));
     LCHK(G(c->tf_mid, D, Y.nw1, F, D, Y.nb1, c->tf_big, F, M).h3(c).ln(c->tf_mid_part, pnm).relu().run(s));
     LCHK(G(c->tf_big, F, Y.w2, D, F, Y.b2, c->tf_x, D, M).h3(c).res(c->tf_mid, D).stats(c->tf_x_part).run(s, &pnx));
@@ -1075,20 +1081,27 @@ static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, b
                                want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s);
 }
 
-int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
-                     const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L, float* d_score,
-                     float* d_tok_logp, float* d_logp, void* stream) {
+// nd_score_targets (want_attn false: d_attn unused, the call and its graph as they were before the tap
+// existed) and nd_score_targets_attn (want_attn: d_attn required)
+static int score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                         const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
+                         float* d_score, float* d_tok_logp, float* d_logp, bool want_attn, float* d_attn,
+                         void* stream) {
   // every argument check comes before the first HIP call
+  const std::string who = want_attn ? "nd_score_targets_attn" : "nd_score_targets";
   if (!c) return fail(ND_ERR_ARG, "null ctx");
   if (c->cfg.self_attn_type == ND_SELF_AVERAGE)
-    return fail(ND_ERR_ARG, "nd_score_targets: average-attention decoders are not supported (teacher-forced average "
-                            "attention is a cumulative mean, a kernel this library does not have)");
-  if (L < 1 || L > c->cfg.max_steps) return fail(ND_ERR_ARG, "nd_score_targets: L out of range [1, max_steps]");
+    return fail(ND_ERR_ARG, who + ": average-attention decoders are not supported (teacher-forced average "
+                                  "attention is a cumulative mean, a kernel this library does not have)");
+  if (L < 1 || L > c->cfg.max_steps) return fail(ND_ERR_ARG, who + ": L out of range [1, max_steps]");
   int rc = check_call(c, B, T, L);
   if (rc) return rc;
   if (!d_signal || !d_len || !d_span || !d_gold || !d_gold_len || !d_score) return fail(ND_ERR_ARG, "null buffer");
+  if (want_attn && !d_attn) return fail(ND_ERR_ARG, who + ": null d_attn");
   HIPCHK(hipSetDevice(c->cfg.device));
   if ((rc = alloc_score_ws(c))) return rc;
+  // attn_raw holds at least max_batch * max_steps * max_src_len floats: the dense [B * L, T] tap fits
+  if (want_attn && (rc = ensure_attn(c))) return rc;
   hipStream_t cs = (hipStream_t)stream;
   if ((rc = stage_inputs(c, d_signal, d_len, d_span, B, T, cs))) return rc;
   HIPCHK(hipMemcpyAsync(c->tf_gold, d_gold, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
@@ -1100,15 +1113,32 @@ int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, con
   key.T = T;
   key.S = L;
   key.logp = (tl ? 1 : 0) | (lp ? 2 : 0);
+  key.attn = want_attn ? 1 : 0;
   {
     const CallFlags flags(c, false);
-    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_score(c, B, T, L, tl, lp, s); });
+    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_score(c, B, T, L, tl, lp, want_attn, s); });
   }
   if (rc) return rc;
   HIPCHK(hipMemcpyAsync(d_score, c->tf_score, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
   if (tl) HIPCHK(hipMemcpyAsync(d_tok_logp, c->tf_tok_logp, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
   if (lp) HIPCHK(hipMemcpyAsync(d_logp, c->tf_logp, (size_t)B * L * c->V * 4, hipMemcpyDeviceToDevice, c->es));
+  if (want_attn)
+    HIPCHK(hipMemcpyAsync(d_attn, c->attn_raw, (size_t)B * L * T * 4, hipMemcpyDeviceToDevice, c->es));
   return release_to(c, cs);
+}
+
+int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                     const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L, float* d_score,
+                     float* d_tok_logp, float* d_logp, void* stream) {
+  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, L, d_score, d_tok_logp, d_logp, false,
+                       nullptr, stream);
+}
+
+int nd_score_targets_attn(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                          const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
+                          float* d_score, float* d_tok_logp, float* d_logp, float* d_attn, void* stream) {
+  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, L, d_score, d_tok_logp, d_logp, true,
+                       d_attn, stream);
 }
 
 int nd_encode(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span, int32_t B, int32_t T,

@@ -583,6 +583,12 @@ hipError_t launch_tf_embed(const int* gold, int bos, int V, const float* emb, co
 // fp32 attention of Lq query rows per chunk (row c*Lq + i of q, pitch ldq, head h at column 32 h) over the
 // chunk's Lk key rows (row c*Lk + t of kv, pitch ldkv; K at column koff, V at voff): out [B*Lq, 256].
 // causal: keys j <= i (Lq == Lk; mask unused).  Otherwise the context attention's mask over Lk keys.
+// tap (context attention only; a causal launch with one is refused): head 0's masked scores before the
+// softmax, tap[(c * Lq + i) * ld_tap + t] for i < Lq and every key t < Lk the chunk's workgroups walk (all
+// t < min(span[c], Lk), the 32-key block around that edge included): the fp32 score, ND_MASK_FILL for a
+// masked key, -inf for an absent one.  ld_tap >= Lk floats; columns at or past Lk are never written.  out
+// is bit for bit what the launch without a tap writes; launch_attn_rows_softmax turns a dense tap
+// (ld_tap == Lk) into probabilities.
 struct TfAttnArgs {
   const float* q = nullptr;
   int ldq = 0;
@@ -592,6 +598,8 @@ struct TfAttnArgs {
   float* out = nullptr;
   int B = 0, Lq = 0, Lk = 0;
   bool causal = false;
+  float* tap = nullptr;
+  int ld_tap = 0;
 };
 hipError_t launch_tf_attention(const TfAttnArgs& a, hipStream_t s);
 // per row c*L + i of g.x (row-major): LN_dec -> generator -> log_softmax; tok_logp[c][i] (nullable) =

@@ -465,6 +465,18 @@ int nd_op_tf_attention(const float* q, int32_t ldq, const float* kv, int32_t ldk
                                          .causal = causal != 0}, (hipStream_t)stream));
 }
 
+int nd_op_tf_attention_tap(const float* q, int32_t ldq, const float* kv, int32_t ldkv, int32_t koff, int32_t voff,
+                           const float* signal, const int32_t* span, float pad_val, float* out, int32_t B, int32_t Lq,
+                           int32_t Lk, int32_t causal, float* tap, int32_t ld_tap, void* stream) {
+  if (causal != 0) return fail(ND_ERR_ARG, "tf_attention_tap: the tap is the context attention's (causal must be 0)");
+  if (!tap) return fail(ND_ERR_ARG, "tf_attention_tap: null tap");
+  if (ld_tap < Lk) return fail(ND_ERR_ARG, "tf_attention_tap: ld_tap below Lk");
+  return status("tf_attention_tap",
+                nd::launch_tf_attention({.q = q, .ldq = ldq, .kv = kv, .ldkv = ldkv, .koff = koff, .voff = voff,
+                                         .mask = {signal, span, pad_val}, .out = out, .B = B, .Lq = Lq, .Lk = Lk,
+                                         .causal = false, .tap = tap, .ld_tap = ld_tap}, (hipStream_t)stream));
+}
+
 int nd_op_ctx_pack_q24(const float* kv, int32_t ld, int32_t layers, void* out, const int32_t* span, int32_t B,
                        int32_t T, void* stream) {
   if (!kv || !out || !span) return fail(ND_ERR_ARG, "ctx_pack_q24: bad arguments");

@@ -10,7 +10,8 @@
 //   (S^T = K Q^T on v_mfma_f32_32x32x2_f32) so a lane holds one query's 32 scores, online softmax and O in
 //   registers, one wave per 32 query rows.  K / V^T stream through LDS in tiles of TF_KT keys (35,840 B
 //   static: K 18,432 at stride 36, V^T 16,896 at stride 132, flags 512), the next tile's global loads in
-//   flight under the current tile's arithmetic.
+//   flight under the current tile's arithmetic.  tf_attention_kernel<false, true> is the same kernel that
+//   also stores its head-0 scores (the tap of nd_score_targets_attn).
 // * score_head_kernel: final LayerNorm, generator, log-softmax, the gold token's log-probability per row,
 //   and their sum per chunk in a fixed order (no float atomics).
 #include "common.hpp"
@@ -62,11 +63,18 @@ hipError_t launch_tf_embed(const int* gold, int bos, int V, const float* emb, co
 // Rows at or past Lq are clamped to the last row (computed, never stored); keys at or past the chunk's key
 // count are clamped loads flagged absent.  Every load is unconditional ("Straight-line
 // loads").
-template <bool CAUSAL>
+// TAP (context attention only): the head-0 workgroups also store every score they walk, after the mask and
+// before the online softmax, at tap[(c * Lq + qi) * ld_tap + t] for the rows qi < Lq and the keys t < Lk
+// (forced alignment).  In the transposed layout a lane's register group r = 4g .. 4g+3
+// is four consecutive keys of its query, so a group is one 16-byte store where the rows allow it (ld_tap and
+// the buffer's address multiples of 4 floats) and four scalar stores otherwise; lanes l and l + 32 together
+// write a row's 32 keys of the block, one whole 128-byte segment.  O, m and l do not know the tap exists.
+template <bool CAUSAL, bool TAP = false>
 __global__ void __launch_bounds__(TF_NW * 64)
 tf_attention_kernel(const float* __restrict__ q, int ldq, const float* __restrict__ kv, int ldkv, int koff, int voff,
                     const float* __restrict__ signal, const int* __restrict__ span, float pad_val,
-                    float* __restrict__ out, int Lq, int Lk) {
+                    float* __restrict__ out, int Lq, int Lk, float* __restrict__ tap, int ld_tap) {
+  static_assert(!(CAUSAL && TAP), "the tap is the context attention's");
   __shared__ __attribute__((aligned(16))) float Ks[TF_KT * TF_KLD];
   __shared__ __attribute__((aligned(16))) float Vt[ND_DH * TF_VLD];
   __shared__ int kflag[TF_KT];  // 0 = key, 1 = masked (signal == pad_val), 2 = absent (t >= span)
@@ -112,6 +120,8 @@ tf_attention_kernel(const float* __restrict__ q, int ldq, const float* __restric
   const int q0 = (qg * TF_NW + wave) * 32;
   const int qi = q0 + lr;
   const bool active = q0 < Lq;  // wave-uniform; idle waves still stage and meet the barriers
+  // TAP: every tapped row starts on a 16-byte boundary (workgroup-uniform)
+  const bool tap_v4 = TAP && (ld_tap & 3) == 0 && (reinterpret_cast<uintptr_t>(tap) & 15) == 0;
   // query fragment: step s = 4j+i uses d = 8j + 4*lh + i; pre-scaled like
   // ``query / math.sqrt(dim_per_head)`` (multi_headed_attn.py:167)
   f32x4 qf[4];
@@ -166,6 +176,23 @@ tf_attention_kernel(const float* __restrict__ q, int ldq, const float* __restric
             sacc[r] = sv;
             mx = fmaxf(mx, sv);
           }
+          if constexpr (TAP) {
+            if (h == 0 && qi < Lq) {
+              const int t0 = key0 + 4 * lh;  // group g holds keys t0 + 8g .. + 3
+              float* trow = tap + ((size_t)c * Lq + qi) * (size_t)ld_tap + t0;
+#pragma unroll
+              for (int g = 0; g < 4; ++g) {
+                if (tap_v4 && t0 + 8 * g + 4 <= Lk) {
+                  const f32x4 v = {sacc[4 * g + 0], sacc[4 * g + 1], sacc[4 * g + 2], sacc[4 * g + 3]};
+                  st4(trow + 8 * g, v);
+                } else {
+#pragma unroll
+                  for (int i = 0; i < 4; ++i)
+                    if (t0 + 8 * g + i < Lk) trow[8 * g + i] = sacc[4 * g + i];
+                }
+              }
+            }
+          }
         }
         mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
         const float mn = fmaxf(m, mx);
@@ -214,13 +241,16 @@ hipError_t launch_tf_attention(const TfAttnArgs& a, hipStream_t s) {
       a.koff + ND_D > a.ldkv || a.voff + ND_D > a.ldkv)
     return hipErrorInvalidValue;
   if (a.causal ? a.Lq != a.Lk : (!m.signal || !m.span)) return hipErrorInvalidValue;
+  if (a.tap && (a.causal || a.ld_tap < a.Lk)) return hipErrorInvalidValue;  // the tap: context attention only
   const dim3 grid(ND_H, (a.Lq + TF_NW * 32 - 1) / (TF_NW * 32), a.B), block(TF_NW * 64);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, grid, block, 0, s, a.q, a.ldq, a.kv, a.ldkv, a.koff, a.voff, m.signal, m.span, m.pad_val,
-                       a.out, a.Lq, a.Lk);
+                       a.out, a.Lq, a.Lk, a.tap, a.ld_tap);
   };
   if (a.causal)
     go(tf_attention_kernel<true>);
+  else if (a.tap)
+    go(tf_attention_kernel<false, true>);
   else
     go(tf_attention_kernel<false>);
   return hipGetLastError();

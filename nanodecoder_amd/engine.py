@@ -282,12 +282,16 @@ class Engine:
         return out
 
     def score_targets(self, signal, lengths, spans=None, gold=None, gold_len=None, return_tok_logp: bool = False,
-                      return_logp: bool = False):
+                      return_logp: bool = False, return_attn: bool = False):
         """Teacher-forced scoring (nd_score_targets; Translator._score_target, translator.py:928-941): one
         decoder pass over every position of every target.  gold [B, L] int32: each chunk's tokens followed
         by EOS, then pad_idx; gold_len [B] in [1, L]: tokens counted, EOS included.  Returns dict(scores [B]
         f32 = sum over i < gold_len of logp[i][gold[i]], tok_logp [B, L] or None: the summands (0 at
-        i >= gold_len), logp [B, L, V] or None (rows i >= gold_len unspecified), overflow)."""
+        i >= gold_len), logp [B, L, V] or None (rows i >= gold_len unspecified), attn, overflow).  With
+        ``return_attn`` (nd_score_targets_attn; forced alignment) attn [B, L, T] holds, per target position,
+        the head-0 probabilities of the last decoder layer's context attention, what a translate call's
+        return_attn gives per step (zero at t >= span; rows i >= gold_len unspecified): token_positions turns
+        it into one signal sample per position.  Otherwise attn is None and the call is nd_score_targets."""
         if self.cfg.self_attn_type == "average":
             raise NotImplementedError("score_targets: average-attention decoders are not supported")
         signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
@@ -301,10 +305,17 @@ class Engine:
         sc = torch.empty(B, dtype=torch.float32, device=self.device)
         tl = torch.empty(B, L, dtype=torch.float32, device=self.device) if return_tok_logp else None
         lp = torch.empty(B, L, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logp else None
-        _lib.check(self._L.nd_score_targets(self._h, _ptr(signal), _ptr(lengths), _ptr(spans), _ptr(gold),
-                                            _ptr(gold_len), B, T, L, _ptr(sc), _ptr(tl), _ptr(lp), self._stream()),
-                   "nd_score_targets")
-        return dict(scores=sc, tok_logp=tl, logp=lp, overflow=self._take_overflow())
+        at = None
+        if return_attn:
+            at = torch.empty(B, L, T, dtype=torch.float32, device=self.device)
+            _lib.check(self._L.nd_score_targets_attn(self._h, _ptr(signal), _ptr(lengths), _ptr(spans), _ptr(gold),
+                                                     _ptr(gold_len), B, T, L, _ptr(sc), _ptr(tl), _ptr(lp), _ptr(at),
+                                                     self._stream()), "nd_score_targets_attn")
+        else:
+            _lib.check(self._L.nd_score_targets(self._h, _ptr(signal), _ptr(lengths), _ptr(spans), _ptr(gold),
+                                                _ptr(gold_len), B, T, L, _ptr(sc), _ptr(tl), _ptr(lp),
+                                                self._stream()), "nd_score_targets")
+        return dict(scores=sc, tok_logp=tl, logp=lp, attn=at, overflow=self._take_overflow())
 
     def token_weights(self, tokens, logp=None, tok_logp=None):
         """The uint16 weights of a call's tokens (nd_token_weights, on the current stream): w =
@@ -892,6 +903,22 @@ def op_tf_attention(q, kv, B, Lq, Lk, koff, voff, causal, signal=None, span=None
                                              _ptr(span), float(pad_val), _ptr(out), B, Lq, Lk, int(causal), s),
                "nd_op_tf_attention")
     return out
+
+
+def op_tf_attention_tap(q, kv, B, Lq, Lk, koff, voff, signal, span, pad_val=0.0, tap=None, ld_tap=None):
+    """The tapped context attention (nd_op_tf_attention_tap): op_tf_attention with causal False that also
+    stores head 0's masked scores into ``tap`` (a float32 device buffer of at least B * Lq * ld_tap elements,
+    row (c, i) at (c * Lq + i) * ld_tap; default: a new [B * Lq, Lk] buffer of NaN).  Returns (out, tap)."""
+    out = torch.empty(B * Lq, 256, dtype=torch.float32, device=q.device)
+    ld_tap = Lk if ld_tap is None else int(ld_tap)
+    if tap is None:
+        tap = torch.full((B * Lq, ld_tap), float("nan"), dtype=torch.float32, device=q.device)
+    span = span.to(torch.int32)
+    s = ctypes.c_void_p(torch.cuda.current_stream(q.device).cuda_stream)
+    _lib.check(_lib.lib().nd_op_tf_attention_tap(_ptr(q), q.shape[1], _ptr(kv), kv.shape[1], koff, voff, _ptr(signal),
+                                                 _ptr(span), float(pad_val), _ptr(out), B, Lq, Lk, 0, _ptr(tap),
+                                                 ld_tap, s), "nd_op_tf_attention_tap")
+    return out, tap
 
 
 CTXQ_ROW = 1600  # bytes per (key row, layer) of the 24-bit context K/V image (kernels.hpp)

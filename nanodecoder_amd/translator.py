@@ -529,12 +529,15 @@ class Translator(object):
                              f"{self.engine.max_steps - 1}")
         return ids
 
-    def score(self, chunks, targets, batch_size):
+    def score(self, chunks, targets, batch_size, moves: bool = False):
         """Teacher-forced scores of given target sequences (Translator._score_target,
         translate/translator.py:928-941): per chunk (score, tok_logp list), score = the sum of the target's
         token log-probabilities, EOS (appended here) included, tok_logp = the summands.  ``targets``: one
         token string or id sequence per chunk (see _gold_ids).  Each chunk keeps the span of its reference
-        batch (consecutive ``batch_size`` chunks), exactly as stream_reads assigns it."""
+        batch (consecutive ``batch_size`` chunks), exactly as stream_reads assigns it.  With ``moves`` (forced
+        alignment) each chunk's result is (score, tok_logp, positions): the signal sample of every target
+        token, EOS included, chunk-relative and non-decreasing: nd_token_positions of the scoring pass's own
+        context attention, the rule -moves applies to decoded tokens (DESIGN.md sections 1.6, 1.7)."""
         if batch_size is None:
             raise ValueError("batch_size must be set")
         chunks = [parse_chunk(c) for c in chunks]
@@ -549,11 +552,13 @@ class Translator(object):
             spans += [max(len(c) for c in part)] * len(part)
         out, cap = [], self.engine.max_batch
         for b0 in range(0, len(chunks), cap):
-            out += self._score_batch(chunks[b0: b0 + cap], spans[b0: b0 + cap], ids[b0: b0 + cap])
+            out += self._score_batch(chunks[b0: b0 + cap], spans[b0: b0 + cap], ids[b0: b0 + cap], moves=moves)
         return out
 
-    def _score_batch(self, chunks, spans, ids, exact: bool = False):
-        """One engine batch of score(): stage, call, collect on the host."""
+    def _score_batch(self, chunks, spans, ids, exact: bool = False, moves: bool = False):
+        """One engine batch of score(): stage, call, collect on the host.  With ``moves`` the call returns its
+        attention too, token_positions reduces it on the call's stream (its EnginePool lane), and only the
+        [B, L] positions come to the host."""
         n = len(chunks)
         lens = np.array([len(c) for c in chunks], np.int32)
         if (lens < 1).any():
@@ -579,8 +584,9 @@ class Translator(object):
             gold[i, : len(t)] = t
             gold[i, len(t)] = self.cfg.eos_idx
             gold_len[i] = len(t) + 1
+        want = dict(return_attn=True) if moves else {}
         r = self.engine.score_targets(sig, ln, sp, gold=torch.from_numpy(gold), gold_len=torch.from_numpy(gold_len),
-                                      return_tok_logp=True)
+                                      return_tok_logp=True, **want)
         if "event" in r:
             r["event"].synchronize()
         ov = r.get("overflow")
@@ -588,10 +594,17 @@ class Translator(object):
             # split-fp16 range guard: the batch again with every product in exact fp32 (see _rerun_exact)
             self.engine.set_exact_fp32(True)
             try:
-                return self._score_batch(chunks, spans, ids, exact=True)
+                return self._score_batch(chunks, spans, ids, exact=True, moves=moves)
             finally:
                 self.engine.set_exact_fp32(False)
+        if moves:
+            self._positions(r, sp)
+            if "lane" in r:
+                self.engine.engines[r["lane"]].stream.synchronize()
         sc, tl = r["scores"].cpu().numpy(), r["tok_logp"].cpu().numpy()
+        if moves:
+            ps = r["positions"].cpu().numpy()
+            return [(float(sc[i]), tl[i, : gold_len[i]].tolist(), ps[i, : gold_len[i]].tolist()) for i in range(n)]
         return [(float(sc[i]), tl[i, : gold_len[i]].tolist()) for i in range(n)]
 
     def translate(self, src, tgt=None, src_dir=None, batch_size=None, attn_debug=False):
