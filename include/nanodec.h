@@ -229,6 +229,43 @@ int nd_score_targets_attn(nd_ctx* ctx, const float* d_signal, const int32_t* d_l
                           const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
                           float* d_score, float* d_tok_logp, float* d_logp, float* d_attn, void* stream);
 
+/* Several candidate targets per chunk on one encoder pass (the reference has no such
+ * call): "which of these K sequences does this signal support?"  The encoder and the context K/V
+ * projections run once over the B chunks; the decoder runs over the B * K candidate rows, the K candidates
+ * of a chunk being K * L consecutive query rows of its context attention.  nd_score_targets is the K = 1
+ * case of the same function.
+ *   d_cand     [B, K, L] i32: a gold row per (chunk, slot) exactly as nd_score_targets takes it: tokens,
+ *              EOS, then pad_idx
+ *   d_cand_len [B, K] i32 in [0, L], EOS included; 0 marks an empty slot (calls are rectangular: a chunk
+ *              with fewer than K candidates leaves slots empty).  Values outside [0, L] are clamped on
+ *              the device, token ids as in nd_score_targets
+ *   d_score    [B, K] f32, required: the sum of the slot's token log-probabilities, nd_score_targets'
+ *              quantity; -inf for an empty slot.  log P(y | x) is normalised over all sequences (EOS
+ *              included), so the sums compare across candidates of different lengths
+ *   d_post     nullable [B, K] f32: score - logsumexp over the chunk's non-empty slots; -inf for an empty slot
+ *   d_best     nullable [B] i32: the non-empty slot with the largest score, the lowest slot on a tie; -1 when
+ *              every slot is empty
+ *   d_tok_logp nullable [B, K, L] f32, d_logp nullable [B, K, L, V] f32: as in nd_score_targets (tok_logp
+ *              0 at i >= cand_len, logp rows there unspecified)
+ * 1 <= K, B * K <= max_batch, L <= max_steps, T <= max_src_len (ND_ERR_ARG otherwise); an ND_SELF_AVERAGE
+ * decoder is refused as by nd_score_targets; every check, null buffers included, comes before the first HIP
+ * call.  Its own captured graph per (B, T, K, L).  Honours nd_set_graphs, nd_set_exact_fp32 and
+ * nd_take_overflow like nd_score_targets, whose workspaces it uses.
+ *
+ * The posterior rule, one chunk per thread, slots in the order k = 0 .. K-1 (so a chunk's bits depend on its
+ * own K scores only): m = the maximum over the non-empty slots, updated by s > m; sum = the sum of
+ * expf(s_k - m) in slot order; post_k = (s_k - m) - logf(sum).  A NaN score is never best and makes the
+ * chunk's post values NaN.  nd_cand_posterior applies the rule to given scores (no context needed; one
+ * launch on `stream`): d_score [B, K] and d_cand_len [B, K] in, d_score_out [B, K] (required; may be d_score:
+ * the scores with -inf in the empty slots), d_post (nullable) and d_best (nullable) out.  K < 1, B < 0 or a
+ * null required buffer return ND_ERR_ARG before any HIP call; B == 0 returns ND_OK at once. */
+int nd_score_candidates(nd_ctx* ctx, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                        const int32_t* d_cand, const int32_t* d_cand_len, int32_t B, int32_t T, int32_t K, int32_t L,
+                        float* d_score, float* d_post, int32_t* d_best, float* d_tok_logp, float* d_logp,
+                        void* stream);
+int nd_cand_posterior(const float* d_score, const int32_t* d_cand_len, int32_t B, int32_t K, float* d_score_out,
+                      float* d_post, int32_t* d_best, void* stream);
+
 /* Signal front end (utils/labelop.py:194-243, extract_fast5_raw): R raw
  * reads concatenated in d_raw (float64, read r at d_offsets[r] ..
  * d_offsets[r+1]) normalised per read into d_out (float32, same offsets).
@@ -494,7 +531,9 @@ int nd_set_kernel_stamps(nd_ctx* c, int enable);
 int nd_kernel_stamps(nd_ctx* c, float* avg_us, int32_t* launches);
 
 /* Kernel statistics of the last translate call (ms of device time per
- * phase, measured with HIP events on the engine stream when enabled). */
+ * phase, measured with HIP events on the engine stream when enabled).  The
+ * scoring calls report too: a timed one runs its launches as two pieces, the
+ * encoder with the context K/V projections, then the decoder rows. */
 int nd_set_timing(nd_ctx* ctx, int enable);
 int nd_last_timing(nd_ctx* ctx, float* encode_ms, float* decode_ms);
 

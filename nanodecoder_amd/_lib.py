@@ -71,7 +71,9 @@ SIGNATURES = {
     "nd_op_tf_attention": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _I, _I, _P]),
     "nd_score_targets_attn": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P]),
     "nd_op_tf_attention_tap": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _F, _P, _I, _I, _I, _I, _P, _I, _P]),
-    "nd_normalize_reads": (_I, [_P, _P, _I, _I, _P, _P]),
+    "nd_score_candidates": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
+    "nd_cand_posterior": (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
+    "nd_normalize_reads":(_I, [_P, _P, _I, _I, _P, _P]),
     "nd_window_reads": (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P]),
     "nd_assemble_reads_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
     "nd_assemble_reads": (_I, [_P, _P, _P, _I, _I, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P]),

@@ -1039,106 +1039,160 @@ static int alloc_score_ws(nd_ctx* c) {
   WST(c->tf_gold_len, B);
   WST(c->tf_tok_logp, B * S);
   WST(c->tf_logp, B * S * (size_t)c->V);
+  WST(c->tf_post, B);
+  WST(c->tf_best, B);
   WST(c->tf_score, B);
 #undef WST
   return ND_OK;
 }
 
-// Encoder, fp32 context K/V of every layer, then the decoder over the M = B * L target rows at once
+// Encoder, fp32 context K/V of every layer, then the decoder over the M = N * L target rows at once
 // (decoder/transformer.py:53-95 with step = None): the row-major GEMMs of the encoder side (split-fp16
 // images of the decoder's fp32 weights, or fp32 MFMA in exact mode: the same G calls) around the two
 // attentions of score.hip; the FFN is the two GEMMs (its hidden in tf_big), in both product modes.
-// want_attn (nd_score_targets_attn): the last layer's context attention is the tapped form, its head-0
+// K targets per chunk (nd_score_candidates; nd_score_targets is K = 1): the encoder
+// and the context K/V run over the B chunks, everything that works on decoder rows over the N = B * K
+// sequences of L rows, and the context attention, the one place a decoder row meets its chunk, takes the K
+// candidates of chunk c as the K * L consecutive query rows they are.  post: the candidates' posterior
+// and best behind the head (tf_gold_len holds the [B, K] candidate lengths).
+// want_attn (nd_score_targets_attn, K = 1): the last layer's context attention is the tapped form, its head-0
 // scores dense [B * L, T] in attn_raw (ensure_attn), turned into probabilities right behind it.
-static hipError_t enqueue_score(nd_ctx* c, int B, int T, int L, bool want_tok, bool want_logp, bool want_attn,
-                                hipStream_t s) {
+// part: 0 the whole call; a timed call (nd_set_timing) enqueues 1, the encoder side, and 2, the decoder
+// side, with an event between them: the same launches in the same order.
+static hipError_t enqueue_score(nd_ctx* c, int B, int T, int K, int L, bool want_tok, bool want_logp, bool want_attn,
+                                bool post, int part, hipStream_t s) {
   const Model& m = c->m;
-  const int M = B * L, D = c->D, F = c->F, Ld = (int)m.dec.size();
+  const int N = B * K, M = N * L, D = c->D, F = c->F, Ld = (int)m.dec.size();
   const float pad = (float)c->cfg.pad_idx;
-  LCHK(enqueue_encode(c, B, T, s));
-  LCHK(enqueue_ctxkv(c, B, T, s, false));
+  if (part != 2) {
+    LCHK(enqueue_encode(c, B, T, s));
+    LCHK(enqueue_ctxkv(c, B, T, s, false));
+  }
+  if (part == 1) return hipSuccess;
   LCHK(nd::launch_tf_embed(c->tf_gold, c->cfg.bos_idx, c->V, m.emb, c->cfg.position_encoding ? m.pe : nullptr, c->tf_x,
-                           c->tf_x_part, B, L, s));
+                           c->tf_x_part, N, L, s));
   int pnx = 1, pnq = 0, pnm = 0;
   const auto tap_here = [&](int layer) { return want_attn && layer == Ld - 1; };
   for (int i = 0; i < Ld; ++i) {
     const DecLayer& Y = m.dec[i];
     LCHK(G(c->tf_x, D, Y.nwqkv, 3 * D, D, Y.nbqkv, c->tf_big, 3 * D, M).h3(c).ln(c->tf_x_part, pnx).run(s));
     LCHK(nd::launch_tf_attention({.q = c->tf_big, .ldq = 3 * D, .kv = c->tf_big, .ldkv = 3 * D, .koff = D, .voff = 2 * D,
-                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = L, .causal = true}, s));
+                                  .out = c->tf_att, .B = N, .Lq = L, .Lk = L, .causal = true}, s));
     LCHK(G(c->tf_att, D, Y.wo, D, D, Y.bo, c->tf_q1, D, M).h3(c).res(c->tf_x, D).stats(c->tf_q1_part).run(s, &pnq));
     LCHK(G(c->tf_q1, D, Y.ncwq, D, D, Y.ncbq, c->tf_cq, D, M).h3(c).ln(c->tf_q1_part, pnq).run(s));
     LCHK(nd::launch_tf_attention({.q = c->tf_cq, .ldq = D, .kv = c->ctxkv, .ldkv = Ld * 2 * D, .koff = i * 2 * D,
                                   .voff = i * 2 * D + D, .mask = {.signal = c->sig, .span = c->span, .pad_val = pad},
-                                  .out = c->tf_att, .B = B, .Lq = L, .Lk = T,
+                                  .out = c->tf_att, .B = B, .Lq = K * L, .Lk = T,
                                   .tap = tap_here(i) ? c->attn_raw : nullptr, .ld_tap = tap_here(i) ? T : 0}, s));
-    if (tap_here(i)) LCHK(nd::launch_attn_rows_softmax(c->attn_raw, c->span, B, L, T, s));
+    if (tap_here(i)) LCHK(nd::launch_attn_rows_softmax(c->attn_raw, c->span, B, K * L, T, s));
     LCHK(G(c->tf_att, D, Y.cwo, D, D, Y.cbo, c->tf_mid, D, M).h3(c).res(c->tf_q1, D).stats(c->tf_mid_part).run(s, &pnm));
     LCHK(G(c->tf_mid, D, Y.nw1, F, D, Y.nb1, c->tf_big, F, M).h3(c).ln(c->tf_mid_part, pnm).relu().run(s));
     LCHK(G(c->tf_big, F, Y.w2, D, F, Y.b2, c->tf_x, D, M).h3(c).res(c->tf_mid, D).stats(c->tf_x_part).run(s, &pnx));
   }
-  return nd::launch_score_head(generator(c, c->tf_x), c->tf_gold, c->tf_gold_len, B, L, c->tf_score,
-                               want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s);
+  LCHK(nd::launch_score_head(generator(c, c->tf_x), c->tf_gold, c->tf_gold_len, N, L, c->tf_score,
+                             want_tok ? c->tf_tok_logp : nullptr, want_logp ? c->tf_logp : nullptr, s));
+  if (!post) return hipSuccess;
+  return nd::launch_cand_posterior(c->tf_score, c->tf_gold_len, B, K, c->tf_score, c->tf_post, c->tf_best, s);
 }
 
-// nd_score_targets (want_attn false: d_attn unused, the call and its graph as they were before the tap
-// existed) and nd_score_targets_attn (want_attn: d_attn required)
+// What a scoring call writes: score is required; attn belongs to nd_score_targets_attn, post and best
+// (both nullable) to nd_score_candidates.
+struct ScoreOut {
+  float *score = nullptr, *tok_logp = nullptr, *logp = nullptr, *attn = nullptr, *post = nullptr;
+  int32_t* best = nullptr;
+};
+
+// nd_score_targets (cand and want_attn false, K = 1: o.attn unused, the call and its graph as they were before
+// the tap and the candidates existed), nd_score_targets_attn (want_attn: o.attn required) and
+// nd_score_candidates (cand: d_gold [B, K, L], d_gold_len [B, K] with 0 for an empty slot)
 static int score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
-                         const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
-                         float* d_score, float* d_tok_logp, float* d_logp, bool want_attn, float* d_attn,
-                         void* stream) {
+                         const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t K, int32_t L,
+                         const ScoreOut& o, bool want_attn, bool cand, void* stream) {
   // every argument check comes before the first HIP call
-  const std::string who = want_attn ? "nd_score_targets_attn" : "nd_score_targets";
+  const std::string who = cand ? "nd_score_candidates" : want_attn ? "nd_score_targets_attn" : "nd_score_targets";
   if (!c) return fail(ND_ERR_ARG, "null ctx");
   if (c->cfg.self_attn_type == ND_SELF_AVERAGE)
     return fail(ND_ERR_ARG, who + ": average-attention decoders are not supported (teacher-forced average "
                                   "attention is a cumulative mean, a kernel this library does not have)");
+  if (K < 1) return fail(ND_ERR_ARG, who + ": K out of range [1, max_batch / B]");
   if (L < 1 || L > c->cfg.max_steps) return fail(ND_ERR_ARG, who + ": L out of range [1, max_steps]");
   int rc = check_call(c, B, T, L);
   if (rc) return rc;
-  if (!d_signal || !d_len || !d_span || !d_gold || !d_gold_len || !d_score) return fail(ND_ERR_ARG, "null buffer");
-  if (want_attn && !d_attn) return fail(ND_ERR_ARG, who + ": null d_attn");
+  if ((int64_t)B * K > c->cfg.max_batch) return fail(ND_ERR_ARG, who + ": B * K out of range [1, max_batch]");
+  if (!d_signal || !d_len || !d_span || !d_gold || !d_gold_len || !o.score) return fail(ND_ERR_ARG, "null buffer");
+  if (want_attn && !o.attn) return fail(ND_ERR_ARG, who + ": null d_attn");
   HIPCHK(hipSetDevice(c->cfg.device));
   if ((rc = alloc_score_ws(c))) return rc;
   // attn_raw holds at least max_batch * max_steps * max_src_len floats: the dense [B * L, T] tap fits
   if (want_attn && (rc = ensure_attn(c))) return rc;
   hipStream_t cs = (hipStream_t)stream;
+  const int N = B * K;
   if ((rc = stage_inputs(c, d_signal, d_len, d_span, B, T, cs))) return rc;
-  HIPCHK(hipMemcpyAsync(c->tf_gold, d_gold, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
-  HIPCHK(hipMemcpyAsync(c->tf_gold_len, d_gold_len, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
-  const bool tl = d_tok_logp != nullptr, lp = d_logp != nullptr;
+  HIPCHK(hipMemcpyAsync(c->tf_gold, d_gold, (size_t)N * L * 4, hipMemcpyDeviceToDevice, c->es));
+  HIPCHK(hipMemcpyAsync(c->tf_gold_len, d_gold_len, (size_t)N * 4, hipMemcpyDeviceToDevice, c->es));
+  const bool tl = o.tok_logp != nullptr, lp = o.logp != nullptr;
   GraphKey key;
   key.mode = 3;
   key.B = B;
   key.T = T;
   key.S = L;
+  key.K = cand ? K : 0;
   key.logp = (tl ? 1 : 0) | (lp ? 2 : 0);
   key.attn = want_attn ? 1 : 0;
   {
     const CallFlags flags(c, false);
-    rc = run_graph(c, key, [&](hipStream_t s) { return enqueue_score(c, B, T, L, tl, lp, want_attn, s); });
+    const auto run = [&](int part) {
+      key.seg = part == 1 ? -1 : part;  // the whole call keeps the key it always had (seg 0)
+      return run_graph(c, key,
+                       [&](hipStream_t s) { return enqueue_score(c, B, T, K, L, tl, lp, want_attn, cand, part, s); });
+    };
+    if (!c->timing) {
+      rc = run(0);
+    } else {  // the same launches as two pieces, the encoder side and the decoder side, an event between
+      HIPCHK(hipEventRecord(c->ev_a, c->es));
+      if ((rc = run(1))) return rc;
+      HIPCHK(hipEventRecord(c->ev_b, c->es));
+      rc = run(2);
+      if (!rc) HIPCHK(hipEventRecord(c->ev_c, c->es));
+    }
   }
   if (rc) return rc;
-  HIPCHK(hipMemcpyAsync(d_score, c->tf_score, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
-  if (tl) HIPCHK(hipMemcpyAsync(d_tok_logp, c->tf_tok_logp, (size_t)B * L * 4, hipMemcpyDeviceToDevice, c->es));
-  if (lp) HIPCHK(hipMemcpyAsync(d_logp, c->tf_logp, (size_t)B * L * c->V * 4, hipMemcpyDeviceToDevice, c->es));
+  HIPCHK(hipMemcpyAsync(o.score, c->tf_score, (size_t)N * 4, hipMemcpyDeviceToDevice, c->es));
+  if (tl) HIPCHK(hipMemcpyAsync(o.tok_logp, c->tf_tok_logp, (size_t)N * L * 4, hipMemcpyDeviceToDevice, c->es));
+  if (lp) HIPCHK(hipMemcpyAsync(o.logp, c->tf_logp, (size_t)N * L * c->V * 4, hipMemcpyDeviceToDevice, c->es));
   if (want_attn)
-    HIPCHK(hipMemcpyAsync(d_attn, c->attn_raw, (size_t)B * L * T * 4, hipMemcpyDeviceToDevice, c->es));
+    HIPCHK(hipMemcpyAsync(o.attn, c->attn_raw, (size_t)N * L * T * 4, hipMemcpyDeviceToDevice, c->es));
+  if (cand && o.post) HIPCHK(hipMemcpyAsync(o.post, c->tf_post, (size_t)N * 4, hipMemcpyDeviceToDevice, c->es));
+  if (cand && o.best) HIPCHK(hipMemcpyAsync(o.best, c->tf_best, (size_t)B * 4, hipMemcpyDeviceToDevice, c->es));
+  if (c->timing) {
+    HIPCHK(hipEventSynchronize(c->ev_c));
+    HIPCHK(hipEventElapsedTime(&c->t_enc, c->ev_a, c->ev_b));
+    HIPCHK(hipEventElapsedTime(&c->t_dec, c->ev_b, c->ev_c));
+  }
   return release_to(c, cs);
 }
 
 int nd_score_targets(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
                      const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L, float* d_score,
                      float* d_tok_logp, float* d_logp, void* stream) {
-  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, L, d_score, d_tok_logp, d_logp, false,
-                       nullptr, stream);
+  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, 1, L,
+                       {.score = d_score, .tok_logp = d_tok_logp, .logp = d_logp}, false, false, stream);
 }
 
 int nd_score_targets_attn(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
                           const int32_t* d_gold, const int32_t* d_gold_len, int32_t B, int32_t T, int32_t L,
                           float* d_score, float* d_tok_logp, float* d_logp, float* d_attn, void* stream) {
-  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, L, d_score, d_tok_logp, d_logp, true,
-                       d_attn, stream);
+  return score_targets(c, d_signal, d_len, d_span, d_gold, d_gold_len, B, T, 1, L,
+                       {.score = d_score, .tok_logp = d_tok_logp, .logp = d_logp, .attn = d_attn}, true, false, stream);
+}
+
+int nd_score_candidates(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span,
+                        const int32_t* d_cand, const int32_t* d_cand_len, int32_t B, int32_t T, int32_t K, int32_t L,
+                        float* d_score, float* d_post, int32_t* d_best, float* d_tok_logp, float* d_logp,
+                        void* stream) {
+  return score_targets(c, d_signal, d_len, d_span, d_cand, d_cand_len, B, T, K, L,
+                       {.score = d_score, .tok_logp = d_tok_logp, .logp = d_logp, .post = d_post, .best = d_best},
+                       false, true, stream);
 }
 
 int nd_encode(nd_ctx* c, const float* d_signal, const int32_t* d_len, const int32_t* d_span, int32_t B, int32_t T,

@@ -92,6 +92,7 @@ struct NanoLayer {
 struct GraphKey {
   int mode = 0;  // 0 greedy / sampling, 1 --fast beam, 2 classic beam, 3 teacher-forced scoring (S = L)
   int B = 0, T = 0, S = 0, min_len = 0, beam = 1, n_best = 1;
+  int K = 0;  // scoring: candidate slots per chunk (nd_score_candidates); 0 = nd_score_targets, no posterior
   int seg = 0;   // beam: first step of the segment, -1 = the prologue (encoder, memory, init)
   int logp = 0;  // greedy: per-step log-probabilities kept; scoring: bit 0 tok_logp, bit 1 logp kept
   float alpha = 0.f;
@@ -109,7 +110,7 @@ struct GraphKey {
   int splitk = 0;     // long-K step GEMMs split over workgroups (set by run_graph from the ctx)
   int tail = 0;   // --fast beam tail segments (nd_ctx.beam_tail)
   auto tie() const {
-    return std::tie(mode, B, T, S, min_len, beam, n_best, seg, logp, alpha, stamp, attn, lenpen, cov, stepwise, ngram,
+    return std::tie(mode, B, T, S, K, min_len, beam, n_best, seg, logp, alpha, stamp, attn, lenpen, cov, stepwise, ngram,
                     excl, beta, topk, temp, exact, tail, bank_nt, bank_grid, splitk);
   }
   bool operator<(const GraphKey& o) const { return tie() < o.tie(); }
@@ -245,11 +246,12 @@ struct nd_ctx {
   // teacher-forced scoring (nd_score_targets), made on first use: the [max_batch * max_steps, .] row-major
   // decoder rows x / q1 / mid / cq / att with their row statistics, q | k | v and the FFN hidden (tf_big: the
   // encoder's `big` when max_steps <= max_src_len, the encoder being done with it), the staged gold rows
-  // and the results
+  // and the results (tf_post / tf_best: nd_score_candidates' per-slot posterior and per-chunk best)
   float *tf_x = nullptr, *tf_q1 = nullptr, *tf_mid = nullptr, *tf_cq = nullptr, *tf_att = nullptr, *tf_big = nullptr;
   float *tf_x_part = nullptr, *tf_q1_part = nullptr, *tf_mid_part = nullptr;
   int *tf_gold = nullptr, *tf_gold_len = nullptr;
-  float *tf_score = nullptr, *tf_tok_logp = nullptr, *tf_logp = nullptr;
+  float *tf_score = nullptr, *tf_tok_logp = nullptr, *tf_logp = nullptr, *tf_post = nullptr;
+  int* tf_best = nullptr;
 
   hipStream_t es = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr, ev_a = nullptr, ev_b = nullptr, ev_c = nullptr;

@@ -607,5 +607,11 @@ hipError_t launch_tf_attention(const TfAttnArgs& a, hipStream_t s);
 // [B, L, V] every row's log-probabilities.  L <= 512, V <= 32.
 hipError_t launch_score_head(const Generator& g, const int* gold, const int* gold_len, int B, int L, float* score,
                              float* tok_logp, float* logp, hipStream_t s);
+// K candidate slots per chunk, slot (c, k) empty when cand_len[c][k] <= 0: score_out[c][k] = score[c][k], -inf
+// for an empty slot (score_out may be score); post[c][k] (nullable) = score - logsumexp over the chunk's
+// non-empty slots, -inf for an empty one; best[c] (nullable) = the non-empty slot of the largest score, the
+// lowest on a tie, -1 when all are empty.  One thread per chunk, slots in order: see cand_posterior_kernel.
+hipError_t launch_cand_posterior(const float* score, const int* cand_len, int B, int K, float* score_out, float* post,
+                                 int* best, hipStream_t s);
 
 }  // namespace nd

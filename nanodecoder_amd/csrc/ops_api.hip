@@ -386,6 +386,16 @@ int nd_token_positions(const float* d_attn, int64_t ld_chunk, const int32_t* d_s
                                                               (hipStream_t)stream), ND_ERR_HIP);
 }
 
+int nd_cand_posterior(const float* d_score, const int32_t* d_cand_len, int32_t B, int32_t K, float* d_score_out,
+                      float* d_post, int32_t* d_best, void* stream) {
+  if (B < 0 || K < 1 || (int64_t)B * K >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, "cand_posterior: B must be >= 0, K >= 1 and B * K < 2^31");
+  if (B == 0) return ND_OK;
+  if (!d_score || !d_cand_len || !d_score_out) return fail(ND_ERR_ARG, "cand_posterior: null buffer");
+  return status("cand_posterior", nd::launch_cand_posterior(d_score, d_cand_len, B, K, d_score_out, d_post, d_best,
+                                                            (hipStream_t)stream), ND_ERR_HIP);
+}
+
 int64_t nd_assemble_reads_p_work_bytes(int32_t C, int64_t total_bases) {
   return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, false, false, true) : -1;
 }

@@ -14,6 +14,8 @@
 //   also stores its head-0 scores (the tap of nd_score_targets_attn).
 // * score_head_kernel: final LayerNorm, generator, log-softmax, the gold token's log-probability per row,
 //   and their sum per chunk in a fixed order (no float atomics).
+// * cand_posterior_kernel: K candidate targets per chunk (nd_score_candidates): the log-posterior over a
+//   chunk's candidates and the best of them from their K scores.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -351,6 +353,51 @@ hipError_t launch_score_head(const Generator& g, const int* gold, const int* gol
   if (B < 1 || L < 1 || L > TF_MAXL || g.V < 1 || g.V > ND_MAXV || !score) return hipErrorInvalidValue;
   hipLaunchKernelGGL(score_head_kernel, dim3(B), dim3(TF_HW * 64), 0, s, g.x, g.ln_g, g.ln_b, g.gw, g.gb, g.V, gold,
                      gold_len, L, score, tok_logp, logp);
+  return hipGetLastError();
+}
+
+// Candidate posterior (nd_score_candidates, nd_cand_posterior): one chunk per thread,
+// its K slots walked in slot order three times (maximum and best, sum, outputs), so a chunk's bits depend on
+// nothing but its own K scores.  A slot is empty when its cand_len <= 0: it reads -inf in score_out and post
+// and takes no part.  m = the maximum over the other slots (updated by s > m: the lowest slot wins a tie, a
+// NaN is never best), sum = the sum of expf(s_k - m) in slot order, post_k = (s_k - m) - logf(sum): a NaN
+// score makes every post of its chunk NaN.  Each slot's score is read before score_out[slot] is written, so
+// score_out may be score (no __restrict__ on the two).
+__global__ void __launch_bounds__(256)
+cand_posterior_kernel(const float* score, const int* __restrict__ cand_len, int B, int K, float* score_out,
+                      float* __restrict__ post, int* __restrict__ best) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= B) return;
+  const float* sc = score + (size_t)c * K;
+  const int* cl = cand_len + (size_t)c * K;
+  float m = -INFINITY;
+  int bk = -1;
+  for (int k = 0; k < K; ++k) {
+    if (cl[k] <= 0) continue;
+    const float s = sc[k];
+    if (s > m || (bk < 0 && s == m)) {  // s == m with no best yet: a score of -inf itself
+      m = s;
+      bk = k;
+    }
+  }
+  float sum = 0.f;
+  for (int k = 0; k < K; ++k)
+    if (cl[k] > 0) sum += expf(sc[k] - m);
+  const float ls = logf(sum);
+  for (int k = 0; k < K; ++k) {
+    const bool live = cl[k] > 0;
+    const float s = sc[k];
+    score_out[(size_t)c * K + k] = live ? s : -INFINITY;
+    if (post) post[(size_t)c * K + k] = live ? (s - m) - ls : -INFINITY;
+  }
+  if (best) best[c] = bk;
+}
+
+hipError_t launch_cand_posterior(const float* score, const int* cand_len, int B, int K, float* score_out, float* post,
+                                 int* best, hipStream_t s) {
+  if (!score || !cand_len || !score_out || B < 1 || K < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cand_posterior_kernel, dim3((B + 255) / 256), dim3(256), 0, s, score, cand_len, B, K, score_out,
+                     post, best);
   return hipGetLastError();
 }
 

@@ -317,6 +317,36 @@ class Engine:
                                                 self._stream()), "nd_score_targets")
         return dict(scores=sc, tok_logp=tl, logp=lp, attn=at, overflow=self._take_overflow())
 
+    def score_candidates(self, signal, lengths, spans=None, cand=None, cand_len=None, return_tok_logp: bool = False,
+                         return_logp: bool = False):
+        """Several candidate targets per chunk on one encoder pass (nd_score_candidates; DESIGN.md section
+        1.8).  cand [B, K, L] int32: a gold row per (chunk, slot) as score_targets takes it (tokens, EOS, then
+        pad_idx); cand_len [B, K] in [0, L], EOS included, 0 = an empty slot; B * K <= max_batch.  Returns
+        dict(scores [B, K] f32: each slot's sum of token log-probabilities (score_targets' quantity), -inf
+        for an empty slot; post [B, K]: score - logsumexp over the chunk's non-empty slots
+        (frontend.candidate_posterior is the same rule), -inf for an empty slot; best [B] int32: the non-empty
+        slot of the largest score, the lowest on a tie, -1 when all are empty; tok_logp [B, K, L] or None;
+        logp [B, K, L, V] or None; overflow)."""
+        if self.cfg.self_attn_type == "average":
+            raise NotImplementedError("score_candidates: average-attention decoders are not supported")
+        signal, lengths, spans, B, T = self._inputs(signal, lengths, spans)
+        if cand is None or cand_len is None:
+            raise ValueError("score_candidates needs cand and cand_len")
+        cand = torch.as_tensor(cand).to(self.device, torch.int32, non_blocking=True).contiguous()
+        cand_len = torch.as_tensor(cand_len).to(self.device, torch.int32, non_blocking=True).contiguous()
+        if cand.dim() != 3 or cand.shape[0] != B or tuple(cand_len.shape) != (B, cand.shape[1]):
+            raise ValueError("cand must be [B, K, L] and cand_len [B, K]")
+        K, L = cand.shape[1], cand.shape[2]
+        sc = torch.empty(B, K, dtype=torch.float32, device=self.device)
+        post = torch.empty(B, K, dtype=torch.float32, device=self.device)
+        best = torch.empty(B, dtype=torch.int32, device=self.device)
+        tl = torch.empty(B, K, L, dtype=torch.float32, device=self.device) if return_tok_logp else None
+        lp = torch.empty(B, K, L, self.cfg.vocab, dtype=torch.float32, device=self.device) if return_logp else None
+        _lib.check(self._L.nd_score_candidates(self._h, _ptr(signal), _ptr(lengths), _ptr(spans), _ptr(cand),
+                                               _ptr(cand_len), B, T, K, L, _ptr(sc), _ptr(post), _ptr(best), _ptr(tl),
+                                               _ptr(lp), self._stream()), "nd_score_candidates")
+        return dict(scores=sc, post=post, best=best, tok_logp=tl, logp=lp, overflow=self._take_overflow())
+
     def token_weights(self, tokens, logp=None, tok_logp=None):
         """The uint16 weights of a call's tokens (nd_token_weights, on the current stream): w =
         min(65535, floor(65535 exp(lp) + 0.5)) with lp = logp[..., token] (``logp`` [..., V], what a translate
@@ -500,6 +530,12 @@ class EnginePool:
         r = self._call("score_targets", signal, lengths, spans, **kw)
         # the gold rows stay referenced like the other inputs (see _call)
         self._held[r["lane"]] = r["inputs"] = r["inputs"] + (kw.get("gold"), kw.get("gold_len"))
+        return r
+
+    def score_candidates(self, signal, lengths, spans=None, **kw):
+        r = self._call("score_candidates", signal, lengths, spans, **kw)
+        # the candidate rows stay referenced like the other inputs (see _call)
+        self._held[r["lane"]] = r["inputs"] = r["inputs"] + (kw.get("cand"), kw.get("cand_len"))
         return r
 
     def token_weights(self, tokens, logp=None, tok_logp=None, lane: int = 0):

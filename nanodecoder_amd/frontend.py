@@ -464,6 +464,27 @@ def token_positions(attn_rows, span) -> np.ndarray:
     return np.maximum.accumulate(c.astype(np.int64), axis=-1).astype(np.int32)
 
 
+def candidate_posterior(scores, cand_len):
+    """The posterior over each chunk's candidate targets (Engine.score_candidates; nd_cand_posterior is the same
+    rule in fp32): ``scores`` [..., K] the candidates' summed log-probabilities, ``cand_len`` [..., K] their
+    lengths, <= 0 for an empty slot.  Returns (post [..., K] float64, best [...] int64): post = score -
+    logsumexp over the non-empty slots, taken about their maximum, -inf in an empty slot; best = the non-empty
+    slot of the largest score, the lowest on a tie, -1 when every slot is empty.  A NaN score is never best and
+    makes its chunk's post values NaN."""
+    s = np.asarray(scores, np.float64)
+    live = np.asarray(cand_len) > 0
+    if s.ndim < 1 or live.shape != s.shape:
+        raise ValueError("scores and cand_len must both be [..., K]")
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        ranked = np.where(live & ~np.isnan(s), s, -np.inf)
+        m = ranked.max(-1, keepdims=True)
+        hit = live & (s == m)  # never a NaN
+        best = np.where(hit.any(-1), hit.argmax(-1), -1).astype(np.int64)
+        lse = np.log(np.where(live, np.exp(s - m), 0.0).sum(-1, keepdims=True))
+        post = np.where(live, (s - m) - lse, -np.inf)
+    return post, best
+
+
 def column_position(n, P):
     """The position of columns with ``n`` votes whose absolute positions sum to ``P`` (ints or integer arrays):
     P // n, and 0 where n is 0; int or int64 array."""

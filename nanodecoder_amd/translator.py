@@ -607,6 +607,95 @@ class Translator(object):
             return [(float(sc[i]), tl[i, : gold_len[i]].tolist(), ps[i, : gold_len[i]].tolist()) for i in range(n)]
         return [(float(sc[i]), tl[i, : gold_len[i]].tolist()) for i in range(n)]
 
+    def score_candidates(self, chunks, candidates, batch_size):
+        """Which of its candidate targets does each chunk's signal support?
+        ``candidates[i]``: a non-empty list of targets for chunk i, each a token string or an id sequence (see
+        _gold_ids).  Returns per chunk (scores, log_posteriors, best): the teacher-forced score of every
+        candidate (what score() gives for it, EOS included), their log-posterior over the chunk's own
+        candidates, and the index of the best one (the first on a tie); the lists are as long as the chunk's
+        candidate list.  Each chunk keeps the span score() gives it.  A chunk's candidates share its encoder
+        pass: consecutive chunks go into one engine call while chunks * K <= max_batch, K = the call's
+        largest candidate count rounded up to a power of two (few captured graphs); the slots a chunk does
+        not fill stay empty and take no part in its posterior."""
+        if batch_size is None:
+            raise ValueError("batch_size must be set")
+        chunks = [parse_chunk(c) for c in chunks]
+        if len(chunks) != len(candidates):
+            raise ValueError("one candidate list per chunk")
+        cap = self.engine.max_batch
+        ids = []
+        for i, cl in enumerate(candidates):
+            cl = [cl] if isinstance(cl, str) else list(cl)
+            if not cl:
+                raise ValueError(f"chunk {i} has no candidates")
+            if len(cl) > cap:
+                raise ValueError(f"chunk {i} has {len(cl)} candidates, more than max_batch = {cap}")
+            ids.append([self._gold_ids(t) for t in cl])
+        if self.cfg.self_attn_type == "average":
+            raise NotImplementedError("scoring targets is not supported for average-attention decoders")
+        spans = []
+        for b0 in range(0, len(chunks), batch_size):
+            part = chunks[b0: b0 + batch_size]
+            spans += [max(len(c) for c in part)] * len(part)
+
+        def slots(n):  # a power of two while one chunk of it fits a call
+            k = 1
+            while k < n:
+                k *= 2
+            return k if k <= cap else n
+
+        out, b0, K = [], 0, 1  # the open call: chunks b0 .. i - 1 at K slots each
+        for i in range(len(chunks)):
+            k = slots(max(K, len(ids[i])))
+            if i > b0 and (i - b0 + 1) * k > cap:
+                out += self._score_cand_batch(chunks[b0:i], spans[b0:i], ids[b0:i], K)
+                b0, k = i, slots(len(ids[i]))
+            K = k
+        if chunks:
+            out += self._score_cand_batch(chunks[b0:], spans[b0:], ids[b0:], K)
+        return out
+
+    def _score_cand_batch(self, chunks, spans, ids, K: int, exact: bool = False):
+        """One engine call of score_candidates(): n chunks of at most K candidates each, n * K <= max_batch."""
+        n = len(chunks)
+        lens = np.array([len(c) for c in chunks], np.int32)
+        if (lens < 1).any():
+            raise ValueError("empty signal chunk")
+        spans = np.asarray(spans, np.int32)
+        if spans.max() > self.engine.max_src_len:
+            raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
+        T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
+        B = _bucket(n, self.engine.max_batch // K)
+        # as _score_batch: rows padded to a multiple of 8 positions (one captured graph per (B, T, K, L))
+        L = min(self.engine.max_steps, (max(len(t) for cl in ids for t in cl) + 1 + 7) // 8 * 8)
+        sig, ln, sp, dev_in = self._stage(B, T)
+        for i, c in enumerate(chunks):
+            sig[i, : len(c)] = c
+        ln[:n], sp[:n] = lens, spans
+        if dev_in is not None:
+            sig, ln, sp = dev_in
+        # padding chunks and the slots a chunk does not fill are empty slots (cand_len 0)
+        cand = np.full((B, K, L), self.cfg.pad_idx, np.int32)
+        cand_len = np.zeros((B, K), np.int32)
+        for i, cl in enumerate(ids):
+            for k, t in enumerate(cl):
+                cand[i, k, : len(t)] = t
+                cand[i, k, len(t)] = self.cfg.eos_idx
+                cand_len[i, k] = len(t) + 1
+        r = self.engine.score_candidates(sig, ln, sp, cand=torch.from_numpy(cand), cand_len=torch.from_numpy(cand_len))
+        if "event" in r:
+            r["event"].synchronize()
+        ov = r.get("overflow")
+        if ov is not None and int(ov.cpu().reshape(-1)[0]) != 0 and not exact:
+            # split-fp16 range guard: the call again with every product in exact fp32 (see _rerun_exact)
+            self.engine.set_exact_fp32(True)
+            try:
+                return self._score_cand_batch(chunks, spans, ids, K, exact=True)
+            finally:
+                self.engine.set_exact_fp32(False)
+        sc, post, best = r["scores"].cpu().numpy(), r["post"].cpu().numpy(), r["best"].cpu().numpy()
+        return [(sc[i, : len(cl)].tolist(), post[i, : len(cl)].tolist(), int(best[i])) for i, cl in enumerate(ids)]
+
     def translate(self, src, tgt=None, src_dir=None, batch_size=None, attn_debug=False):
         """translate/translator.py:181-369.  Returns (all_scores,
         all_predictions): per chunk, n_best scores and n_best strings.  With ``tgt`` (one target per chunk,
