@@ -454,6 +454,51 @@ int nd_assemble_reads_p(const uint8_t* d_bases, const uint32_t* d_bp, const int3
                         uint32_t* d_rpos, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
                         void* stream);
 
+/* Read accuracy against known sequences: the global alignment of P called
+ * reads to their truths in one call.  The reference measures this outside its
+ * own code (minimap2, then matches over alignment length); no reference
+ * equivalent.  No context needed.
+ *
+ * The rule.  Call a[0..n), truth b[0..m), bytes compared for equality (the
+ * caller normalises them: upper case, M written as C on both sides).
+ *   D[i][0] = i, D[0][j] = j,
+ *   D[i][j] = min(D[i-1][j-1] + (a[i-1] != b[j-1]), D[i-1][j] + 1, D[i][j-1] + 1).
+ * Direction at (i, j), taken in this order: diagonal if i, j >= 1 and
+ * D[i-1][j-1] + (a[i-1] != b[j-1]) == D[i][j]; else up if i >= 1 and (j == 0
+ * or D[i-1][j] + 1 == D[i][j]), which consumes a[i-1] only (an inserted base in
+ * the call); else left, which consumes b[j-1] only (a base missing from the
+ * call).  The alignment is the path those directions give from (n, m) back to
+ * (0, 0).
+ *   d_call, d_truth [bytes] u8 and d_call_off, d_truth_off [P + 1] i32: pair p
+ *             is d_call[d_call_off[p] .. d_call_off[p+1]) against the same
+ *             slice of d_truth; empty sides are legal (all insertions, or all
+ *             deletions)
+ *   d_counts  [P, 5] i32: {dist, n_match, n_sub, n_ins, n_del} with
+ *             n_match + n_sub + n_ins == n, n_match + n_sub + n_del == m and
+ *             dist == n_sub + n_ins + n_del; five times -1 when d_status[p] != 0
+ *   d_ops     [d_call_off[P]] u8, may be null: per call base, laid out like
+ *             d_call, 0 = match, 1 = mismatch, 2 = insertion; 0 for the bases
+ *             of a pair whose d_status is not 0
+ *   d_status  [P] i32: 0 = aligned.  Bit 0: n or m above 8192 (distances to
+ *             16384 fit 16 bits; the caller aligns a longer read on the host).
+ *             Bit 1: the pair's directions did not fit into d_work because
+ *             `cells` was understated.
+ * `cells` is the caller's sum of n * m over the pairs within the cap (an
+ * over-estimate is fine).  d_work (8-byte aligned) holds the pairs' 64-bit
+ * offsets, derived on the device, and their packed 2-bit directions; its
+ * layout is internal.  nd_align_seqs_work_bytes(P, cells) = cells / 4 + 16 P +
+ * 64 is the bound for it (-1 for a negative argument); which pairs fit depends
+ * on `cells` alone, not on a larger work_bytes.  Integer min-plus throughout:
+ * the results do not depend on the grid, the order of the pairs or the stream.
+ * P == 0 returns ND_OK at once; a negative P or cells, a work_bytes below the
+ * bound, a null buffer other than d_ops or a misaligned d_work return
+ * ND_ERR_ARG before any HIP call.  Two launches on `stream`: no allocation, no
+ * synchronisation. */
+int64_t nd_align_seqs_work_bytes(int32_t P, int64_t cells);
+int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_t* d_truth,
+                  const int32_t* d_truth_off, int32_t P, int64_t cells, int32_t* d_counts, uint8_t* d_ops,
+                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

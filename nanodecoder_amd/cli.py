@@ -8,6 +8,8 @@ as result/<read>.fasta, segment/<read>.txt and a line of speed.txt
 on (translate.py:97-98).  ``-pack_reads N`` translates N reads per engine pass.
 ``-fastq`` also writes result/<read>.fastq with per-base qualities;
 ``-mod_probs`` (CpG models) result/<read>.mod.fastq with MM / ML tags.
+``-truth FILE`` aligns every read that has a known sequence in FILE to it and
+writes save_data/accuracy.tsv (with ``-fastq`` quality_calibration.tsv too).
 """
 from __future__ import annotations
 
@@ -18,7 +20,9 @@ import os
 import sys
 import time
 
-from . import frontend
+import numpy as np
+
+from . import accuracy, frontend
 from .opts import parse_translate_opts
 
 
@@ -113,7 +117,7 @@ def _extract(args):
 
 
 def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None, mods=None,
-                 moves=None):
+                 moves=None, accuracy_line=None):
     """translate.py:81-98.  ``sequence``: the read already assembled
     (-assembly gpu); None assembles it here.  ``weights`` (-fastq): the
     chunks' per-base weights; ``sequence`` is then (sequence, quality string),
@@ -124,7 +128,9 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
     only with -fastq.  ``moves`` (-moves): the chunks' per-base chunk-relative
     signal positions; ``sequence`` then carries the read positions as its
     last entry ((sequence, positions) without ``weights``), and
-    result/<read>.moves is written before the .fasta too."""
+    result/<read>.moves is written before the .fasta too.  ``accuracy_line``
+    (-truth): the read's line of save_data/accuracy.tsv, appended before the
+    .fasta too.  Returns True when everything was written."""
     try:
         name = file_src.split(".txt")[0]
         rpos = None
@@ -153,6 +159,9 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
         if moves is not None:
             with open(os.path.join(opt.save_data, "result", name + ".moves"), "w") as f:
                 f.write(frontend.moves_record(name, c_bpread, rpos))
+        if accuracy_line is not None:
+            with open(os.path.join(opt.save_data, "accuracy.tsv"), "a") as f:
+                f.write(accuracy_line)
         with open(os.path.join(opt.save_data, "result", name + ".fasta"), "w") as f:
             f.writelines(">%s\n%s" % (name, c_bpread))
         with open(os.path.join(opt.save_data, "segment", file_src), "w+") as f:
@@ -161,11 +170,75 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
         with open(os.path.join(opt.save_data, "speed.txt"), "a+") as f:
             f.writelines("%s\t%0.2f\t%d\t%0.2f\n" % (name, float(time_translate), len(c_bpread),
                                                      len(c_bpread) / max(float(time_translate), 1e-9)))
+        return True
     except Exception:
         print("!!!error!!!data src: " + file_src.split(".txt")[0])
+        return False
 
 
 ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled / of them on the host, this run
+ALIGN_STATS = {"reads": 0, "fallback": 0}     # -truth: reads aligned / of them on the host after a device status
+# -truth, this run: the known sequences (None without the flag), the reads written with and without one, the sums
+# of matches and alignment lengths, and with -fastq the called bases and errors per predicted quality
+TRUTH = {"seqs": None, "evaluated": 0, "missing": 0, "match": 0, "length": 0, "bases": None, "errors": None}
+
+
+def _evaluate_group(opt, group, outs, seqs, weights, mods, positions):
+    """-truth for one translated group: the reads of ``seqs`` still None (-assembly cpu) are assembled here, by
+    the host functions write_output would use, and every read that has a known sequence is aligned to it: one
+    device call for the group (-truth_align gpu) or the host rule.  Returns per read None, or (its accuracy.tsv
+    line, counts, quality string or None, ops or None).  A read whose assembly raises stays None in ``seqs``:
+    write_output assembles it again and reports it."""
+    fastq = weights[0] is not None if weights else False
+    names = [g[0].split(".txt")[0] for g in group]
+    for k, o in enumerate(outs):
+        if seqs[k] is None:
+            try:
+                seqs[k] = frontend.assemble_reads([o[1]], opt.src_seq_length, opt.src_seq_stride,
+                                                  **(dict(weights=[weights[k]]) if weights[k] is not None else {}),
+                                                  **(dict(mod_weights=[mods[k]]) if mods[k] is not None else {}),
+                                                  **(dict(positions=[positions[k]]) if positions[k] is not None
+                                                     else {}))[0]
+            except Exception:
+                seqs[k] = None
+    todo = [k for k in range(len(group)) if seqs[k] is not None and names[k] in TRUTH["seqs"]]
+    res = [None] * len(group)
+    for k in range(len(group)):
+        if seqs[k] is not None and names[k] not in TRUTH["seqs"]:
+            res[k] = ()  # written, without a truth
+    if not todo:
+        return res
+    text = lambda q: q if isinstance(q, str) else q[0]  # noqa: E731
+    called = [accuracy.normalise(text(seqs[k])) for k in todo]
+    truths = [TRUTH["seqs"][names[k]] for k in todo]
+    device = None if getattr(opt, "truth_align", "gpu") == "cpu" else max(0, opt.gpu)
+    try:
+        counts, ops = accuracy.align_reads(called, truths, device=device, want_ops=fastq, stats=ALIGN_STATS)
+    except Exception as e:
+        for k in todo:
+            print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
+        return res
+    for x, k in enumerate(todo):
+        res[k] = (accuracy.accuracy_line(names[k], len(called[x]), len(truths[x]), counts[x]), counts[x],
+                  seqs[k][1] if fastq else None, ops[x] if fastq else None)
+    return res
+
+
+def _account(entry):
+    """A written read's -truth entry (_evaluate_group) into the run's sums."""
+    if entry is None:
+        return
+    if not entry:
+        TRUTH["missing"] += 1
+        return
+    _, counts, quality, ops = entry
+    TRUTH["evaluated"] += 1
+    TRUTH["match"] += int(counts[1])
+    TRUTH["length"] += int(counts[1]) + int(counts[2]) + int(counts[3]) + int(counts[4])
+    if quality is not None:
+        b, e = accuracy.quality_table(quality, ops)
+        TRUTH["bases"] += b
+        TRUTH["errors"] += e
 
 
 def main(opt=None):
@@ -176,8 +249,14 @@ def main(opt=None):
         raise ValueError("-mod_probs is not available together with -attn_debug")
     if getattr(opt, "moves", False) and opt.attn_debug:
         raise ValueError("-moves is not available together with -attn_debug")
+    if getattr(opt, "truth", "") and opt.attn_debug:
+        raise ValueError("-truth is not available together with -attn_debug")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
+    ALIGN_STATS.update(reads=0, fallback=0)
+    TRUTH.update(seqs=accuracy.read_truth(opt.truth) if getattr(opt, "truth", "") else None, evaluated=0, missing=0,
+                 match=0, length=0, bases=np.zeros(accuracy.Q_LEVELS, np.int64),
+                 errors=np.zeros(accuracy.Q_LEVELS, np.int64))
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
         os.makedirs(os.path.join(opt.save_data, sub), exist_ok=True)
     from .translator import build_translator
@@ -213,6 +292,14 @@ def main(opt=None):
     if getattr(opt, "assembly", "cpu") == "gpu":
         logger.info("-assembly gpu: %d of %d reads were assembled on the host (fallback: a chunk of 200 or more "
                     "bases, or text outside ACGTM)" % (ASSEMBLY_STATS["fallback"], ASSEMBLY_STATS["reads"]))
+    if TRUTH["seqs"] is not None:
+        if getattr(opt, "fastq", False):
+            with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:
+                f.writelines(accuracy.calibration_lines(TRUTH["bases"], TRUTH["errors"]))
+        logger.info("-truth: %d reads evaluated, %d without a truth, %d host fallbacks (a read or a truth above %d "
+                    "bases); pooled identity %.6f (%d matches over %d alignment columns)"
+                    % (TRUTH["evaluated"], TRUTH["missing"], ALIGN_STATS["fallback"], accuracy.ALIGN_MAX_LEN,
+                       TRUTH["match"] / TRUTH["length"] if TRUTH["length"] else 0.0, TRUTH["match"], TRUTH["length"]))
     return n_done
 
 
@@ -271,9 +358,18 @@ def _translate_group(opt, translator, group, raw=False):
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    for g, o, seq, w, mw, ps in zip(group, outs, seqs, weights, mods, positions):
-        write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
-                     **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}))
+    if TRUTH["seqs"] is None:
+        for g, o, seq, w, mw, ps in zip(group, outs, seqs, weights, mods, positions):
+            write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
+                         **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}))
+        return len(group)
+    seqs = list(seqs)
+    acc = _evaluate_group(opt, group, outs, seqs, weights, mods, positions)
+    for g, o, seq, w, mw, ps, a in zip(group, outs, seqs, weights, mods, positions, acc):
+        if write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
+                        **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}),
+                        **(dict(accuracy_line=a[0]) if a else {})):
+            _account(a)
     return len(group)
 
 

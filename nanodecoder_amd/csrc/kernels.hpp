@@ -447,6 +447,16 @@ hipError_t launch_token_mod_weights(const int* tokens, const float* logp, int n,
 #define TOKEN_POS_MAX_T (1 << 19)
 hipError_t launch_token_positions(const float* attn, long long ld_chunk, const int* span, int B, int S, int T,
                                   int* pos, hipStream_t s);
+// global alignment of called reads to known sequences (align.hip, which states the rule): pair p is
+// call[call_off[p] .. call_off[p+1]) against the same slice of truth; counts [P, 5] = {dist, n_match, n_sub, n_ins,
+// n_del}, ops (nullable) one byte per call base, status [P] (bit 0: a side above ALIGN_MAX_LEN; bit 1: the pair's
+// directions did not fit, cells understated); work holds align_work_bytes(P, cells) bytes, 8-byte aligned
+#define ALIGN_MAX_LEN 8192
+#define ALIGN_MAX_CELLS (1ll << 60)
+long long align_work_bytes(int P, long long cells);
+hipError_t launch_align_seqs(const unsigned char* call, const int* call_off, const unsigned char* truth,
+                             const int* truth_off, int P, long long cells, int* counts, unsigned char* ops,
+                             int* status, void* work, hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

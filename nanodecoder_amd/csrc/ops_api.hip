@@ -1,5 +1,5 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions): launches on the caller's stream, with no context.
+// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions, nd_align_seqs): launches on the caller's stream, with no context.
 // The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
@@ -422,6 +422,27 @@ int nd_assemble_reads_p(const uint8_t* d_bases, const uint32_t* d_bp, const int3
                 nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
                                           nullptr, d_seq_len, d_status, d_work, (hipStream_t)stream, nullptr, nullptr,
                                           d_bp, d_rpos), ND_ERR_HIP);
+}
+
+int64_t nd_align_seqs_work_bytes(int32_t P, int64_t cells) {
+  return P >= 0 && cells >= 0 && cells <= ALIGN_MAX_CELLS ? (int64_t)nd::align_work_bytes(P, cells) : -1;
+}
+
+int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_t* d_truth,
+                  const int32_t* d_truth_off, int32_t P, int64_t cells, int32_t* d_counts, uint8_t* d_ops,
+                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS)
+    return fail(ND_ERR_ARG, "align_seqs: P and cells must be >= 0 and cells <= 2^60");
+  if (P == 0) return ND_OK;
+  const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "align_seqs: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_align_seqs_work_bytes asks for");
+  if (!d_call || !d_call_off || !d_truth || !d_truth_off || !d_counts || !d_status || !d_work)
+    return fail(ND_ERR_ARG, "align_seqs: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_seqs: d_work must be 8-byte aligned");
+  return status("align_seqs", nd::launch_align_seqs(d_call, d_call_off, d_truth, d_truth_off, P, cells, d_counts,
+                                                    d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
 }
 
 int nd_phred_ratios(double* out, int32_t n) {

@@ -91,6 +91,16 @@ def translate_parser() -> argparse.ArgumentParser:
               "each base was called at (the centroid of the last decoder layer's head-0 context attention, carried "
               "through the assembly vote and made monotone along the read); combines with -fastq, -mod_probs, "
               "-frontend gpu and -assembly gpu; the other outputs are unchanged; not together with -attn_debug")
+    _add(g, "truth", type=str, default="",
+         help="a FASTA file of known sequences (the first word of a header is the read name; M is read as C): every "
+              "read of the run that has one is aligned to it (edit distance, a fixed tie rule) and gets a line of "
+              "save_data/accuracy.tsv: name, called, truth, match, sub, ins, del, identity = matches over alignment "
+              "length; the log ends with the pooled identity; with -fastq, save_data/quality_calibration.tsv sets "
+              "the predicted qualities against the observed errors (Q, bases, errors, empirical_Q); the other "
+              "outputs are unchanged; not together with -attn_debug")
+    _add(g, "truth_align", default="gpu", choices=["gpu", "cpu"],
+         help="where -truth aligns: gpu = one device call per translated group on -gpu's device (align.hip; a read "
+              "above 8192 bases is aligned on the host and counted in the log), cpu = the same rule in numpy")
     return p
 
 
