@@ -499,6 +499,75 @@ int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_
                   const int32_t* d_truth_off, int32_t P, int64_t cells, int32_t* d_counts, uint8_t* d_ops,
                   int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* Read accuracy against a shared reference (a genome, a control sequence):
+ * where each of P segments of called reads lies in it and on which strand
+ * (nd_locate_segs), then the alignment of each segment to the window found,
+ * with free ends on the reference side (nd_align_fit).  The reference maps its
+ * reads outside its own code (pipeline.evaluate.sh: minimap2); no reference
+ * equivalent.  No context needed.  Integers throughout: the results do not
+ * depend on the grid, the order of the segments or the stream, and equal the
+ * host rule of nanodecoder_amd/accuracy.py (locate_host, fit_host).
+ *
+ * The reference is R records concatenated with no separator, d_rec_off [R + 1]
+ * i32 their starts (d_rec_off[R] = the total, at most 2^23).  Base codes A, C,
+ * G, T = 0..3, any other byte invalid.  A k-mer is 15 consecutive valid bases
+ * inside one record, its code the 30-bit number with the first base in the
+ * highest bits.  The index is (code, pos) of every k-mer of the forward
+ * reference sorted by code, then pos, without the codes that occur more than 8
+ * times: d_idx_code, d_idx_pos [idx_len] u32.
+ *
+ * nd_locate_segs.  Segment p is d_call[d_call_off[p] .. d_call_off[p+1]), n
+ * bases.  For strand 0 (the segment) and strand 1 (its reverse complement;
+ * invalid bytes stay as they are): every k-mer of the query at offset x and
+ * every index entry (code, y) with its code gives one vote to bin
+ * (y - x + 4096) >> 9; score[b] = votes[b] + votes[b + 1]; the hit is the
+ * (strand, b) with the largest score, strand 0 before strand 1, then the
+ * lowest b.  With lo = (b << 9) - 4096 the window is that of the record
+ * containing clamp(lo + 512 + n / 2, 0, total - 1): w0 = max(record start,
+ * lo - 1024), w1 = min(record end, lo + 1024 + n + 1024), so w1 - w0 <= n +
+ * 3072.
+ *   d_hit     [P, 4] i32: {strand, w0, w1, votes = the hit's score}; w0 = w1 =
+ *             0 for an unmapped segment
+ *   d_status  [P] i32: 0 = mapped; bit 0 = unmapped: a score below 8, n below
+ *             15 or above 4096, or a total above 2^23
+ *   d_call_or [d_call_off[P]] u8: the oriented segments, laid out like d_call
+ *             (the reverse complement for strand 1); must not be d_call
+ * One workgroup per segment, one launch on `stream`: no allocation, no
+ * synchronisation.  P == 0 returns ND_OK at once; a negative P, idx_len or R or
+ * a null buffer (the index arrays may be null when idx_len == 0) return
+ * ND_ERR_ARG before any HIP call.
+ *
+ * nd_align_fit.  Pair p is d_call_or[d_call_off[p] .. d_call_off[p+1]) = a[0..n)
+ * against the window b[0..m) = d_ref[d_hit[p][1] .. d_hit[p][2]) of the whole
+ * reference d_ref [ref_len] u8.  Borders D[0][j] = 0, D[i][0] = i; recurrence
+ * and direction order as nd_align_seqs; j* is the smallest j in 0..m with
+ * D[n][j] minimal; the path runs from (n, j*) until i == 0, nothing consumed
+ * on row 0, and at j == 0 with i > 0 the rest is insertions.
+ *   d_counts  [P, 5] i32: {dist = D[n][j*], n_match, n_sub, n_ins, n_del},
+ *             n_match + n_sub + n_ins == n, n_match + n_sub + n_del == the
+ *             span's length; five times -1 when d_status[p] != 0
+ *   d_span    [P, 2] i32: the aligned interval of d_ref, {w0 + t_start, w0 +
+ *             j*}; twice -1 when d_status[p] != 0
+ *   d_ops     [d_call_off[P]] u8, may be null: per oriented call base, 0 =
+ *             match, 1 = mismatch, 2 = insertion; 0 when d_status[p] != 0
+ *   d_status  [P] i32, read and written: a pair that comes in with bit 0 set
+ *             (unmapped) is skipped and keeps its status; otherwise 0 =
+ *             aligned, bit 1 = the pair's directions did not fit because
+ *             `cells` was understated, bit 2 = n or m above 8192 or a window
+ *             outside [0, ref_len]
+ * `cells` is the caller's bound on the sum of n * m over the pairs aligned
+ * (the sum of n * (n + 3072) holds after nd_locate_segs); d_work and
+ * nd_align_fit_work_bytes are as for nd_align_seqs, and so are the argument
+ * errors.  Two launches on `stream`; after nd_locate_segs on the same stream
+ * no host round trip is needed in between. */
+int nd_locate_segs(const uint8_t* d_call, const int32_t* d_call_off, int32_t P, const uint32_t* d_idx_code,
+                   const uint32_t* d_idx_pos, int32_t idx_len, const int32_t* d_rec_off, int32_t R, int32_t* d_hit,
+                   int32_t* d_status, uint8_t* d_call_or, void* stream);
+int64_t nd_align_fit_work_bytes(int32_t P, int64_t cells);
+int nd_align_fit(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ref, int32_t ref_len,
+                 const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span, uint8_t* d_ops,
+                 int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

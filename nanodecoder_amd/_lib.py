@@ -90,6 +90,9 @@ SIGNATURES = {
     "nd_assemble_reads_p": (_I, [_P, _P, _P, _P, _I, _I, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "nd_align_seqs_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
     "nd_align_seqs": (_I, [_P, _P, _P, _P, _I, ctypes.c_int64, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "nd_locate_segs": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
+    "nd_align_fit_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
+    "nd_align_fit": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
     "nd_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "nd_set_graphs": (_I, [_P, _I]),
     "nd_set_timing": (_I, [_P, _I]),

@@ -20,6 +20,10 @@ upper case, M written as C on both sides; methylation accuracy is out of scope).
     n_match + n_sub + n_del == m, dist == n_sub + n_ins + n_del
   identity   : n_match / (n_match + n_sub + n_ins + n_del) in double, 0.0 when that sum is 0 (PAF column 10 over
     column 11)
+
+Against a shared reference (a genome, a control sequence) a read is a fragment from either strand: the second half
+of this file maps it (read_reference, locate_host, fit_host, map_reads; nd_locate_segs and nd_align_fit on the
+device) and states those rules there.
 """
 from __future__ import annotations
 
@@ -260,3 +264,357 @@ def accuracy_line(name, n_called, n_truth, counts):
     """One line of accuracy.tsv: name, called, truth, match, sub, ins, del, identity (%.6f)."""
     c = [int(v) for v in counts]
     return "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%.6f\n" % (name, n_called, n_truth, c[1], c[2], c[3], c[4], identity(c))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Read accuracy against a shared reference (-truth_ref): where a piece of a read lies in a genome or a control
+# sequence, on which strand, and its alignment there with free ends on the reference side.  Integer rules, on the
+# host (locate_host, fit_host) or for all segments of a list of reads in two device calls (nd_locate_segs,
+# csrc/locate.hip; nd_align_fit, csrc/align.hip) with the same integers.
+#
+# Reference : the FASTA's records, normalised, concatenated with no separator; rec_off[R + 1] their starts.
+# k-mer     : MAP_K consecutive valid bases (A, C, G, T = 0..3) inside one record; code = the 30-bit number with the
+#             first base in the highest bits.
+# index     : (code, pos) of every k-mer of the forward reference, sorted by code, then pos, without the codes that
+#             occur more than MAP_OCC_MAX times; two uint32 arrays.
+# segments  : a call of n bases is cut into nseg = max(1, ceil(n / MAP_SEG)) segments, segment s = [s n div nseg,
+#             (s + 1) n div nseg); each is mapped on its own, a read's counts are the sums over its mapped segments.
+# locate    : for strand 0 (the segment q) and strand 1 (its reverse complement, invalid bytes as they are): every
+#             k-mer of the query at offset x and every index entry (code, y) with its code votes for bin
+#             (y - x + MAP_SEG) >> MAP_BIN_SHIFT; score[b] = votes[b] + votes[b + 1]; the hit is the (strand, b) of
+#             the largest score, strand 0 before strand 1, then the lowest b; votes = that score; below
+#             MAP_MIN_VOTES, or n < MAP_K (or n > MAP_SEG): unmapped, window (0, 0).
+# window    : lo = (b << 9) - MAP_SEG; the record containing clamp(lo + 512 + n div 2, 0, total - 1); w0 =
+#             max(record start, lo - MAP_PAD), w1 = min(record end, lo + 1024 + n + MAP_PAD): w1 - w0 <= n + 3072.
+# fit       : call a[0..n) against the window b[0..m): D[0][j] = 0, D[i][0] = i, recurrence and direction order of
+#             the rule at the top; j* the smallest j with D[n][j] minimal; the path runs from (n, j*) until i == 0,
+#             nothing consumed on row 0, and at j == 0 with i > 0 the rest is insertions.  counts = {D[n][j*],
+#             n_match, n_sub, n_ins, n_del}, span (t_start, t_end = j*) in window coordinates:
+#             n_match + n_sub + n_ins == n, n_match + n_sub + n_del == t_end - t_start.
+MAP_K = 15
+MAP_OCC_MAX = 8
+MAP_SEG = 4096
+MAP_BIN_SHIFT = 9
+MAP_PAD = 1024
+MAP_MIN_VOTES = 8
+MAP_REF_MAX = 1 << 23
+MAP_STATUS_UNMAPPED = 1   # status bit 0 of nd_locate_segs (kept by nd_align_fit)
+OP_UNMAPPED = 255         # map_reads: the op of a base in an unmapped segment
+
+_CODE = np.full(256, 255, np.uint8)
+_CODE[[ord(c) for c in "ACGT"]] = [0, 1, 2, 3]
+_COMPLEMENT = np.arange(256, dtype=np.uint8)
+_COMPLEMENT[[ord(c) for c in "ACGT"]] = [ord(c) for c in "TGCA"]
+
+
+def reverse_complement(seq) -> np.ndarray:
+    """The bytes of ``seq`` reversed, A <-> T and C <-> G; any other byte stays as it is."""
+    return _COMPLEMENT[_bytes(seq)[::-1]]
+
+
+def _kmers(seq):
+    """(code uint32 [L], valid bool [L]), L = max(0, size - MAP_K + 1): the k-mer starting at every position."""
+    c = _CODE[_bytes(seq)]
+    L = max(0, int(c.size) - MAP_K + 1)
+    code = np.zeros(L, np.uint32)
+    bad = np.zeros(L, np.int32)
+    for k in range(MAP_K if L else 0):
+        part = c[k: k + L]
+        code = (code << np.uint32(2)) | (part & 3).astype(np.uint32)
+        bad += part > 3
+    return code, bad == 0
+
+
+def build_index(seq, rec_off, device=None):
+    """(code uint32 [L], pos uint32 [L]): the index of the rule above.  The k-mers and the occurrence filter are
+    numpy; the sort of the 64-bit key (code << 32 | pos) is numpy's, or torch.sort on ``device``."""
+    rec_off = np.asarray(rec_off, np.int64)
+    code, valid = _kmers(seq)
+    pos = np.arange(code.size, dtype=np.int64)
+    # inside one record: the k-mer's first and last base in the same one
+    rec = np.searchsorted(rec_off[:-1], pos, side="right")
+    valid &= pos + MAP_K <= rec_off[rec]
+    key = (code[valid].astype(np.int64) << 32) | pos[valid]
+    if device is None:
+        key = np.sort(key)
+    else:
+        import torch
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        key = torch.sort(torch.from_numpy(key).to(dev))[0].cpu().numpy()
+    code = (key >> 32).astype(np.uint32)
+    first = np.flatnonzero(np.r_[True, code[1:] != code[:-1]]) if code.size else np.zeros(0, np.int64)
+    runs = np.diff(np.r_[first, code.size])
+    keep = np.repeat(runs <= MAP_OCC_MAX, runs)
+    return np.ascontiguousarray(code[keep]), (key[keep] & 0xFFFFFFFF).astype(np.uint32)
+
+
+class Reference:
+    """A shared reference: ``names`` of its R records, ``seq`` (uint8, the records concatenated), ``rec_off``
+    (int32 [R + 1]) and ``index`` (build_index, built on first use)."""
+
+    def __init__(self, names, seqs):
+        parts = [_bytes(s) for s in seqs]
+        total = sum(int(x.size) for x in parts)
+        if total > MAP_REF_MAX:
+            raise ValueError("a reference of %d bases: more than MAP_REF_MAX = %d" % (total, MAP_REF_MAX))
+        self.names = list(names)
+        self.seq = np.concatenate(parts) if parts else np.zeros(0, np.uint8)
+        self.rec_off = np.zeros(len(parts) + 1, np.int32)
+        self.rec_off[1:] = np.cumsum([x.size for x in parts], dtype=np.int64)
+        self._index = None
+        self._device = {}
+
+    @property
+    def total(self):
+        return int(self.rec_off[-1])
+
+    @property
+    def index(self):
+        if self._index is None:
+            self._index = build_index(self.seq, self.rec_off)
+        return self._index
+
+    def record_of(self, pos):
+        """The record that holds base ``pos`` of the concatenation (0 <= pos < total)."""
+        return int(np.searchsorted(self.rec_off[:-1], pos, side="right")) - 1
+
+    def on_device(self, dev):
+        """(seq uint8 [total + 1], rec_off int32 [R + 1], idx_code, idx_pos int32 bit patterns [L]) as tensors on
+        ``dev``, uploaded once per device.  An index not built yet is built here with the device's sort (the same
+        arrays as the host build's)."""
+        import torch
+        key = str(dev)
+        if key not in self._device:
+            if self._index is None:
+                self._index = build_index(self.seq, self.rec_off, device=dev)
+            code, pos = self.index
+            seq = np.concatenate([self.seq, np.zeros(1, np.uint8)])
+            self._device[key] = tuple(torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in
+                                      (seq, self.rec_off, code.view(np.int32), pos.view(np.int32)))
+        return self._device[key]
+
+
+def read_reference(path):
+    """The Reference of a FASTA file: every record in the file's order (a repeated name stays a record of its
+    own), named by the first word of its header, normalised as read_truth does.  More than MAP_REF_MAX bases in
+    total is a ValueError."""
+    names, seqs, parts = [], [], None
+    with open(path) as f:
+        for line in f:
+            line = line.strip()
+            if line.startswith(">"):
+                if parts is not None:
+                    seqs.append(normalise("".join(parts)))
+                words = line[1:].split()
+                names.append(words[0] if words else "")
+                parts = []
+            elif parts is not None and line:
+                parts.append(line)
+    if parts is not None:
+        seqs.append(normalise("".join(parts)))
+    return Reference(names, seqs)
+
+
+def segments(n):
+    """[(start, end)] of a call of n bases: max(1, ceil(n / MAP_SEG)) segments of nearly equal length."""
+    nseg = max(1, -(-int(n) // MAP_SEG))
+    return [(s * n // nseg, (s + 1) * n // nseg) for s in range(nseg)]
+
+
+def locate_host(seg, ref):
+    """(mapped, strand, w0, w1, votes) of one segment by the rule above."""
+    q = _bytes(seg)
+    n, total = int(q.size), ref.total
+    icode, ipos = ref.index
+    if n < MAP_K or n > MAP_SEG or total < MAP_K or icode.size == 0:
+        return False, 0, 0, 0, 0
+    nbins = ((total + MAP_SEG) >> MAP_BIN_SHIFT) + 1
+    best = (0, 0, 0)  # score, strand, b
+    for strand in (0, 1):
+        code, valid = _kmers(q if strand == 0 else reverse_complement(q))
+        xs = np.flatnonzero(valid)
+        lo = np.searchsorted(icode, code[xs], side="left")
+        cnt = np.searchsorted(icode, code[xs], side="right") - lo
+        x = np.repeat(xs, cnt)
+        entry = np.repeat(lo, cnt) + (np.arange(int(cnt.sum())) - np.repeat(np.cumsum(cnt) - cnt, cnt))
+        votes = np.bincount((ipos[entry].astype(np.int64) - x + MAP_SEG) >> MAP_BIN_SHIFT, minlength=nbins + 1)
+        score = votes[:nbins] + votes[1: nbins + 1]
+        b = int(np.argmax(score))  # the lowest b of the largest score
+        if int(score[b]) > best[0]:
+            best = (int(score[b]), strand, b)
+    votes, strand, b = best
+    if votes < MAP_MIN_VOTES:
+        return False, strand, 0, 0, votes
+    lo = (b << MAP_BIN_SHIFT) - MAP_SEG
+    r = ref.record_of(min(max(lo + (1 << MAP_BIN_SHIFT) + n // 2, 0), total - 1))
+    w0 = max(int(ref.rec_off[r]), lo - MAP_PAD)
+    w1 = min(int(ref.rec_off[r + 1]), lo + (2 << MAP_BIN_SHIFT) + n + MAP_PAD)
+    return True, strand, w0, w1, votes
+
+
+def fit_host(call, window):
+    """(counts int32 [5], (t_start, t_end), ops uint8 [n]) of a call against a window by the fit rule: numpy over
+    the rows (D[i][j] = j + the running minimum of min(diagonal, up)[k] - k), one direction byte per cell, then
+    the traceback."""
+    a, b = _bytes(call), _bytes(window)
+    n, m = int(a.size), int(b.size)
+    ops = np.zeros(n, np.uint8)
+    dirs = np.zeros((n, m), np.uint8)  # cell (i, j) at [i - 1, j - 1]: 0 diagonal, 1 up, 2 left
+    prev = np.zeros(m + 1, np.int32)   # D[0][j] = 0
+    ramp = np.arange(m + 1, dtype=np.int32)
+    for i in range(1, n + 1):
+        t = np.empty(m + 1, np.int32)
+        t[0] = i
+        diag = prev[:-1] + (b != a[i - 1])
+        up = prev[1:] + 1
+        np.minimum(diag, up, out=t[1:])
+        cur = np.minimum.accumulate(t - ramp) + ramp
+        dirs[i - 1] = np.where(diag == cur[1:], 0, np.where(up == cur[1:], 1, 2))
+        prev = cur
+    jstar = int(np.argmin(prev)) if n else 0
+    i, j = n, jstar
+    n_match = n_sub = n_ins = n_del = 0
+    while i > 0:
+        if j == 0:
+            ops[:i] = OP_INS
+            n_ins += i
+            break
+        d = dirs[i - 1, j - 1]
+        if d == 0:
+            if a[i - 1] != b[j - 1]:
+                ops[i - 1] = OP_SUB
+                n_sub += 1
+            else:
+                n_match += 1
+            i -= 1
+            j -= 1
+        elif d == 1:
+            ops[i - 1] = OP_INS
+            n_ins += 1
+            i -= 1
+        else:
+            n_del += 1
+            j -= 1
+    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), (j, jstar), ops
+
+
+def map_host(call, ref):
+    """(counts int32 [5], segment records, ops uint8 [n]) of one call: its segments located and fitted on the
+    host.  A segment record is (seg_start, seg_end, strand, rec, ref_start, ref_end, votes, counts) with the
+    reference interval in the concatenation's coordinates; only mapped segments have one.  ops is per base of the
+    call as written (a strand-1 segment's reversed back), OP_UNMAPPED in an unmapped segment."""
+    a = _bytes(call)
+    total, recs, ops = np.zeros(5, np.int32), [], np.full(a.size, OP_UNMAPPED, np.uint8)
+    for s0, s1 in segments(a.size):
+        mapped, strand, w0, w1, votes = locate_host(a[s0:s1], ref)
+        if not mapped:
+            continue
+        oriented = a[s0:s1] if strand == 0 else reverse_complement(a[s0:s1])
+        counts, (t0, t1), o = fit_host(oriented, ref.seq[w0:w1])
+        ops[s0:s1] = o if strand == 0 else o[::-1]
+        total += counts
+        recs.append((s0, s1, strand, ref.record_of(w0), w0 + t0, w0 + t1, votes, counts))
+    return total, recs, ops
+
+
+def _map_device(call, seg_off, ref, device, want_ops):
+    """nd_locate_segs, then nd_align_fit, on the CURRENT stream of ``device`` with no host round trip in between:
+    (hit int32 [P, 4], status int32 [P], counts int32 [P, 5], span int32 [P, 2], oriented ops uint8 [bytes] or
+    None) on the host."""
+    import ctypes
+
+    import torch
+
+    from . import _lib
+    from .frontend import _pinned
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    P = len(seg_off) - 1
+    n = np.diff(seg_off).astype(np.int64)
+    cells = int((n * (n + 2 * MAP_PAD + (2 << MAP_BIN_SHIFT))).sum())
+    L = _lib.lib()
+    work_bytes = int(L.nd_align_fit_work_bytes(P, cells))
+    if work_bytes < 0:
+        raise ValueError("nd_align_fit_work_bytes refused P = %d, cells = %d" % (P, cells))
+    with torch.cuda.device(dev):
+        seq_d, rec_d, code_d, pos_d = ref.on_device(dev)
+        off_d = _pinned(seg_off).to(dev, non_blocking=True)
+        call_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
+        if call.size:
+            call_d[: call.size].copy_(_pinned(call), non_blocking=True)
+        or_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
+        out_d = torch.zeros(P * 12, dtype=torch.int32, device=dev)  # hit [P, 4], status [P], counts [P, 5], span [P, 2]
+        ops_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev) if want_ops else None
+        work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        hit_d, status_d, counts_d, span_d = out_d, out_d[4 * P:], out_d[5 * P:], out_d[10 * P:]
+        _lib.check(L.nd_locate_segs(p(call_d), p(off_d), P, p(code_d), p(pos_d), int(code_d.numel()), p(rec_d),
+                                    int(rec_d.numel()) - 1, p(hit_d), p(status_d), p(or_d), stream), "nd_locate_segs")
+        _lib.check(L.nd_align_fit(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d), p(span_d),
+                                  p(ops_d) if want_ops else None, p(status_d), p(work_d), work_bytes, stream),
+                   "nd_align_fit")
+        out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
+        ops = ops_d.cpu().numpy()[: call.size] if want_ops else None
+    return (out[: 4 * P].reshape(P, 4).copy(), out[4 * P: 5 * P].copy(), out[5 * P: 10 * P].reshape(P, 5).copy(),
+            out[10 * P:].reshape(P, 2).copy(), ops)
+
+
+def map_reads(calls, ref, device=None, want_ops=False, stats=None):
+    """The rule for a list of calls: (counts int32 [reads, 5], per read its list of segment records, per read its
+    ops or None without ``want_ops``), each as map_host gives them.  ``device=None`` is map_host read by read.
+    Otherwise all segments of all reads are one nd_locate_segs call and one nd_align_fit call on the current torch
+    stream of ``device``: a read of any length runs there.  ``stats`` (a dict) gets "reads", "segments" and
+    "unmapped" (segments) increased."""
+    calls = [_bytes(c) for c in calls]
+    if device is None:
+        res = [map_host(c, ref) for c in calls]
+    else:
+        segs = [segments(c.size) for c in calls]
+        seg_off = np.zeros(sum(len(s) for s in segs) + 1, np.int64)
+        base, k = 0, 0
+        for c, sg in zip(calls, segs):
+            for _, s1 in sg:
+                k += 1
+                seg_off[k] = base + s1
+            base += int(c.size)
+        if base >= 2 ** 31:
+            raise ValueError("more than 2^31 - 1 bases in one mapping call")
+        res = []
+        if calls:
+            flat = np.concatenate(calls) if base else np.zeros(0, np.uint8)
+            hit, status, counts, span, ops_or = _map_device(flat, seg_off.astype(np.int32), ref, device, want_ops)
+            if (status & ~MAP_STATUS_UNMAPPED).any():
+                raise RuntimeError("nd_align_fit status %s" % sorted(set(status.tolist())))
+            k = 0
+            for c, sg in zip(calls, segs):
+                total, recs, ops = np.zeros(5, np.int32), [], np.full(c.size, OP_UNMAPPED, np.uint8)
+                for s0, s1 in sg:
+                    if status[k] == 0:
+                        strand, w0 = int(hit[k, 0]), int(hit[k, 1])
+                        total += counts[k]
+                        recs.append((s0, s1, strand, ref.record_of(w0), int(span[k, 0]), int(span[k, 1]),
+                                     int(hit[k, 3]), counts[k].copy()))
+                        if want_ops:
+                            o = ops_or[seg_off[k]: seg_off[k + 1]]
+                            ops[s0:s1] = o if strand == 0 else o[::-1]
+                    k += 1
+                res.append((total, recs, ops))
+    if stats is not None:
+        nseg = sum(len(segments(c.size)) for c in calls)
+        stats["reads"] = stats.get("reads", 0) + len(calls)
+        stats["segments"] = stats.get("segments", 0) + nseg
+        stats["unmapped"] = stats.get("unmapped", 0) + nseg - sum(len(r[1]) for r in res)
+    counts = np.asarray([r[0] for r in res], np.int32).reshape(len(calls), 5)
+    return counts, [r[1] for r in res], ([r[2] for r in res] if want_ops else None)
+
+
+def paf_line(name, n_called, rec, ref):
+    """One line of mapping.paf for a segment record: the 12 PAF columns (query coordinates on the read as written,
+    target coordinates inside the record, matches, block length = match + sub + ins + del, mapq 255) and vt:i: =
+    the locate votes."""
+    s0, s1, strand, r, t0, t1, votes, counts = rec
+    c = [int(v) for v in counts]
+    base = int(ref.rec_off[r])
+    return "%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tvt:i:%d\n" % (
+        name, n_called, s0, s1, "-" if strand else "+", ref.names[r], int(ref.rec_off[r + 1]) - base, t0 - base,
+        t1 - base, c[1], c[1] + c[2] + c[3] + c[4], votes)

@@ -10,6 +10,8 @@ on (translate.py:97-98).  ``-pack_reads N`` translates N reads per engine pass.
 ``-mod_probs`` (CpG models) result/<read>.mod.fastq with MM / ML tags.
 ``-truth FILE`` aligns every read that has a known sequence in FILE to it and
 writes save_data/accuracy.tsv (with ``-fastq`` quality_calibration.tsv too).
+``-truth_ref FILE`` maps every read to a shared reference instead (segments of
+at most 4096 bases, either strand) and also writes save_data/mapping.paf.
 """
 from __future__ import annotations
 
@@ -117,7 +119,7 @@ def _extract(args):
 
 
 def write_output(opt, file_src, all_predictions, time_translate, sequence=None, weights=None, mods=None,
-                 moves=None, accuracy_line=None):
+                 moves=None, accuracy_line=None, paf_lines=None):
     """translate.py:81-98.  ``sequence``: the read already assembled
     (-assembly gpu); None assembles it here.  ``weights`` (-fastq): the
     chunks' per-base weights; ``sequence`` is then (sequence, quality string),
@@ -129,8 +131,9 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
     signal positions; ``sequence`` then carries the read positions as its
     last entry ((sequence, positions) without ``weights``), and
     result/<read>.moves is written before the .fasta too.  ``accuracy_line``
-    (-truth): the read's line of save_data/accuracy.tsv, appended before the
-    .fasta too.  Returns True when everything was written."""
+    (-truth, -truth_ref): the read's line of save_data/accuracy.tsv, appended
+    before the .fasta too, and ``paf_lines`` (-truth_ref) its mapped segments'
+    lines of save_data/mapping.paf.  Returns True when everything was written."""
     try:
         name = file_src.split(".txt")[0]
         rpos = None
@@ -162,6 +165,9 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
         if accuracy_line is not None:
             with open(os.path.join(opt.save_data, "accuracy.tsv"), "a") as f:
                 f.write(accuracy_line)
+        if paf_lines:
+            with open(os.path.join(opt.save_data, "mapping.paf"), "a") as f:
+                f.writelines(paf_lines)
         with open(os.path.join(opt.save_data, "result", name + ".fasta"), "w") as f:
             f.writelines(">%s\n%s" % (name, c_bpread))
         with open(os.path.join(opt.save_data, "segment", file_src), "w+") as f:
@@ -180,17 +186,14 @@ ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled /
 ALIGN_STATS = {"reads": 0, "fallback": 0}     # -truth: reads aligned / of them on the host after a device status
 # -truth, this run: the known sequences (None without the flag), the reads written with and without one, the sums
 # of matches and alignment lengths, and with -fastq the called bases and errors per predicted quality
-TRUTH = {"seqs": None, "evaluated": 0, "missing": 0, "match": 0, "length": 0, "bases": None, "errors": None}
+# (-truth_ref: "ref" the shared reference, "missing" the reads written without a mapped segment)
+TRUTH = {"seqs": None, "ref": None, "evaluated": 0, "missing": 0, "match": 0, "length": 0, "bases": None,
+         "errors": None}
+MAP_STATS = {"reads": 0, "segments": 0, "unmapped": 0}  # -truth_ref, written reads: their segments, those unmapped
 
 
-def _evaluate_group(opt, group, outs, seqs, weights, mods, positions):
-    """-truth for one translated group: the reads of ``seqs`` still None (-assembly cpu) are assembled here, by
-    the host functions write_output would use, and every read that has a known sequence is aligned to it: one
-    device call for the group (-truth_align gpu) or the host rule.  Returns per read None, or (its accuracy.tsv
-    line, counts, quality string or None, ops or None).  A read whose assembly raises stays None in ``seqs``:
-    write_output assembles it again and reports it."""
-    fastq = weights[0] is not None if weights else False
-    names = [g[0].split(".txt")[0] for g in group]
+def _assemble_missing(opt, outs, seqs, weights, mods, positions):
+    """The reads of ``seqs`` still None, assembled by the host functions write_output would use."""
     for k, o in enumerate(outs):
         if seqs[k] is None:
             try:
@@ -201,6 +204,51 @@ def _evaluate_group(opt, group, outs, seqs, weights, mods, positions):
                                                      else {}))[0]
             except Exception:
                 seqs[k] = None
+
+
+def _evaluate_group_ref(opt, names, seqs, fastq):
+    """-truth_ref for one translated group: every assembled read is mapped to the shared reference, all
+    segments of the group in one locate call and one fit call (-truth_align gpu) or by the host rule.  Returns per
+    read None, or (its accuracy.tsv line, None for a read without a mapped segment; the summed counts; quality
+    string or None; ops or None; its mapping.paf lines; (its segments, those of them mapped)).  The run's sums
+    take a read's entry only once the read is written (_account)."""
+    ref = TRUTH["ref"]
+    todo = [k for k in range(len(names)) if seqs[k] is not None]
+    res = [None] * len(names)
+    if not todo:
+        return res
+    text = lambda q: q if isinstance(q, str) else q[0]  # noqa: E731
+    called = [accuracy.normalise(text(seqs[k])) for k in todo]
+    device = None if getattr(opt, "truth_align", "gpu") == "cpu" else max(0, opt.gpu)
+    try:
+        counts, recs, ops = accuracy.map_reads(called, ref, device=device, want_ops=fastq)
+    except Exception as e:
+        for k in todo:
+            print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
+        return res
+    for x, k in enumerate(todo):
+        nseg = (len(accuracy.segments(len(called[x]))), len(recs[x]))
+        if not recs[x]:
+            res[k] = (None, counts[x], None, None, [], nseg)
+            continue
+        span = sum(r[5] - r[4] for r in recs[x])
+        res[k] = (accuracy.accuracy_line(names[k], len(called[x]), span, counts[x]), counts[x],
+                  seqs[k][1] if fastq else None, ops[x] if fastq else None,
+                  [accuracy.paf_line(names[k], len(called[x]), r, ref) for r in recs[x]], nseg)
+    return res
+
+
+def _evaluate_group(opt, group, outs, seqs, weights, mods, positions):
+    """-truth for one translated group: the reads of ``seqs`` still None (-assembly cpu) are assembled here, by
+    the host functions write_output would use, and every read that has a known sequence is aligned to it: one
+    device call for the group (-truth_align gpu) or the host rule.  Returns per read None, or (its accuracy.tsv
+    line, counts, quality string or None, ops or None).  A read whose assembly raises stays None in ``seqs``:
+    write_output assembles it again and reports it."""
+    fastq = weights[0] is not None if weights else False
+    names = [g[0].split(".txt")[0] for g in group]
+    _assemble_missing(opt, outs, seqs, weights, mods, positions)
+    if TRUTH["ref"] is not None:
+        return _evaluate_group_ref(opt, names, seqs, fastq)
     todo = [k for k in range(len(group)) if seqs[k] is not None and names[k] in TRUTH["seqs"]]
     res = [None] * len(group)
     for k in range(len(group)):
@@ -231,11 +279,21 @@ def _account(entry):
     if not entry:
         TRUTH["missing"] += 1
         return
-    _, counts, quality, ops = entry
+    line, counts, quality, ops = entry[:4]
+    if len(entry) > 4:  # -truth_ref
+        MAP_STATS["reads"] += 1
+        MAP_STATS["segments"] += entry[5][0]
+        MAP_STATS["unmapped"] += entry[5][0] - entry[5][1]
+        if line is None:
+            TRUTH["missing"] += 1
+            return
     TRUTH["evaluated"] += 1
     TRUTH["match"] += int(counts[1])
     TRUTH["length"] += int(counts[1]) + int(counts[2]) + int(counts[3]) + int(counts[4])
     if quality is not None:
+        if len(entry) > 4:  # -truth_ref: the bases of the mapped segments only
+            keep = ops != accuracy.OP_UNMAPPED
+            quality, ops = np.frombuffer(quality.encode("ascii"), np.uint8)[keep].tobytes(), ops[keep]
         b, e = accuracy.quality_table(quality, ops)
         TRUTH["bases"] += b
         TRUTH["errors"] += e
@@ -251,10 +309,17 @@ def main(opt=None):
         raise ValueError("-moves is not available together with -attn_debug")
     if getattr(opt, "truth", "") and opt.attn_debug:
         raise ValueError("-truth is not available together with -attn_debug")
+    if getattr(opt, "truth_ref", "") and opt.attn_debug:
+        raise ValueError("-truth_ref is not available together with -attn_debug")
+    if getattr(opt, "truth_ref", "") and getattr(opt, "truth", ""):
+        raise ValueError("-truth_ref and -truth exclude each other")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
     ALIGN_STATS.update(reads=0, fallback=0)
-    TRUTH.update(seqs=accuracy.read_truth(opt.truth) if getattr(opt, "truth", "") else None, evaluated=0, missing=0,
+    MAP_STATS.update(reads=0, segments=0, unmapped=0)
+    TRUTH.update(seqs=accuracy.read_truth(opt.truth) if getattr(opt, "truth", "") else None,
+                 ref=accuracy.read_reference(opt.truth_ref) if getattr(opt, "truth_ref", "") else None,
+                 evaluated=0, missing=0,
                  match=0, length=0, bases=np.zeros(accuracy.Q_LEVELS, np.int64),
                  errors=np.zeros(accuracy.Q_LEVELS, np.int64))
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
@@ -292,6 +357,15 @@ def main(opt=None):
     if getattr(opt, "assembly", "cpu") == "gpu":
         logger.info("-assembly gpu: %d of %d reads were assembled on the host (fallback: a chunk of 200 or more "
                     "bases, or text outside ACGTM)" % (ASSEMBLY_STATS["fallback"], ASSEMBLY_STATS["reads"]))
+    if TRUTH["ref"] is not None:
+        if getattr(opt, "fastq", False):
+            with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:
+                f.writelines(accuracy.calibration_lines(TRUTH["bases"], TRUTH["errors"]))
+        logger.info("-truth_ref: %d reads evaluated, %d reads unmapped, %d segments mapped, %d unmapped; pooled "
+                    "identity %.6f (%d matches over %d alignment columns)"
+                    % (TRUTH["evaluated"], TRUTH["missing"], MAP_STATS["segments"] - MAP_STATS["unmapped"],
+                       MAP_STATS["unmapped"], TRUTH["match"] / TRUTH["length"] if TRUTH["length"] else 0.0,
+                       TRUTH["match"], TRUTH["length"]))
     if TRUTH["seqs"] is not None:
         if getattr(opt, "fastq", False):
             with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:
@@ -358,7 +432,7 @@ def _translate_group(opt, translator, group, raw=False):
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    if TRUTH["seqs"] is None:
+    if TRUTH["seqs"] is None and TRUTH["ref"] is None:
         for g, o, seq, w, mw, ps in zip(group, outs, seqs, weights, mods, positions):
             write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
                          **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}))
@@ -368,7 +442,8 @@ def _translate_group(opt, translator, group, raw=False):
     for g, o, seq, w, mw, ps, a in zip(group, outs, seqs, weights, mods, positions, acc):
         if write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
                         **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}),
-                        **(dict(accuracy_line=a[0]) if a else {})):
+                        **(dict(accuracy_line=a[0]) if a else {}),
+                        **(dict(paf_lines=a[4]) if a and len(a) > 4 else {})):
             _account(a)
     return len(group)
 

@@ -43,7 +43,19 @@
 // cell, into LDS; thread 0 walks the path inside it (writing op[] and counting), and the window moves.  A border
 // ends it: the rest of a column 0 is insertions (written by all threads), the rest of row 0 deletions.
 //
-// LDS: 2 x 8208 (sequences) + 16416 (strip row) + 16384 (block rows) + 1024 (window) + 8 = 50,248 bytes static.
+// The fit form (nd_align_fit, FIT = true below; the rule is in nanodecoder_amd/accuracy.py, fit_host): the truth
+// of pair p is the window ref[hit[p][1] .. hit[p][2]) of one shared reference and its ends are free: D[0][j] = 0
+// (the strip row starts at 0), the alignment ends in the smallest j* with D[n][j*] minimal and its path runs from
+// (n, j*) until i == 0, nothing consumed on row 0.  Row n lies in the last strip, whose bottom row no strip reads:
+// there the thread that owns row n, and no other, writes into the strip row, and what it writes is row n, block by
+// block (the loop is instantiated for each of the four places row n can have among its rows); after the DP all
+// threads reduce (D[n][j], j) over j = 0..m (D[n][0] = n, the padded columns j > m left out) to the smallest key.  A pair whose status has bit 0 set on entry (unmapped) is skipped.  The global
+// form's instantiation holds none of this.
+//
+// LDS: 2 x 8208 (sequences) + 16416 (strip row) + 16384 (block rows) + 1024 (window) + 8 = 50,248 bytes static
+// (the fit form: + 4).
+#include <type_traits>
+
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -62,16 +74,40 @@ __host__ __device__ __forceinline__ long long aln_pair_bytes(int n, int m) {
   return (b + 3) & ~3ll;
 }
 
+// pair p's sides.  Global form: tb = truth_off.  Fit form: tb = hit [P, 4], the truth the window hit[p][1] ..
+// hit[p][2] of a reference of ref_len bytes.  Returns 0, or the fit form's 1 = skipped (status bit 0 on entry),
+// 4 = the window is not inside [0, ref_len]
+template <bool FIT>
+__device__ __forceinline__ int aln_dims(const int* __restrict__ call_off, const int* __restrict__ tb,
+                                        const int* __restrict__ status, int ref_len, int p, int& n, int& ob, int& m) {
+  n = call_off[p + 1] - call_off[p];
+  if constexpr (FIT) {
+    ob = tb[4 * (size_t)p + 1];
+    m = tb[4 * (size_t)p + 2] - ob;
+    if (status[p] & 1) return 1;
+    if (ob < 0 || m < 0 || (long long)ob + m > ref_len) return 4;
+  } else {
+    ob = tb[p];
+    m = tb[p + 1] - ob;
+  }
+  return 0;
+}
+
 // off[p] = the direction bytes of the pairs before p, off[P] their total: a blocked scan with a carry
+template <bool FIT>
 __global__ void __launch_bounds__(ALN_THREADS)
 align_offsets_kernel(const int* __restrict__ call_off, const int* __restrict__ truth_off, int P,
-                     long long* __restrict__ off) {
+                     long long* __restrict__ off, const int* __restrict__ status, int ref_len) {
   __shared__ long long sm[ALN_THREADS];
   const int tid = threadIdx.x;
   long long carry = 0;
   for (int base = 0; base < P; base += ALN_THREADS) {
     const int p = base + tid;
-    const long long mine = p < P ? aln_pair_bytes(call_off[p + 1] - call_off[p], truth_off[p + 1] - truth_off[p]) : 0;
+    long long mine = 0;
+    if (p < P) {
+      int n, ob, m;
+      if (aln_dims<FIT>(call_off, truth_off, status, ref_len, p, n, ob, m) == 0) mine = aln_pair_bytes(n, m);
+    }
     sm[tid] = mine;
     __syncthreads();
     for (int o = 1; o < ALN_THREADS; o <<= 1) {
@@ -100,26 +136,32 @@ __device__ __forceinline__ unsigned aln_dir_word(const unsigned* __restrict__ fu
   return (unsigned)(v >> (bit0 & 7)) & ((1u << (2 * r)) - 1u);
 }
 
+template <bool FIT>
 __global__ void __launch_bounds__(ALN_THREADS)
 align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ call_off,
              const unsigned char* __restrict__ truth, const int* __restrict__ truth_off,
              const long long* __restrict__ off, long long capacity, unsigned char* __restrict__ dirs,
-             int* __restrict__ counts, unsigned char* __restrict__ ops, int* __restrict__ status) {
+             int* __restrict__ counts, unsigned char* __restrict__ ops, int* __restrict__ status,
+             int* __restrict__ span, int ref_len) {
   __shared__ __align__(16) unsigned char sa[ALIGN_MAX_LEN + 16], sb[ALIGN_MAX_LEN + 16];
   __shared__ __align__(16) unsigned short srow[ALIGN_MAX_LEN + 16];  // srow[j - 1] = D[the strip's top row][j]
   __shared__ __align__(16) unsigned short sx[2][ALN_THREADS][16];    // [step parity][thread]: its block's bottom row
   __shared__ unsigned swin[ALN_WIN_ROWS][ALN_WIN_BLKS];
   __shared__ int s_ij[2];
+  __shared__ int s_end[1];  // the fit form: j*
   const int p = blockIdx.x, tid = threadIdx.x;
-  const int oa = call_off[p], n = call_off[p + 1] - oa;
-  const int ob = truth_off[p], m = truth_off[p + 1] - ob;
+  const int oa = call_off[p];
+  int n, ob, m;
+  const int dims = aln_dims<FIT>(call_off, truth_off, status, ref_len, p, n, ob, m);
   unsigned char* op = ops ? ops + oa : nullptr;
   int bad = 0;
-  if (n < 0 || m < 0 || n > ALIGN_MAX_LEN || m > ALIGN_MAX_LEN) bad = 1;
+  if (FIT && dims) bad = dims;
+  else if (n < 0 || m < 0 || n > ALIGN_MAX_LEN || m > ALIGN_MAX_LEN) bad = FIT ? 4 : 1;
   else if (off[p + 1] > capacity) bad = 2;
   if (bad) {
-    if (tid == 0) status[p] = bad;
+    if (tid == 0 && !(FIT && bad == 1)) status[p] = bad;  // a skipped pair keeps its status
     if (tid < 5) counts[(size_t)p * 5 + tid] = -1;
+    if (FIT && tid < 2) span[(size_t)p * 2 + tid] = -1;
     if (op)
       for (int x = tid; x < n; x += ALN_THREADS) op[x] = 0;
     return;
@@ -134,11 +176,18 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
     for (int x = tid; x < nstrips * ALN_STRIP; x += ALN_THREADS) sa[x] = x < n ? call[oa + x] : 0;
     for (int x = tid; x < mb * 16; x += ALN_THREADS) {
       sb[x] = x < m ? truth[ob + x] : 0;
-      srow[x] = (unsigned short)(x + 1);
+      srow[x] = FIT ? (unsigned short)0 : (unsigned short)(x + 1);
     }
     __syncthreads();
     const int period = max(mb, ALN_THREADS);           // steps between two strips' block 0 on one thread
     const int steps = nstrips * period + ALN_THREADS;  // thread 255's last block is step (nstrips-1) period + mb + 254
+    // the fit form: row n lies in the last strip, whose bottom row nobody reads; there the thread that owns row n
+    // writes that row into the strip row and no other thread does (thread 0 has read a block of it at least one
+    // step before the owner writes there).  Which of the owner's four rows it is, is the same for the whole pair:
+    // the loop is instantiated per value (own_k below), so that the row is picked at compile time
+    const bool own = FIT && tid == ((n - 1) % ALN_STRIP) / ALN_ROWS;
+    auto dp = [&](auto own_k_c) {
+    constexpr int OWN_K = decltype(own_k_c)::value;
     int left[ALN_ROWS], corner = 0;
     int s = 0, cb = -tid;  // this thread's strip and block at the current step (cb < 0: not started)
     for (int g = 0; g < steps; ++g) {
@@ -165,6 +214,8 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
         const unsigned bw[4] = {bq.x, bq.y, bq.z, bq.w};
         const unsigned aw = *reinterpret_cast<const unsigned*>(&sa[i0 - 1]);
         unsigned words[ALN_ROWS];
+        const bool last_strip = FIT && s == nstrips - 1;
+        unsigned rown[8];  // the fit form: row OWN_K of this block, packed like the bottom row
 #pragma unroll
         for (int k = 0; k < ALN_ROWS; ++k) {
           const int ai = (int)((aw >> (8 * k)) & 0xFFu);
@@ -185,6 +236,12 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
           }
           left[k] = lft;
           words[k] = word;
+          if constexpr (FIT) {
+            if (k == OWN_K && OWN_K < ALN_ROWS - 1) {  // (folds once k is unrolled) for the owner, D[n][16 cb + 1 ..]
+#pragma unroll
+              for (int c = 0; c < 8; ++c) rown[c] = (unsigned)top[2 * c + 1] | ((unsigned)top[2 * c + 2] << 16);
+            }
+          }
         }
         uint4 o0, o1;
         o0.x = (unsigned)top[1] | ((unsigned)top[2] << 16);
@@ -195,7 +252,23 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
         o1.y = (unsigned)top[11] | ((unsigned)top[12] << 16);
         o1.z = (unsigned)top[13] | ((unsigned)top[14] << 16);
         o1.w = (unsigned)top[15] | ((unsigned)top[16] << 16);
-        uint4* dst = reinterpret_cast<uint4*>(tid == ALN_THREADS - 1 ? &srow[16 * cb] : &sx[g & 1][tid][0]);
+        if constexpr (FIT && OWN_K < ALN_ROWS - 1) {
+          // the owner stores row n in place of its bottom row: the threads below it hold rows past n, whose values
+          // reach no output (their directions are not stored, and the strip row takes nothing from them here)
+          const bool mine = own && last_strip;
+          o0.x = mine ? rown[0] : o0.x;
+          o0.y = mine ? rown[1] : o0.y;
+          o0.z = mine ? rown[2] : o0.z;
+          o0.w = mine ? rown[3] : o0.w;
+          o1.x = mine ? rown[4] : o1.x;
+          o1.y = mine ? rown[5] : o1.y;
+          o1.z = mine ? rown[6] : o1.z;
+          o1.w = mine ? rown[7] : o1.w;
+        }
+        // one store, its destination selected: a second store under a condition of its own made hipcc keep 279
+        // registers live here instead of 97
+        uint4* dst = reinterpret_cast<uint4*>((last_strip ? own : tid == ALN_THREADS - 1) ? &srow[16 * cb]
+                                                                                         : &sx[g & 1][tid][0]);
         dst[0] = o0;
         dst[1] = o1;
         if (cb < W) {
@@ -218,11 +291,38 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
       }
       __syncthreads();
     }
+    };
+    if constexpr (FIT) {
+      switch ((n - 1) % ALN_ROWS) {
+        case 0: dp(std::integral_constant<int, 0>{}); break;
+        case 1: dp(std::integral_constant<int, 1>{}); break;
+        case 2: dp(std::integral_constant<int, 2>{}); break;
+        default: dp(std::integral_constant<int, ALN_ROWS - 1>{}); break;
+      }
+    } else {
+      dp(std::integral_constant<int, ALN_ROWS - 1>{});
+    }
     __threadfence();  // the directions, before other threads of the workgroup read them back
+    if constexpr (FIT) {  // the smallest j with D[n][j] minimal: srow[j - 1] = D[n][j], D[n][0] = n; (value, j) as one key
+      unsigned best = (unsigned)n << 14;
+      for (int j = tid + 1; j <= m; j += ALN_THREADS) best = min(best, ((unsigned)srow[j - 1] << 14) | (unsigned)j);
+      unsigned* red = &swin[0][0];  // 256 words, free until the traceback
+      red[tid] = best;
+      __syncthreads();
+      for (int o = ALN_THREADS / 2; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = min(red[tid], red[tid + o]);
+        __syncthreads();
+      }
+      if (tid == 0) s_end[0] = (int)(red[0] & 0x3FFFu);
+    }
+  } else if constexpr (FIT) {
+    if (tid == 0) s_end[0] = 0;  // an empty side: j* = 0
   }
+  if constexpr (FIT) __syncthreads();
   if (tid == 0) {
     s_ij[0] = n;
-    s_ij[1] = m;
+    if constexpr (FIT) s_ij[1] = s_end[0];
+    else s_ij[1] = m;
   }
   int n_match = 0, n_sub = 0, n_ins = 0, n_del = 0;  // thread 0's
   for (;;) {
@@ -266,7 +366,12 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
     for (int x = tid; x < ri; x += ALN_THREADS) op[x] = 2;
   if (tid == 0) {
     n_ins += max(ri, 0);
-    n_del += max(rj, 0);
+    if constexpr (FIT) {  // row 0 consumes nothing: the path starts at column rj of the window
+      span[(size_t)p * 2] = ob + max(rj, 0);
+      span[(size_t)p * 2 + 1] = ob + s_end[0];
+    } else {
+      n_del += max(rj, 0);
+    }
     int* c = counts + (size_t)p * 5;
     c[0] = n_sub + n_ins + n_del;
     c[1] = n_match;
@@ -287,9 +392,28 @@ hipError_t launch_align_seqs(const unsigned char* call, const int* call_off, con
   if (P == 0) return hipSuccess;
   long long* off = static_cast<long long*>(work);
   const long long head = 8ll * (P + 1);  // the offsets; the directions follow
-  hipLaunchKernelGGL(align_offsets_kernel, dim3(1), dim3(ALN_THREADS), 0, s, call_off, truth_off, P, off);
-  hipLaunchKernelGGL(align_kernel, dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, truth, truth_off, off,
-                     align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops, status);
+  hipLaunchKernelGGL(align_offsets_kernel<false>, dim3(1), dim3(ALN_THREADS), 0, s, call_off, truth_off, P, off,
+                     (const int*)nullptr, 0);
+  hipLaunchKernelGGL(align_kernel<false>, dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, truth, truth_off, off,
+                     align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops, status,
+                     (int*)nullptr, 0);
+  return hipGetLastError();
+}
+
+hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                            int* status, void* work, hipStream_t s) {
+  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0 || !call_off ||
+      (P > 0 && (!call || !ref || !hit || !counts || !span || !status || !work)))
+    return hipErrorInvalidValue;
+  if (P == 0) return hipSuccess;
+  long long* off = static_cast<long long*>(work);
+  const long long head = 8ll * (P + 1);
+  hipLaunchKernelGGL(align_offsets_kernel<true>, dim3(1), dim3(ALN_THREADS), 0, s, call_off, hit, P, off,
+                     (const int*)status, ref_len);
+  hipLaunchKernelGGL(align_kernel<true>, dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, ref, hit, off,
+                     align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops, status,
+                     span, ref_len);
   return hipGetLastError();
 }
 

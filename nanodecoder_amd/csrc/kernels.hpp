@@ -457,6 +457,26 @@ long long align_work_bytes(int P, long long cells);
 hipError_t launch_align_seqs(const unsigned char* call, const int* call_off, const unsigned char* truth,
                              const int* truth_off, int P, long long cells, int* counts, unsigned char* ops,
                              int* status, void* work, hipStream_t s);
+// read mapping against a shared reference (locate.hip states the rule): segment p is call[call_off[p] ..
+// call_off[p+1]); the index is the reference's 15-mers as (code, pos) sorted by code then pos; hit [P, 4] =
+// {strand, w0, w1, votes}, status [P] (bit 0: unmapped), call_or the oriented bytes laid out like call
+#define MAP_K 15
+#define MAP_OCC_MAX 8
+#define MAP_SEG 4096
+#define MAP_BIN_SHIFT 9
+#define MAP_PAD 1024
+#define MAP_MIN_VOTES 8
+#define MAP_REF_MAX (1 << 23)
+hipError_t launch_locate_segs(const unsigned char* call, const int* call_off, int P, const unsigned* idx_code,
+                              const unsigned* idx_pos, int idx_len, const int* rec_off, int R, int* hit, int* status,
+                              unsigned char* call_or, hipStream_t s);
+// the fit form of the alignment (align.hip): pair p is call[call_off[p] .. call_off[p+1]) against ref[hit[p][1] ..
+// hit[p][2]) with free ends on the reference side; a pair whose status has bit 0 set on entry is skipped; span
+// [P, 2] = the aligned reference interval in ref's coordinates; status bit 1: cells understated, bit 2: a side
+// above ALIGN_MAX_LEN or a window outside [0, ref_len]
+hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                            int* status, void* work, hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

@@ -1,5 +1,5 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions, nd_align_seqs): launches on the caller's stream, with no context.
+// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions, nd_align_seqs, nd_locate_segs, nd_align_fit): launches on the caller's stream, with no context.
 // The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
@@ -443,6 +443,38 @@ int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_
   if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_seqs: d_work must be 8-byte aligned");
   return status("align_seqs", nd::launch_align_seqs(d_call, d_call_off, d_truth, d_truth_off, P, cells, d_counts,
                                                     d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_locate_segs(const uint8_t* d_call, const int32_t* d_call_off, int32_t P, const uint32_t* d_idx_code,
+                   const uint32_t* d_idx_pos, int32_t idx_len, const int32_t* d_rec_off, int32_t R, int32_t* d_hit,
+                   int32_t* d_status, uint8_t* d_call_or, void* stream) {
+  if (P < 0 || idx_len < 0 || R < 0) return fail(ND_ERR_ARG, "locate_segs: P, idx_len and R must be >= 0");
+  if (P == 0) return ND_OK;
+  if (!d_call || !d_call_off || !d_rec_off || !d_hit || !d_status || !d_call_or ||
+      (idx_len > 0 && (!d_idx_code || !d_idx_pos)))
+    return fail(ND_ERR_ARG, "locate_segs: null buffer");
+  if (d_call == d_call_or) return fail(ND_ERR_ARG, "locate_segs: d_call_or must not be d_call");
+  return status("locate_segs", nd::launch_locate_segs(d_call, d_call_off, P, d_idx_code, d_idx_pos, idx_len, d_rec_off,
+                                                      R, d_hit, d_status, d_call_or, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int64_t nd_align_fit_work_bytes(int32_t P, int64_t cells) { return nd_align_seqs_work_bytes(P, cells); }
+
+int nd_align_fit(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ref, int32_t ref_len,
+                 const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span, uint8_t* d_ops,
+                 int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0)
+    return fail(ND_ERR_ARG, "align_fit: P, cells and ref_len must be >= 0 and cells <= 2^60");
+  if (P == 0) return ND_OK;
+  const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "align_fit: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_align_fit_work_bytes asks for");
+  if (!d_call_or || !d_call_off || !d_ref || !d_hit || !d_counts || !d_span || !d_status || !d_work)
+    return fail(ND_ERR_ARG, "align_fit: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_fit: d_work must be 8-byte aligned");
+  return status("align_fit", nd::launch_align_fit(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells, d_counts,
+                                                  d_span, d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
 }
 
 int nd_phred_ratios(double* out, int32_t n) {

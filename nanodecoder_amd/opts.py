@@ -100,7 +100,16 @@ def translate_parser() -> argparse.ArgumentParser:
               "outputs are unchanged; not together with -attn_debug")
     _add(g, "truth_align", default="gpu", choices=["gpu", "cpu"],
          help="where -truth aligns: gpu = one device call per translated group on -gpu's device (align.hip; a read "
-              "above 8192 bases is aligned on the host and counted in the log), cpu = the same rule in numpy")
+              "above 8192 bases is aligned on the host and counted in the log), cpu = the same rule in numpy; with "
+              "-truth_ref: gpu = all segments of a group in one locate call and one fit call (locate.hip, align.hip)")
+    _add(g, "truth_ref", type=str, default="",
+         help="a FASTA file of a shared reference (a genome, a control sequence; at most 2^23 bases in all records): "
+              "every read is cut into segments of at most 4096 bases, each segment is located in the reference by "
+              "15-mer votes on either strand and aligned there with free ends on the reference side; a read with a "
+              "mapped segment gets a line of save_data/accuracy.tsv (truth = the aligned reference bases, counts "
+              "summed over its mapped segments) and every mapped segment a line of save_data/mapping.paf (12 PAF "
+              "columns and vt:i: = the locate votes); with -fastq, quality_calibration.tsv as with -truth, from the "
+              "mapped segments; not together with -truth or -attn_debug")
     return p
 
 
