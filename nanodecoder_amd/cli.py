@@ -136,29 +136,19 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
     lines of save_data/mapping.paf.  Returns True when everything was written."""
     try:
         name = file_src.split(".txt")[0]
-        rpos = None
-        if moves is not None and sequence is not None:
-            rpos, sequence = sequence[-1], (sequence[:-1] if weights is not None else sequence[0])
-        elif moves is not None and weights is not None:  # a second host assembly: the forms are not multiplied
-            rpos = frontend.assemble_read_p(all_predictions, moves, opt.src_seq_length, opt.src_seq_stride)[1]
+        if sequence is None:
+            c_bpread, quality, ml, rpos = frontend.assemble_read_annotated(
+                all_predictions, opt.src_seq_length, opt.src_seq_stride, weights, mods, moves)
+        else:  # as frontend.assemble_reads gives a read: the string, or a tuple with what was asked for, in order
+            rest = list(sequence[1:]) if weights is not None or moves is not None else []
+            c_bpread = sequence if not rest else sequence[0]
+            quality, ml, rpos = (rest.pop(0) if given is not None else None for given in (weights, mods, moves))
         if mods is not None:
-            c_bpread, quality, ml = sequence if sequence is not None else \
-                frontend.assemble_read_m(all_predictions, weights, mods, opt.src_seq_length, opt.src_seq_stride)
             with open(os.path.join(opt.save_data, "result", name + ".mod.fastq"), "w") as f:
                 f.write(frontend.mod_fastq_record(name, c_bpread, quality, ml))
-            if getattr(opt, "fastq", False):
-                with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
-                    f.write("@%s\n%s\n+\n%s\n" % (name, c_bpread, quality))
-        elif weights is not None:
-            c_bpread, quality = sequence if sequence is not None else \
-                frontend.assemble_read_q(all_predictions, weights, opt.src_seq_length, opt.src_seq_stride)
+        if weights is not None and (mods is None or getattr(opt, "fastq", False)):
             with open(os.path.join(opt.save_data, "result", name + ".fastq"), "w") as f:
                 f.write("@%s\n%s\n+\n%s\n" % (name, c_bpread, quality))
-        elif moves is not None and sequence is None:
-            c_bpread, rpos = frontend.assemble_read_p(all_predictions, moves, opt.src_seq_length, opt.src_seq_stride)
-        else:
-            c_bpread = sequence if sequence is not None else \
-                frontend.assemble_read(all_predictions, opt.src_seq_length, opt.src_seq_stride)
         if moves is not None:
             with open(os.path.join(opt.save_data, "result", name + ".moves"), "w") as f:
                 f.write(frontend.moves_record(name, c_bpread, rpos))

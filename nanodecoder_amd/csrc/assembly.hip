@@ -47,6 +47,10 @@
 // atomics as above), the call kernel gives a column of n >= 1 votes P div n (0 with no vote), and a fifth
 // launch, one workgroup per read, takes the running maximum along the read in blocks of 256 columns with a
 // carry.  nd_token_positions (one launch) turns a call's attention rows into the chunk-relative positions.
+//
+// The four forms share one launcher: launch_assemble_reads reads the form off the optional pointer pairs of its
+// AsmArgs, lays the work buffer out plane by plane (the 64-bit sums of the form, then pos, rd and the counts),
+// clears the counts and the sums with one memset each, and picks the vote / call instantiations of the form.
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -301,70 +305,66 @@ asm_pos_scan_kernel(const int* __restrict__ chunk_off, const int* __restrict__ r
   }
 }
 
+// the 64-bit planes of a form: wsum's five, msum's one, psum's one
+static size_t asm_planes64(bool qual, bool mod, bool pos) { return (qual ? 5 : 0) + (mod ? 1 : 0) + (pos ? 1 : 0); }
+
 size_t assemble_work_bytes(int C, long long total, bool qual, bool mod, bool pos) {
-  return (size_t)2 * C * sizeof(int) + (size_t)5 * total * sizeof(int) +
-         (qual ? (size_t)5 * total * sizeof(unsigned long long) : 0) +
-         (mod ? (size_t)total * sizeof(unsigned long long) : 0) +
-         (pos ? (size_t)total * sizeof(unsigned long long) : 0);
+  return asm_planes64(qual, mod, pos) * (size_t)total * sizeof(unsigned long long) + (size_t)2 * C * sizeof(int) +
+         (size_t)5 * total * sizeof(int);
 }
 
-hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
-                                 const int* read_off, int R, int C, int total, unsigned char* seq,
-                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
-                                 const unsigned short* mw, unsigned char* ml, const unsigned* bp, unsigned* rpos) {
-  const bool q = qual != nullptr;  // with qualities: qw and qual both given
-  const bool m = ml != nullptr;    // with modification values (only beside qualities): mw and ml both given
-  const bool p = rpos != nullptr;  // with signal positions (the plain form only): bp and rpos both given
-  if (R < 0 || C < 0 || total < 0 || !chunk_off || !read_off || (R > 0 && (!seq_len || !status)) ||
-      (C > 0 && !work) || (total > 0 && (!bases || !seq)) || (qw != nullptr) != q || (mw != nullptr) != m ||
-      (m && !q) || (bp != nullptr) != p || (p && q))
+hipError_t launch_assemble_reads(const AsmArgs& a, hipStream_t s) {
+  const bool q = a.qual != nullptr, m = a.ml != nullptr, p = a.rpos != nullptr;  // the form: which pairs are given
+  const int R = a.R, C = a.C, total = a.total;
+  if (R < 0 || C < 0 || total < 0 || !a.chunk_off || !a.read_off || (R > 0 && (!a.seq_len || !a.status)) ||
+      (C > 0 && !a.work) || (total > 0 && (!a.bases || !a.seq)) || (a.qw != nullptr) != q ||
+      (a.mw != nullptr) != m || (m && !q) || (a.bp != nullptr) != p || (p && q))
     return hipErrorInvalidValue;
   if (R == 0) return hipSuccess;
-  hipError_t e = hipMemsetAsync(status, 0, (size_t)R * sizeof(int), s);
+  hipError_t e = hipMemsetAsync(a.status, 0, (size_t)R * sizeof(int), s);
   if (e != hipSuccess) return e;
-  if (C == 0) return hipMemsetAsync(seq_len, 0, (size_t)R * sizeof(int), s);  // no chunks: every read is ""
-  // the 64-bit weight sums first, so they are 8-byte aligned whatever C is: wsum's five planes, then msum's one
-  unsigned long long* wsum = static_cast<unsigned long long*>(work);
-  unsigned long long* msum = wsum + (size_t)5 * total;
-  unsigned long long* psum = static_cast<unsigned long long*>(work);  // POS: the one 64-bit plane, first as well
-  int* pos = q   ? reinterpret_cast<int*>(wsum + (size_t)(m ? 6 : 5) * total)
-             : p ? reinterpret_cast<int*>(psum + (size_t)total)
-                 : static_cast<int*>(work);
+  if (C == 0) return hipMemsetAsync(a.seq_len, 0, (size_t)R * sizeof(int), s);  // no chunks: every read is ""
+  // work, plane by plane: the 64-bit sums first, so they are 8-byte aligned whatever C is (wsum[5][total],
+  // msum[total], psum[total], each only in its form), then pos[C], rd[C] and count[5][total]
+  unsigned long long* const sums = static_cast<unsigned long long*>(a.work);
+  unsigned long long* next = sums;
+  auto plane = [&](bool on, int n) {
+    unsigned long long* at = on ? next : nullptr;
+    if (on) next += (size_t)n * total;
+    return at;
+  };
+  unsigned long long* wsum = plane(q, 5);
+  unsigned long long* msum = plane(m, 1);
+  unsigned long long* psum = plane(p, 1);
+  int* pos = reinterpret_cast<int*>(next);
   int* rd = pos + C;
   int* count = rd + C;
   if (total > 0) {
     e = hipMemsetAsync(count, 0, (size_t)5 * total * sizeof(int), s);
-    if (e == hipSuccess && q)
-      e = hipMemsetAsync(wsum, 0, (size_t)(m ? 6 : 5) * total * sizeof(unsigned long long), s);
-    if (e == hipSuccess && p) e = hipMemsetAsync(psum, 0, (size_t)total * sizeof(unsigned long long), s);
+    if (e == hipSuccess && next != sums) e = hipMemsetAsync(sums, 0, (size_t)(next - sums) * sizeof(*sums), s);
     if (e != hipSuccess) return e;
   }
   const int per = ASM_THREADS / 64;
   const dim3 grid((C + per - 1) / per), block(ASM_THREADS);
-  hipLaunchKernelGGL(asm_overlap_kernel, dim3(C), block, 0, s, bases, chunk_off, read_off, R, pos, rd, status);
-  hipLaunchKernelGGL(asm_place_kernel, dim3(R), block, 0, s, chunk_off, read_off, pos, status, seq_len);
-  if (total > 0 && m) {
-    hipLaunchKernelGGL((asm_vote_kernel<true, true>), grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd,
-                       status, C, total, count, wsum, msum, bp, psum);
-    hipLaunchKernelGGL((asm_call_kernel<true, true>), grid, block, 0, s, chunk_off, read_off, rd, seq_len, count,
-                       wsum, msum, C, total, seq, qual, ml, psum, rpos);
-  } else if (total > 0 && q) {
-    hipLaunchKernelGGL(asm_vote_kernel<true>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
-                       C, total, count, wsum, msum, bp, psum);
-    hipLaunchKernelGGL(asm_call_kernel<true>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
-                       C, total, seq, qual, ml, psum, rpos);
-  } else if (total > 0 && p) {
-    hipLaunchKernelGGL((asm_vote_kernel<false, false, true>), grid, block, 0, s, bases, qw, mw, chunk_off, read_off,
-                       pos, rd, status, C, total, count, wsum, msum, bp, psum);
-    hipLaunchKernelGGL((asm_call_kernel<false, false, true>), grid, block, 0, s, chunk_off, read_off, rd, seq_len,
-                       count, wsum, msum, C, total, seq, qual, ml, psum, rpos);
-    hipLaunchKernelGGL(asm_pos_scan_kernel, dim3(R), block, 0, s, chunk_off, read_off, seq_len, total, rpos);
-  } else if (total > 0) {
-    hipLaunchKernelGGL(asm_vote_kernel<false>, grid, block, 0, s, bases, qw, mw, chunk_off, read_off, pos, rd, status,
-                       C, total, count, wsum, msum, bp, psum);
-    hipLaunchKernelGGL(asm_call_kernel<false>, grid, block, 0, s, chunk_off, read_off, rd, seq_len, count, wsum, msum,
-                       C, total, seq, qual, ml, psum, rpos);
-  }
+  hipLaunchKernelGGL(asm_overlap_kernel, dim3(C), block, 0, s, a.bases, a.chunk_off, a.read_off, R, pos, rd, a.status);
+  hipLaunchKernelGGL(asm_place_kernel, dim3(R), block, 0, s, a.chunk_off, a.read_off, pos, a.status, a.seq_len);
+  auto go = [&](auto vote, auto call) {
+    hipLaunchKernelGGL(vote, grid, block, 0, s, a.bases, a.qw, a.mw, a.chunk_off, a.read_off, pos, rd, a.status, C,
+                       total, count, wsum, msum, a.bp, psum);
+    hipLaunchKernelGGL(call, grid, block, 0, s, a.chunk_off, a.read_off, rd, a.seq_len, count, wsum, msum, C, total,
+                       a.seq, a.qual, a.ml, psum, a.rpos);
+  };
+  if (total == 0) return hipGetLastError();  // only empty chunks: place has written every seq_len
+  if (m)
+    go(asm_vote_kernel<true, true>, asm_call_kernel<true, true>);
+  else if (q)
+    go(asm_vote_kernel<true>, asm_call_kernel<true>);
+  else if (p)
+    go(asm_vote_kernel<false, false, true>, asm_call_kernel<false, false, true>);
+  else
+    go(asm_vote_kernel<false>, asm_call_kernel<false>);
+  if (p)
+    hipLaunchKernelGGL(asm_pos_scan_kernel, dim3(R), block, 0, s, a.chunk_off, a.read_off, a.seq_len, total, a.rpos);
   return hipGetLastError();
 }
 

@@ -410,24 +410,28 @@ hipError_t launch_read_normalize(const double* raw, const long long* off, int R,
 hipError_t launch_read_window(const float* sig, const long long* off, const int* rd, const int* start,
                               const int* len, int C, int T, float* out, hipStream_t s);
 // read assembly (assembly.hip): the overlap consensus of utils/labelop.py:310-352 for R reads whose chunk
-// strings (ASCII, spaces removed) are concatenated in bases[total]: chunk c = chunk_off[c] .. chunk_off[c+1],
-// read r = chunks read_off[r] .. read_off[r+1].  Read r's bases go to seq at chunk_off[read_off[r]], their
-// count to seq_len[r]; status[r] != 0 (bit 0: a chunk of 200 or more chars, bit 1: a char outside ACGTM) means
-// the read was not assembled (seq_len[r] = -1).  With qw (each base's uint16 weight) and qual, both or neither,
-// the columns' qualities Q in 0..40 go to qual, laid out like seq.  work holds assemble_work_bytes(C, total,
-// qual != nullptr, ml != nullptr) bytes.  With mw (each base's uint16 modification weight) and ml too, both or
-// neither and only beside qw / qual, a column called C or M gets ML = min(255, (256 W) div (65535 n_cm)) in ml
-// (laid out like seq; W the mw sum of its C and M votes, n_cm their number), every other byte of ml 0.  With bp
-// (each base's absolute signal position, uint32) and rpos, both or neither and only without qw / qual, a column
-// of n >= 1 votes gets the 64-bit sum of its votes' positions div n (0 with no vote) and rpos (laid out like seq)
-// the running maximum of the column positions along each read, 0 past its length; work then holds
-// assemble_work_bytes(C, total, false, false, true)
-size_t assemble_work_bytes(int C, long long total, bool qual = false, bool mod = false, bool pos = false);
-hipError_t launch_assemble_reads(const unsigned char* bases, const unsigned short* qw, const int* chunk_off,
-                                 const int* read_off, int R, int C, int total, unsigned char* seq,
-                                 unsigned char* qual, int* seq_len, int* status, void* work, hipStream_t s,
-                                 const unsigned short* mw = nullptr, unsigned char* ml = nullptr,
-                                 const unsigned* bp = nullptr, unsigned* rpos = nullptr);
+// strings (ASCII, spaces removed) are concatenated in bases[total].  The optional pairs are given both or
+// neither; mw / ml only beside qw / qual, bp / rpos only without them.
+struct AsmArgs {
+  const unsigned char* bases = nullptr;
+  const int* chunk_off = nullptr;  // chunk c = bases[chunk_off[c] .. chunk_off[c+1])
+  const int* read_off = nullptr;   // read r = chunks read_off[r] .. read_off[r+1]
+  int R = 0, C = 0, total = 0;
+  unsigned char* seq = nullptr;  // read r's bases, at chunk_off[read_off[r]]
+  int* seq_len = nullptr;        // their count; -1 when status[r] != 0: the read was not assembled
+  int* status = nullptr;         // bit 0: a chunk of 200 or more chars, bit 1: a char outside ACGTM
+  void* work = nullptr;  // assemble_work_bytes(C, total, qual, ml, rpos given) bytes, 8-byte aligned
+  const unsigned short* qw = nullptr;  // each base's uint16 weight
+  unsigned char* qual = nullptr;       // the columns' qualities Q in 0..40, laid out like seq
+  const unsigned short* mw = nullptr;  // each base's uint16 modification weight
+  unsigned char* ml = nullptr;  // min(255, (256 W) div (65535 n_cm)) of a column called C or M (W the mw sum of
+                                // its C and M votes, n_cm their number), every other byte 0; laid out like seq
+  const unsigned* bp = nullptr;  // each base's absolute signal position
+  unsigned* rpos = nullptr;  // the running maximum along each read of the column positions (the 64-bit sum of a
+                             // column's n >= 1 votes' positions div n, 0 with no vote), 0 past the read's length
+};
+size_t assemble_work_bytes(int C, long long total, bool qual, bool mod, bool pos);
+hipError_t launch_assemble_reads(const AsmArgs& a, hipStream_t s);
 // the column quality's table, the doubles 10.0 ** (k / 10.0) for k < PHRED_LEVELS
 #define PHRED_LEVELS 41
 const double* phred_ratios();

@@ -276,53 +276,55 @@ int nd_window_reads(const float* d_sig, const int64_t* d_offsets, const int32_t*
                                                        d_signal, (hipStream_t)stream));
 }
 
+// The four forms of read assembly: ``name`` the entry without its nd_ prefix, q / m / p the form (which optional
+// pairs of ``a`` the entry has); a.total is set here, from total_bases once it is known to fit.
+static int assemble_entry(const char* name, bool q, bool m, bool p, nd::AsmArgs a, int64_t total_bases,
+                          int64_t work_bytes, void* stream) {
+  const std::string n(name);
+  if (a.R < 0 || a.C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
+    return fail(ND_ERR_ARG, n + ": R, C and total_bases must be >= 0 and total_bases < 2^31");
+  const int64_t need = (int64_t)nd::assemble_work_bytes(a.C, total_bases, q, m, p);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, n + ": work_bytes " + std::to_string(work_bytes) + " below the " + std::to_string(need) +
+                                " nd_" + n + "_work_bytes asks for");
+  if (!a.chunk_off || !a.read_off || (a.R > 0 && (!a.seq_len || !a.status)) || (need > 0 && !a.work) ||
+      (total_bases > 0 && (!a.bases || !a.seq || (q && (!a.qw || !a.qual)) || (m && (!a.mw || !a.ml)) ||
+                           (p && (!a.bp || !a.rpos)))))
+    return fail(ND_ERR_ARG, n + ": null buffer");
+  if (a.R == 0) return ND_OK;
+  a.total = (int)total_bases;
+  if (total_bases == 0) {  // no base to weigh or to place: the plain form's paths (no chunks, or only empty ones)
+    a.qw = a.mw = nullptr;
+    a.qual = a.ml = nullptr;
+    a.bp = nullptr;
+    a.rpos = nullptr;
+  }
+  return status(name, nd::launch_assemble_reads(a, (hipStream_t)stream), ND_ERR_HIP);
+}
+
 int64_t nd_assemble_reads_work_bytes(int32_t C, int64_t total_bases) {
-  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases) : -1;
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, false, false, false) : -1;
 }
 
 int nd_assemble_reads(const uint8_t* d_bases, const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R,
                       int32_t C, int64_t total_bases, uint8_t* d_seq, int32_t* d_seq_len, int32_t* d_status,
                       void* d_work, int64_t work_bytes, void* stream) {
-  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
-    return fail(ND_ERR_ARG, "assemble_reads: R, C and total_bases must be >= 0 and total_bases < 2^31");
-  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "assemble_reads: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_assemble_reads_work_bytes asks for");
-  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
-      (total_bases > 0 && (!d_bases || !d_seq)))
-    return fail(ND_ERR_ARG, "assemble_reads: null buffer");
-  if (R == 0) return ND_OK;
-  return status("assemble_reads",
-                nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
-                                          nullptr, d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+  nd::AsmArgs a{.bases = d_bases, .chunk_off = d_chunk_off, .read_off = d_read_off, .R = R, .C = C, .seq = d_seq,
+                .seq_len = d_seq_len, .status = d_status, .work = d_work};
+  return assemble_entry("assemble_reads", false, false, false, a, total_bases, work_bytes, stream);
 }
 
 int64_t nd_assemble_reads_q_work_bytes(int32_t C, int64_t total_bases) {
-  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true) : -1;
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true, false, false) : -1;
 }
 
 int nd_assemble_reads_q(const uint8_t* d_bases, const uint16_t* d_qw, const int32_t* d_chunk_off,
                         const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
                         uint8_t* d_qual, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
                         void* stream) {
-  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
-    return fail(ND_ERR_ARG, "assemble_reads_q: R, C and total_bases must be >= 0 and total_bases < 2^31");
-  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, true);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "assemble_reads_q: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_assemble_reads_q_work_bytes asks for");
-  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
-      (total_bases > 0 && (!d_bases || !d_qw || !d_seq || !d_qual)))
-    return fail(ND_ERR_ARG, "assemble_reads_q: null buffer");
-  if (R == 0) return ND_OK;
-  if (total_bases == 0)  // nothing to weigh: the plain call's paths (no chunks, or only empty ones)
-    return status("assemble_reads_q",
-                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
-                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
-  return status("assemble_reads_q",
-                nd::launch_assemble_reads(d_bases, d_qw, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
-                                          d_qual, d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+  nd::AsmArgs a{.bases = d_bases, .chunk_off = d_chunk_off, .read_off = d_read_off, .R = R, .C = C, .seq = d_seq,
+                .seq_len = d_seq_len, .status = d_status, .work = d_work, .qw = d_qw, .qual = d_qual};
+  return assemble_entry("assemble_reads_q", true, false, false, a, total_bases, work_bytes, stream);
 }
 
 int nd_token_weights(const int32_t* d_tokens, const float* d_logp, const float* d_tok_logp, int32_t B, int32_t S,
@@ -348,31 +350,17 @@ int nd_token_mod_weights(const int32_t* d_tokens, const float* d_logp, int32_t B
 }
 
 int64_t nd_assemble_reads_m_work_bytes(int32_t C, int64_t total_bases) {
-  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true, true) : -1;
+  return C >= 0 && total_bases >= 0 ? (int64_t)nd::assemble_work_bytes(C, total_bases, true, true, false) : -1;
 }
 
 int nd_assemble_reads_m(const uint8_t* d_bases, const uint16_t* d_qw, const uint16_t* d_mw,
                         const int32_t* d_chunk_off, const int32_t* d_read_off, int32_t R, int32_t C,
                         int64_t total_bases, uint8_t* d_seq, uint8_t* d_qual, uint8_t* d_ml, int32_t* d_seq_len,
                         int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
-  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
-    return fail(ND_ERR_ARG, "assemble_reads_m: R, C and total_bases must be >= 0 and total_bases < 2^31");
-  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, true, true);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "assemble_reads_m: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_assemble_reads_m_work_bytes asks for");
-  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
-      (total_bases > 0 && (!d_bases || !d_qw || !d_mw || !d_seq || !d_qual || !d_ml)))
-    return fail(ND_ERR_ARG, "assemble_reads_m: null buffer");
-  if (R == 0) return ND_OK;
-  if (total_bases == 0)  // nothing to weigh: the plain call's paths (no chunks, or only empty ones)
-    return status("assemble_reads_m",
-                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
-                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
-  return status("assemble_reads_m",
-                nd::launch_assemble_reads(d_bases, d_qw, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
-                                          d_qual, d_seq_len, d_status, d_work, (hipStream_t)stream, d_mw, d_ml),
-                ND_ERR_HIP);
+  nd::AsmArgs a{.bases = d_bases, .chunk_off = d_chunk_off, .read_off = d_read_off, .R = R, .C = C, .seq = d_seq,
+                .seq_len = d_seq_len, .status = d_status, .work = d_work, .qw = d_qw, .qual = d_qual,
+                .mw = d_mw, .ml = d_ml};
+  return assemble_entry("assemble_reads_m", true, true, false, a, total_bases, work_bytes, stream);
 }
 
 int nd_token_positions(const float* d_attn, int64_t ld_chunk, const int32_t* d_span, int32_t B, int32_t S, int32_t T,
@@ -404,24 +392,9 @@ int nd_assemble_reads_p(const uint8_t* d_bases, const uint32_t* d_bp, const int3
                         const int32_t* d_read_off, int32_t R, int32_t C, int64_t total_bases, uint8_t* d_seq,
                         uint32_t* d_rpos, int32_t* d_seq_len, int32_t* d_status, void* d_work, int64_t work_bytes,
                         void* stream) {
-  if (R < 0 || C < 0 || total_bases < 0 || total_bases >= (int64_t)1 << 31)
-    return fail(ND_ERR_ARG, "assemble_reads_p: R, C and total_bases must be >= 0 and total_bases < 2^31");
-  const int64_t need = (int64_t)nd::assemble_work_bytes(C, total_bases, false, false, true);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "assemble_reads_p: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_assemble_reads_p_work_bytes asks for");
-  if (!d_chunk_off || !d_read_off || (R > 0 && (!d_seq_len || !d_status)) || (need > 0 && !d_work) ||
-      (total_bases > 0 && (!d_bases || !d_bp || !d_seq || !d_rpos)))
-    return fail(ND_ERR_ARG, "assemble_reads_p: null buffer");
-  if (R == 0) return ND_OK;
-  if (total_bases == 0)  // no base has a position: the plain call's paths (no chunks, or only empty ones)
-    return status("assemble_reads_p",
-                  nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, 0, d_seq, nullptr,
-                                            d_seq_len, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
-  return status("assemble_reads_p",
-                nd::launch_assemble_reads(d_bases, nullptr, d_chunk_off, d_read_off, R, C, (int)total_bases, d_seq,
-                                          nullptr, d_seq_len, d_status, d_work, (hipStream_t)stream, nullptr, nullptr,
-                                          d_bp, d_rpos), ND_ERR_HIP);
+  nd::AsmArgs a{.bases = d_bases, .chunk_off = d_chunk_off, .read_off = d_read_off, .R = R, .C = C, .seq = d_seq,
+                .seq_len = d_seq_len, .status = d_status, .work = d_work, .bp = d_bp, .rpos = d_rpos};
+  return assemble_entry("assemble_reads_p", false, false, true, a, total_bases, work_bytes, stream);
 }
 
 int64_t nd_align_seqs_work_bytes(int32_t P, int64_t cells) {

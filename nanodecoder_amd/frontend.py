@@ -10,6 +10,7 @@ is skipped.
 """
 from __future__ import annotations
 
+import collections
 import difflib
 import math
 from typing import List
@@ -248,72 +249,6 @@ def quality_string(q) -> str:
     return (np.asarray(q, np.uint8) + np.uint8(33)).tobytes().decode("ascii")
 
 
-def _valid_weights(bpreads, weights):
-    """The weights of simple_assembly's ``valid`` chunks, one int64 array per chunk."""
-    if len(weights) != len(bpreads):
-        raise ValueError("one weight array per chunk")
-    return [np.asarray(w, np.int64).reshape(-1) for x, w in zip(bpreads, weights) if x[0] != ""]
-
-
-def _add_count_q(consensus, wsum, start, segment, w):
-    """_add_count, each vote's weight added to ``wsum`` beside its count."""
-    if len(w) != len(segment):
-        raise ValueError("a chunk of %d bases with %d weights" % (len(segment), len(w)))
-    if start < 0:
-        segment, w = segment[-start:], w[-start:]
-        start = 0
-    for i, base in enumerate(segment):
-        k = BASE_DICT[base.upper()]
-        consensus[k][start + i] += 1
-        wsum[k][start + i] += w[i]
-
-
-def simple_assembly_q(bpreads, weights):
-    """simple_assembly with flag_intersection, line for line, with the weight sums [5, length] (int64) of the
-    votes beside the counts: (consensus, wsum)."""
-    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
-    vw = _valid_weights(bpreads, weights)
-    consensus = np.zeros([len(BASE_KEYS), 1000])
-    wsum = np.zeros([len(BASE_KEYS), 1000], np.int64)
-    pos = 0
-    length = 0
-    census_len = 1000
-    for indx, bpread in enumerate(valid):
-        if indx == 0:
-            _add_count_q(consensus, wsum, 0, bpread, vw[0])
-            continue
-        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
-        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
-        disp = match_block[0] - match_block[1]
-        if disp + pos + len(valid[indx]) > census_len:
-            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
-            wsum = np.pad(wsum, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
-            census_len += 1000
-        _add_count_q(consensus, wsum, pos + disp, valid[indx], vw[indx])
-        pos += disp
-        length = max(length, pos + len(valid[indx]))
-    return consensus[:, :length], wsum[:, :length]
-
-
-def assemble_read_q(all_predictions, weights, src_seq_length: int, src_seq_stride: int):
-    """assemble_read with per-base qualities: (sequence, quality string).  ``weights``: per chunk, the uint16
-    weight of every char of its x[0] with the spaces removed.  The sequence is assemble_read's, and what
-    assemble_read raises is raised here."""
-    if src_seq_stride < src_seq_length:
-        consensus, wsum = simple_assembly_q(all_predictions, weights)
-        win = np.argmax(consensus, axis=0)
-        n = consensus.sum(axis=0).astype(np.int64)
-        S = wsum[win, np.arange(win.size)] if win.size else np.zeros(0, np.int64)
-        return index2base(win), quality_string(column_quality(n, S))
-    # the concatenation branch: every base is its own column, n = 1 and S = its weight
-    seq = simple_assembly(all_predictions, flag_intersection=False)
-    vw = _valid_weights(all_predictions, weights)
-    w = np.concatenate(vw) if vw else np.zeros(0, np.int64)
-    if w.size != len(seq):
-        raise ValueError("a read of %d bases with %d weights" % (len(seq), w.size))
-    return seq, quality_string(column_quality(np.ones(w.size, np.int64), w))
-
-
 # ---------------------------------------------------------------- per-base methylation probabilities (MM / ML)
 # CpG models have a ninth token M, a methylated C.  A C or M token's modification weight is the model's
 # P(methylated | the base is a C) at its step in 16 bits: with d = (double)lp[C] - (double)lp[M],
@@ -342,76 +277,6 @@ def column_ml(n_cm, W):
     n64, w64 = np.asarray(n_cm, np.int64), np.asarray(W, np.int64)
     ml = np.where(n64 > 0, np.minimum(255, (256 * w64) // np.maximum(WEIGHT_ONE * n64, 1)), 0).astype(np.uint8)
     return int(ml) if ml.ndim == 0 else ml
-
-
-def _is_cm(base: str) -> bool:
-    return base.upper() in ("C", "M")
-
-
-def _add_count_m(consensus, wsum, msum, start, segment, w, mw):
-    """_add_count_q, a C or M vote's modification weight added to ``msum`` of its column."""
-    if len(mw) != len(segment):
-        raise ValueError("a chunk of %d bases with %d modification weights" % (len(segment), len(mw)))
-    _add_count_q(consensus, wsum, start, segment, w)
-    if start < 0:
-        segment, mw = segment[-start:], mw[-start:]
-        start = 0
-    for i, base in enumerate(segment):
-        if _is_cm(base):
-            msum[start + i] += mw[i]
-
-
-def simple_assembly_m(bpreads, weights, mod_weights):
-    """simple_assembly_q with the sums [length] (int64) of the C and M votes' modification weights beside it:
-    (consensus, wsum, msum)."""
-    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
-    vw = _valid_weights(bpreads, weights)
-    vm = _valid_weights(bpreads, mod_weights)
-    consensus = np.zeros([len(BASE_KEYS), 1000])
-    wsum = np.zeros([len(BASE_KEYS), 1000], np.int64)
-    msum = np.zeros(1000, np.int64)
-    pos = 0
-    length = 0
-    census_len = 1000
-    for indx, bpread in enumerate(valid):
-        if indx == 0:
-            _add_count_m(consensus, wsum, msum, 0, bpread, vw[0], vm[0])
-            continue
-        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
-        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
-        disp = match_block[0] - match_block[1]
-        if disp + pos + len(valid[indx]) > census_len:
-            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
-            wsum = np.pad(wsum, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
-            msum = np.pad(msum, (0, 1000), mode="constant", constant_values=0)
-            census_len += 1000
-        _add_count_m(consensus, wsum, msum, pos + disp, valid[indx], vw[indx], vm[indx])
-        pos += disp
-        length = max(length, pos + len(valid[indx]))
-    return consensus[:, :length], wsum[:, :length], msum[:length]
-
-
-def assemble_read_m(all_predictions, weights, mod_weights, src_seq_length: int, src_seq_stride: int):
-    """assemble_read_q with per-base methylation values: (sequence, quality string, ml uint8 [len(sequence)]).
-    ``mod_weights``: per chunk, the uint16 modification weight of every char of its x[0] with the spaces removed.
-    Sequence and qualities are assemble_read_q's; ml is 0 wherever the sequence is neither C nor M."""
-    if src_seq_stride < src_seq_length:
-        consensus, wsum, msum = simple_assembly_m(all_predictions, weights, mod_weights)
-        win = np.argmax(consensus, axis=0)
-        n = consensus.sum(axis=0).astype(np.int64)
-        S = wsum[win, np.arange(win.size)] if win.size else np.zeros(0, np.int64)
-        site = (win == BASE_DICT["C"]) | (win == BASE_DICT["M"])
-        n_cm = (consensus[BASE_DICT["C"]] + consensus[BASE_DICT["M"]]).astype(np.int64)
-        ml = np.where(site, column_ml(n_cm, msum), 0).astype(np.uint8)
-        return index2base(win), quality_string(column_quality(n, S)), ml
-    # the concatenation branch: every base is its own column, n_cm = 1 and W = its modification weight
-    seq, qual = assemble_read_q(all_predictions, weights, src_seq_length, src_seq_stride)
-    vm = _valid_weights(all_predictions, mod_weights)
-    mw = np.concatenate(vm) if vm else np.zeros(0, np.int64)
-    if mw.size != len(seq):
-        raise ValueError("a read of %d bases with %d modification weights" % (len(seq), mw.size))
-    site = np.fromiter((_is_cm(b) for b in seq), bool, len(seq))
-    return seq, qual, np.where(site, column_ml(np.ones(mw.size, np.int64), mw), 0).astype(np.uint8)
 
 
 def mod_fastq_record(name: str, sequence: str, quality: str, ml) -> str:
@@ -493,76 +358,6 @@ def column_position(n, P):
     return int(col) if col.ndim == 0 else col
 
 
-def _valid_positions(bpreads, positions, src_seq_stride: int):
-    """The absolute positions of simple_assembly's ``valid`` chunks, one int64 array per chunk: chunk ci of
-    ``bpreads`` (empty ones counted) adds ci * src_seq_stride to its chunk-relative ``positions[ci]``."""
-    if len(positions) != len(bpreads):
-        raise ValueError("one position array per chunk")
-    return [np.asarray(p, np.int64).reshape(-1) + ci * int(src_seq_stride)
-            for ci, (x, p) in enumerate(zip(bpreads, positions)) if x[0] != ""]
-
-
-def _add_count_p(consensus, psum, start, segment, p):
-    """_add_count, each vote's position added to ``psum`` of its column."""
-    if len(p) != len(segment):
-        raise ValueError("a chunk of %d bases with %d positions" % (len(segment), len(p)))
-    if start < 0:
-        segment, p = segment[-start:], p[-start:]
-        start = 0
-    for i, base in enumerate(segment):
-        consensus[BASE_DICT[base.upper()]][start + i] += 1
-        psum[start + i] += p[i]
-
-
-def simple_assembly_p(bpreads, positions, src_seq_stride: int):
-    """simple_assembly with flag_intersection, line for line, with the sums [length] (int64) of the votes'
-    absolute positions beside the counts: (consensus, psum)."""
-    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
-    vp = _valid_positions(bpreads, positions, src_seq_stride)
-    consensus = np.zeros([len(BASE_KEYS), 1000])
-    psum = np.zeros(1000, np.int64)
-    pos = 0
-    length = 0
-    census_len = 1000
-    for indx, bpread in enumerate(valid):
-        if indx == 0:
-            _add_count_p(consensus, psum, 0, bpread, vp[0])
-            continue
-        d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
-        match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
-        disp = match_block[0] - match_block[1]
-        if disp + pos + len(valid[indx]) > census_len:
-            consensus = np.pad(consensus, ((0, 0), (0, 1000)), mode="constant", constant_values=0)
-            psum = np.pad(psum, (0, 1000), mode="constant", constant_values=0)
-            census_len += 1000
-        _add_count_p(consensus, psum, pos + disp, valid[indx], vp[indx])
-        pos += disp
-        length = max(length, pos + len(valid[indx]))
-    return consensus[:, :length], psum[:length]
-
-
-def assemble_read_p(all_predictions, positions, src_seq_length: int, src_seq_stride: int):
-    """assemble_read with per-base signal positions: (sequence, read positions uint32 [len(sequence)]).
-    ``positions``: per chunk, the chunk-relative position (Translator.translate_reads(..., moves=True)) of
-    every char of its x[0] with the spaces removed; chunk ci's offset ci * src_seq_stride is added here, ci
-    counting the empty chunks too.  A column's position is the sum of its votes' positions // their number (0
-    with no vote), a read's the running maximum of its columns.  The sequence is assemble_read's, and what
-    assemble_read raises is raised here."""
-    if src_seq_stride < src_seq_length:
-        consensus, psum = simple_assembly_p(all_predictions, positions, src_seq_stride)
-        win = np.argmax(consensus, axis=0)
-        n = consensus.sum(axis=0).astype(np.int64)
-        col = column_position(n, psum)
-        return index2base(win), np.maximum.accumulate(col).astype(np.uint32)
-    # the concatenation branch: every base is its own column, n = 1 and P = its position
-    seq = simple_assembly(all_predictions, flag_intersection=False)
-    vp = _valid_positions(all_predictions, positions, src_seq_stride)
-    p = np.concatenate(vp) if vp else np.zeros(0, np.int64)
-    if p.size != len(seq):
-        raise ValueError("a read of %d bases with %d positions" % (len(seq), p.size))
-    return seq, np.maximum.accumulate(p).astype(np.uint32)
-
-
 def moves_record(name: str, sequence: str, rpos) -> str:
     """The three lines of result/<read>.moves: the header, the sequence (the .fasta's) and the read positions
     as comma-separated decimals, one per base (an empty line for an empty read)."""
@@ -572,36 +367,179 @@ def moves_record(name: str, sequence: str, rpos) -> str:
     return ">%s\n%s\n%s\n" % (name, sequence, ",".join("%d" % int(v) for v in rpos))
 
 
+# ---------------------------------------------------------------- the annotated vote (-fastq, -mod_probs, -moves)
+# One restatement of simple_assembly carries every per-base value through the vote: beside a column's counts,
+# the int64 sums of its votes' weights per class (wsum), of its C and M votes' modification weights (msum) and
+# of its votes' absolute positions (psum), each only when asked for.  column_quality, column_ml and
+# column_position turn a column's counts and sums into its values.
+Annotated = collections.namedtuple("Annotated", "sequence quality ml rpos")
+
+
+def _is_cm(base: str) -> bool:
+    return base.upper() in ("C", "M")
+
+
+def _valid_arrays(bpreads, arrays, what: str, stride: int = 0):
+    """The per-char values of simple_assembly's ``valid`` chunks, one int64 array per chunk; chunk ci of
+    ``bpreads`` (empty ones counted) adds ci * stride to its ``arrays[ci]``.  None for no ``arrays``."""
+    if arrays is None:
+        return None
+    if len(arrays) != len(bpreads):
+        raise ValueError("one %s array per chunk" % what)
+    return [np.asarray(a, np.int64).reshape(-1) + ci * stride
+            for ci, (x, a) in enumerate(zip(bpreads, arrays)) if x[0] != ""]
+
+
+def simple_assembly_annotated(bpreads, weights=None, mod_weights=None, positions=None, src_seq_stride=0):
+    """simple_assembly with flag_intersection, line for line, with the sums of the votes' values beside the
+    counts: (consensus, wsum, msum, psum), None for what was not given.  ``weights``: wsum [5, length], each
+    vote's weight added at its class and column (where _add_count counts it).  ``mod_weights``: msum [length], the
+    modification weights of the C and M votes.  ``positions`` with ``src_seq_stride``: psum [length], the votes'
+    absolute positions, chunk ci's at ci * src_seq_stride, ci counting the empty chunks.  All sums int64.  A
+    chunk whose array has another length than the chunk raises ValueError before any of its votes is counted."""
+    valid = [x[0].replace(" ", "") for x in bpreads if x[0] != ""]
+    vw = _valid_arrays(bpreads, weights, "weight")
+    vm = _valid_arrays(bpreads, mod_weights, "weight")
+    vp = _valid_arrays(bpreads, positions, "position", int(src_seq_stride))
+    consensus = np.zeros([len(BASE_KEYS), 1000])
+    wsum = None if vw is None else np.zeros([len(BASE_KEYS), 1000], np.int64)
+    msum = None if vm is None else np.zeros(1000, np.int64)
+    psum = None if vp is None else np.zeros(1000, np.int64)
+    pos = 0
+    length = 0
+    census_len = 1000
+    for indx, bpread in enumerate(valid):
+        if indx > 0:
+            d = difflib.SequenceMatcher(None, valid[indx - 1], bpread)
+            match_block = max(d.get_matching_blocks(), key=lambda x: x[2])
+            disp = match_block[0] - match_block[1]
+            if disp + pos + len(bpread) > census_len:
+                consensus, wsum, msum, psum = (
+                    a if a is None else np.pad(a, [(0, 0)] * (a.ndim - 1) + [(0, 1000)], mode="constant",
+                                               constant_values=0) for a in (consensus, wsum, msum, psum))
+                census_len += 1000
+            pos += disp
+            length = max(length, pos + len(bpread))
+        for v, what in ((vm, "modification weights"), (vw, "weights"), (vp, "positions")):
+            if v is not None and len(v[indx]) != len(bpread):
+                raise ValueError("a chunk of %d bases with %d %s" % (len(bpread), len(v[indx]), what))
+        _add_count(consensus, pos, bpread)
+        # the same votes' values: the chars left of column 0 are dropped, the others land on distinct columns
+        lo = max(-pos, 0)
+        cols = np.arange(pos + lo, pos + len(bpread))
+        if wsum is not None or msum is not None:
+            k = np.array([BASE_DICT[base.upper()] for base in bpread[lo:]], np.int64)
+        if wsum is not None:
+            wsum[k, cols] += vw[indx][lo:]
+        if msum is not None:
+            msum[cols] += np.where((k == BASE_DICT["C"]) | (k == BASE_DICT["M"]), vm[indx][lo:], 0)
+        if psum is not None:
+            psum[cols] += vp[indx][lo:]
+    return tuple(a if a is None else a[..., :length] for a in (consensus, wsum, msum, psum))
+
+
+def assemble_read_annotated(all_predictions, src_seq_length: int, src_seq_stride: int, weights=None,
+                            mod_weights=None, positions=None) -> Annotated:
+    """assemble_read with a read's per-base values: Annotated(sequence, quality, ml, rpos), None for what was
+    not asked for.  The three arguments are laid out alike: per chunk, one value for every char of its x[0] with
+    the spaces removed.  ``weights`` (uint16 token weights): ``quality``, the FASTQ string of the columns' Q.
+    ``mod_weights`` (uint16 modification weights, only beside ``weights``): ``ml`` uint8 [len(sequence)], 0
+    wherever the sequence is neither C nor M.  ``positions`` (chunk-relative signal positions,
+    Translator.translate_reads(..., moves=True); chunk ci's offset ci * src_seq_stride is added here, ci counting
+    the empty chunks too): ``rpos`` uint32 [len(sequence)], the running maximum of the columns' positions.  The
+    sequence is assemble_read's, and what assemble_read raises is raised here."""
+    if mod_weights is not None and weights is None:
+        raise ValueError("mod_weights need weights")
+    if weights is None and positions is None:
+        return Annotated(assemble_read(all_predictions, src_seq_length, src_seq_stride), None, None, None)
+    if src_seq_stride < src_seq_length:
+        consensus, S, W, P = simple_assembly_annotated(all_predictions, weights, mod_weights, positions,
+                                                       src_seq_stride)
+        win = np.argmax(consensus, axis=0)
+        seq = index2base(win)
+        n = consensus.sum(axis=0).astype(np.int64)
+        n_cm = (consensus[BASE_DICT["C"]] + consensus[BASE_DICT["M"]]).astype(np.int64)
+        if S is not None:
+            S = S[win, np.arange(win.size)]  # the winning class's weights
+    else:
+        # the concatenation branch: every base is its own column, with one vote and its own value as each sum
+        seq = simple_assembly(all_predictions, flag_intersection=False)
+        n = n_cm = np.ones(len(seq), np.int64)
+
+        def own(arrays, what, many, stride=0):
+            v = _valid_arrays(all_predictions, arrays, what, stride)
+            if v is not None:
+                v = np.concatenate(v) if v else np.zeros(0, np.int64)
+                if v.size != len(seq):
+                    raise ValueError("a read of %d bases with %d %s" % (len(seq), v.size, many))
+            return v
+        S = own(weights, "weight", "weights")
+        W = own(mod_weights, "weight", "modification weights")
+        P = own(positions, "position", "positions", int(src_seq_stride))
+    quality = ml = rpos = None
+    if S is not None:
+        quality = quality_string(column_quality(n, S))
+    if W is not None:
+        site = np.fromiter((_is_cm(b) for b in seq), bool, len(seq))
+        ml = np.where(site, column_ml(n_cm, W), 0).astype(np.uint8)
+    if P is not None:
+        rpos = np.maximum.accumulate(column_position(n, P)).astype(np.uint32)
+    return Annotated(seq, quality, ml, rpos)
+
+
+def assemble_read_q(all_predictions, weights, src_seq_length: int, src_seq_stride: int):
+    """assemble_read with per-base qualities: (sequence, quality string); see assemble_read_annotated."""
+    a = assemble_read_annotated(all_predictions, src_seq_length, src_seq_stride, weights=weights)
+    return a.sequence, a.quality
+
+
+def assemble_read_m(all_predictions, weights, mod_weights, src_seq_length: int, src_seq_stride: int):
+    """assemble_read_q with per-base methylation values: (sequence, quality string, ml uint8 [len(sequence)])."""
+    a = assemble_read_annotated(all_predictions, src_seq_length, src_seq_stride, weights=weights,
+                                mod_weights=mod_weights)
+    return a.sequence, a.quality, a.ml
+
+
+def assemble_read_p(all_predictions, positions, src_seq_length: int, src_seq_stride: int):
+    """assemble_read with per-base signal positions: (sequence, read positions uint32 [len(sequence)])."""
+    a = assemble_read_annotated(all_predictions, src_seq_length, src_seq_stride, positions=positions)
+    return a.sequence, a.rpos
+
+
 # ---------------------------------------------------------------- assembly on the device (-assembly gpu)
 ASM_STATUS_LONG = 1   # include/nanodec.h nd_assemble_reads: a chunk of 200 or more chars (difflib autojunk)
 ASM_STATUS_CHAR = 2   # a char whose upper case is not in BASE_KEYS
+AssemblyInput = collections.namedtuple("AssemblyInput", "bases chunk_off read_off host qw mw bp")
+AssemblyOutput = collections.namedtuple("AssemblyOutput", "seq seq_len status qual ml rpos")
 
 
 def pack_assembly_input(reads, weights=None, mod_weights=None, positions=None, src_seq_stride=None):
     """The input of nd_assemble_reads for a group of reads (each the
     all_predictions assemble_read takes): every chunk's x[0] with the spaces
-    removed, as ASCII bytes, concatenated.  Returns (bases uint8 [total],
-    chunk_off int32 [C + 1], read_off int32 [R + 1], host): read r owns chunks
+    removed, as ASCII bytes, concatenated.  Returns AssemblyInput(bases uint8 [total],
+    chunk_off int32 [C + 1], read_off int32 [R + 1], host, qw, mw, bp): read r owns chunks
     read_off[r] .. read_off[r+1], one per prediction, empty ones included.
     ``host`` lists the reads kept back for assemble_read: text that is not
     ASCII, and a hypothesis of nothing but spaces (simple_assembly drops ""
     before it removes the spaces, so that one stays in its chunk list as an
     empty string).  Such a read is packed with no chunks.
-    With ``weights`` (per read, per chunk, the uint16 weight of every char of that string) a fifth value
-    follows: qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q).  With
-    ``mod_weights`` too (laid out like ``weights``, which it needs) a sixth: mw uint16 [total], each byte's
-    modification weight (nd_assemble_reads_m).  With ``positions`` instead (per read, per chunk, the
-    chunk-relative position of every char; not beside ``weights``) and ``src_seq_stride`` a fifth value follows:
-    bp uint32 [total], each byte's absolute position, chunk ci of its read at ci * src_seq_stride
-    (nd_assemble_reads_p)."""
-    lens, parts, host, wparts, mparts, pparts, pci = [], [], [], [], [], [], []
-    if positions is not None:
-        if weights is not None or src_seq_stride is None or len(positions) != len(reads):
-            raise ValueError("one list of positions per read, with src_seq_stride and without weights")
+    The last three are None unless asked for.  ``weights`` (per read, per chunk, the uint16 weight of every char
+    of that string): qw uint16 [total], the weight of each byte of ``bases`` (nd_assemble_reads_q).
+    ``mod_weights`` (laid out like ``weights``, which it needs): mw uint16 [total], each byte's modification
+    weight (nd_assemble_reads_m).  ``positions`` (per read, per chunk, the chunk-relative position of every char)
+    with ``src_seq_stride``: bp uint32 [total], each byte's absolute position, chunk ci of its read at
+    ci * src_seq_stride (nd_assemble_reads_p)."""
+    if positions is not None and (src_seq_stride is None or len(positions) != len(reads)):
+        raise ValueError("one list of positions per read, with src_seq_stride")
     if weights is not None and len(weights) != len(reads):
         raise ValueError("one list of weights per read")
     if mod_weights is not None and (weights is None or len(mod_weights) != len(reads)):
         raise ValueError("one list of modification weights per read, beside the weights")
+    # what was given: its name in the messages (one, many), the per-read lists, the dtype, and the chunks' arrays
+    kinds = [k + ([],) for k in (("weight", "weights", weights, np.uint16),
+                                 ("modification weight", "modification weights", mod_weights, np.uint16),
+                                 ("position", "positions", positions, None)) if k[2] is not None]
+    lens, parts, host, pci = [], [], [], []
     read_off = np.zeros(len(reads) + 1, np.int64)
     for r, preds in enumerate(reads):
         strs = [x[0].replace(" ", "") for x in preds]
@@ -613,60 +551,48 @@ def pack_assembly_input(reads, weights=None, mod_weights=None, positions=None, s
             host.append(r)
             read_off[r + 1] = read_off[r]
             continue
-        if weights is not None:
-            if len(weights[r]) != len(strs):
-                raise ValueError("one weight array per chunk")
-            for st, w in zip(strs, weights[r]):
-                w = np.asarray(w, np.uint16).reshape(-1)
+        for one, many, given, dtype, packed in kinds:
+            if len(given[r]) != len(strs):
+                raise ValueError("one %s array per chunk" % one)
+            for st, w in zip(strs, given[r]):
+                w = np.asarray(w, dtype).reshape(-1)
                 if w.size != len(st):
-                    raise ValueError("a chunk of %d bases with %d weights" % (len(st), w.size))
-                wparts.append(w)
-        if mod_weights is not None:
-            if len(mod_weights[r]) != len(strs):
-                raise ValueError("one modification weight array per chunk")
-            for st, w in zip(strs, mod_weights[r]):
-                w = np.asarray(w, np.uint16).reshape(-1)
-                if w.size != len(st):
-                    raise ValueError("a chunk of %d bases with %d modification weights" % (len(st), w.size))
-                mparts.append(w)
-        if positions is not None:
-            if len(positions[r]) != len(strs):
-                raise ValueError("one position array per chunk")
-            for ci, (st, w) in enumerate(zip(strs, positions[r])):
-                w = np.asarray(w).reshape(-1)
-                if w.size != len(st):
-                    raise ValueError("a chunk of %d bases with %d positions" % (len(st), w.size))
-                pparts.append(w)
-                pci.append(ci)
+                    raise ValueError("a chunk of %d bases with %d %s" % (len(st), w.size, many))
+                packed.append(w)
         parts.append(raw)
         lens.extend(len(s) for s in strs)
+        if positions is not None:
+            pci.extend(range(len(strs)))
         read_off[r + 1] = read_off[r] + len(strs)
     chunk_off = np.zeros(len(lens) + 1, np.int64)
     chunk_off[1:] = np.cumsum(np.asarray(lens, np.int64))
     if chunk_off[-1] >= 2 ** 31:
         raise ValueError("more than 2^31 - 1 bases in one assembly group")
     bases = np.frombuffer(bytearray(b"").join(parts), np.uint8)  # a bytearray: writable, as torch.from_numpy wants
-    if positions is not None:
+    flat = {many: np.concatenate(packed) if packed else np.zeros(0, dtype) for one, many, given, dtype, packed in kinds}
+    bp = flat.get("positions")
+    if bp is not None:
         # the chunks' offsets in one pass: ci * stride repeated over each chunk's chars
-        off = np.repeat(np.asarray(pci, np.int64) * int(src_seq_stride), [w.size for w in pparts])
-        bp = (np.concatenate(pparts).astype(np.int64) + off).astype(np.uint32) if pparts else np.zeros(0, np.uint32)
-        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, bp
-    if weights is None:
-        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host
-    qw = np.concatenate(wparts) if wparts else np.zeros(0, np.uint16)
-    if mod_weights is None:
-        return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw
-    mw = np.concatenate(mparts) if mparts else np.zeros(0, np.uint16)
-    return bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, qw, mw
+        off = np.repeat(np.asarray(pci, np.int64) * int(src_seq_stride), lens)
+        bp = (bp.astype(np.int64) + off).astype(np.uint32)
+    return AssemblyInput(bases, chunk_off.astype(np.int32), read_off.astype(np.int32), host, flat.get("weights"),
+                         flat.get("modification weights"), bp)
+
+
+# which optional inputs (qw, mw, bp) a call carries -> its entry point; <entry>_work_bytes sizes its work buffer.
+# Every entry takes bases, the optional inputs it has, chunk_off, read_off, R, C, total, seq, one output per optional
+# input (qual, ml, rpos), seq_len, status, work, work_bytes, stream.
+_ASSEMBLE_ENTRY = {(False, False, False): "nd_assemble_reads", (True, False, False): "nd_assemble_reads_q",
+                   (True, True, False): "nd_assemble_reads_m", (False, False, True): "nd_assemble_reads_p"}
 
 
 def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None, bp=None):
-    """One nd_assemble_reads call on the CURRENT stream of ``device``:
-    (seq uint8 [total], seq_len int32 [R], status int32 [R]) on the host.  With ``qw`` (uint16 [total], each
-    base's weight) the call is nd_assemble_reads_q and qual uint8 [total] follows; with ``mw`` too (uint16 [total],
-    each base's modification weight) it is nd_assemble_reads_m and ml uint8 [total] follows qual.  With ``bp``
-    instead (uint32 [total], each base's absolute position) it is nd_assemble_reads_p and rpos uint32 [total]
-    follows status."""
+    """One nd_assemble_reads call on the CURRENT stream of ``device``: AssemblyOutput(seq uint8 [total],
+    seq_len int32 [R], status int32 [R], qual, ml, rpos) on the host, the last three None unless computed.  With
+    ``qw`` (uint16 [total], each base's weight) the call is nd_assemble_reads_q and qual is uint8 [total]; with
+    ``mw`` too (uint16 [total], each base's modification weight) it is nd_assemble_reads_m and ml is uint8
+    [total].  With ``bp`` instead (uint32 [total], each base's absolute position) it is nd_assemble_reads_p and
+    rpos is uint32 [total]."""
     import ctypes
 
     import torch
@@ -679,55 +605,30 @@ def _assemble_device(bases, chunk_off, read_off, device, qw=None, mw=None, bp=No
         raise ValueError("mw needs qw")
     if bp is not None and qw is not None:
         raise ValueError("bp goes with the plain call only")
-    work_bytes = int((L.nd_assemble_reads_p_work_bytes if bp is not None else
-                      L.nd_assemble_reads_work_bytes if qw is None else L.nd_assemble_reads_q_work_bytes
-                      if mw is None else L.nd_assemble_reads_m_work_bytes)(C, total))
+    for name, a, dtype in (("qw", qw, np.uint16), ("mw", mw, np.uint16), ("bp", bp, np.uint32)):
+        if a is not None and (a.dtype != dtype or a.size != total):
+            raise ValueError("%s must hold one %s per base" % (name, np.dtype(dtype).name))
+    entry = _ASSEMBLE_ENTRY[(qw is not None, mw is not None, bp is not None)]
+    work_bytes = int(getattr(L, entry + "_work_bytes")(C, total))
     with torch.cuda.device(dev):
         off_d = _pinned(np.concatenate([chunk_off, read_off])).to(dev, non_blocking=True)
         bases_d = _pinned(bases).to(dev, non_blocking=True)
         seq_d = torch.empty(total, dtype=torch.uint8, device=dev)
         out_d = torch.empty(2, R, dtype=torch.int32, device=dev)  # seq_len, status
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
+        # the optional inputs go over as their bits (torch copies no unsigned 16- or 32-bit type)
+        in_d = [_pinned(a.view("i%d" % a.itemsize)).to(dev, non_blocking=True) for a in (qw, mw, bp) if a is not None]
+        opt_d = [None if a is None else torch.empty(total, dtype=t, device=dev)
+                 for a, t in ((qw, torch.uint8), (mw, torch.uint8), (bp, torch.int32))]  # qual, ml, rpos
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-        if bp is not None:
-            if bp.dtype != np.uint32 or bp.size != total:
-                raise ValueError("bp must hold one uint32 per base")
-            bp_d = _pinned(bp.view(np.int32)).to(dev, non_blocking=True)  # the bits
-            rpos_d = torch.empty(total, dtype=torch.int32, device=dev)
-            _lib.check(L.nd_assemble_reads_p(p(bases_d), p(bp_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
-                                             p(rpos_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
-                       "nd_assemble_reads_p")
-        elif qw is None:
-            _lib.check(L.nd_assemble_reads(p(bases_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
-                                           p(out_d[0]), p(out_d[1]), p(work_d), work_bytes, stream),
-                       "nd_assemble_reads")
-        else:
-            if qw.dtype != np.uint16 or qw.size != total:
-                raise ValueError("qw must hold one uint16 per base")
-            qw_d = _pinned(qw.view(np.int16)).to(dev, non_blocking=True)  # the bits: torch has no uint16 copy
-            qual_d = torch.empty(total, dtype=torch.uint8, device=dev)
-            if mw is None:
-                _lib.check(L.nd_assemble_reads_q(p(bases_d), p(qw_d), p(off_d), p(off_d[C + 1:]), R, C, total,
-                                                 p(seq_d), p(qual_d), p(out_d[0]), p(out_d[1]), p(work_d), work_bytes,
-                                                 stream), "nd_assemble_reads_q")
-            else:
-                if mw.dtype != np.uint16 or mw.size != total:
-                    raise ValueError("mw must hold one uint16 per base")
-                mw_d = _pinned(mw.view(np.int16)).to(dev, non_blocking=True)
-                ml_d = torch.empty(total, dtype=torch.uint8, device=dev)
-                _lib.check(L.nd_assemble_reads_m(p(bases_d), p(qw_d), p(mw_d), p(off_d), p(off_d[C + 1:]), R, C, total,
-                                                 p(seq_d), p(qual_d), p(ml_d), p(out_d[0]), p(out_d[1]), p(work_d),
-                                                 work_bytes, stream), "nd_assemble_reads_m")
+        _lib.check(getattr(L, entry)(p(bases_d), *map(p, in_d), p(off_d), p(off_d[C + 1:]), R, C, total, p(seq_d),
+                                     *(p(t) for t in opt_d if t is not None), p(out_d[0]), p(out_d[1]), p(work_d),
+                                     work_bytes, stream), entry)
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         seq = seq_d.cpu().numpy()
-        if bp is not None:
-            return seq, out[0], out[1], rpos_d.cpu().numpy().view(np.uint32)
-        if mw is not None:
-            return seq, out[0], out[1], qual_d.cpu().numpy(), ml_d.cpu().numpy()
-        if qw is not None:
-            return seq, out[0], out[1], qual_d.cpu().numpy()
-    return seq, out[0], out[1]
+        qual, ml, rpos = (None if t is None else t.cpu().numpy() for t in opt_d)
+    return AssemblyOutput(seq, out[0], out[1], qual, ml, None if rpos is None else rpos.view(np.uint32))
 
 
 def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None, stats=None,
@@ -746,103 +647,56 @@ def assemble_reads(reads, src_seq_length: int, src_seq_stride: int, device=None,
     increased by the reads of this call and by those assembled on the host.
     ``defer_errors``: a read whose host assembly raises yields None instead
     (the caller assembles it again where it handles that read's errors).
-    ``weights`` (per read, per chunk, the uint16 weight of every char of the chunk's string; see
-    assemble_read_q): every read yields (sequence, quality string) instead, the device call is
-    nd_assemble_reads_q, and the host path and the fallback are assemble_read_q.
-    ``mod_weights`` (beside ``weights``, laid out like them; see assemble_read_m): every read yields (sequence,
-    quality string, ml uint8 array), the device call is nd_assemble_reads_m, and the host path and the fallback
-    are assemble_read_m.
-    ``positions`` (per read, per chunk, the chunk-relative signal position of every char of the chunk's string;
-    see assemble_read_p): every read yields (sequence, read positions uint32 array), the device call is
-    nd_assemble_reads_p, and the host path and the fallback are assemble_read_p.  Beside ``weights`` the
-    positions follow as the last entry, (sequence, quality string[, ml], read positions), from a second pass
-    over the same reads (a second device call: the forms are not multiplied); ``stats`` counts the reads once."""
+    With ``weights``, ``mod_weights`` (beside ``weights``) or ``positions`` (each per read what
+    assemble_read_annotated takes) the host path and the fallback are assemble_read_annotated and every read
+    yields a tuple: (sequence, quality string) with ``weights``, the device call being nd_assemble_reads_q;
+    (sequence, quality string, ml uint8 array) with ``mod_weights``, by nd_assemble_reads_m; and with
+    ``positions`` the read positions (uint32 array) come last, by nd_assemble_reads_p: that call alone, or beside
+    ``weights`` a second call on the same packed group (the forms are not multiplied)."""
     reads = list(reads)
-    if positions is not None and weights is not None:
-        first = assemble_reads(reads, src_seq_length, src_seq_stride, device, stats, defer_errors, weights,
-                               mod_weights)
-        second = assemble_reads(reads, src_seq_length, src_seq_stride, device, None, defer_errors,
-                                positions=positions)
-        return [None if a is None or b is None else a + (b[1],) for a, b in zip(first, second)]
-    if positions is not None:
-        positions = list(positions)
-        if len(positions) != len(reads):
-            raise ValueError("one list of positions per read")
-        one = lambda r: assemble_read_p(reads[r], positions[r], src_seq_length, src_seq_stride)  # noqa: E731
-        if device is None or src_seq_stride >= src_seq_length:
-            return [one(r) for r in range(len(reads))]
-        R = len(reads)
-        bases, chunk_off, read_off, host, bp = pack_assembly_input(reads, positions=positions,
-                                                                   src_seq_stride=src_seq_stride)
-        out = [("", np.zeros(0, np.uint32)) for _ in range(R)]
-        todo = set(host)
-        if bases.size:
-            seq, seq_len, status, rpos = _assemble_device(bases, chunk_off, read_off, device, bp=bp)
-            raw = seq.tobytes()
-            start = chunk_off[read_off[:-1]]
-            for r in range(R):
-                if status[r] != 0:
-                    todo.add(r)
-                elif seq_len[r] > 0:
-                    out[r] = (raw[start[r]: start[r] + seq_len[r]].decode("ascii"),
-                              rpos[start[r]: start[r] + seq_len[r]].copy())
-        if stats is not None:
-            stats["reads"] = stats.get("reads", 0) + R
-            stats["fallback"] = stats.get("fallback", 0) + len(todo)
-        for r in sorted(todo):
-            try:
-                out[r] = one(r)
-            except Exception:
-                if not defer_errors:
-                    raise
-                out[r] = None
-        return out
     if mod_weights is not None and weights is None:
         raise ValueError("mod_weights need weights")
-    if weights is None:
-        one = lambda r: assemble_read(reads[r], src_seq_length, src_seq_stride)  # noqa: E731
-    else:
-        weights = list(weights)
-        if len(weights) != len(reads):
-            raise ValueError("one list of weights per read")
-        one = lambda r: assemble_read_q(reads[r], weights[r], src_seq_length, src_seq_stride)  # noqa: E731
-        if mod_weights is not None:
-            mod_weights = list(mod_weights)
-            if len(mod_weights) != len(reads):
-                raise ValueError("one list of modification weights per read")
-            one = lambda r: assemble_read_m(reads[r], weights[r], mod_weights[r], src_seq_length,  # noqa: E731
-                                            src_seq_stride)
-    if device is None or src_seq_stride >= src_seq_length:
-        return [one(r) for r in range(len(reads))]
+    given = []
+    for many, arrays in (("weights", weights), ("modification weights", mod_weights), ("positions", positions)):
+        given.append(None if arrays is None else list(arrays))
+        if arrays is not None and len(given[-1]) != len(reads):
+            raise ValueError("one list of %s per read" % many)
+    weights, mod_weights, positions = given
+
+    plain = weights is None and positions is None
+
+    def shape(a):  # a read as the caller gets it: the string, or a tuple with what was asked for
+        return a[0] if plain else tuple(v for v in a if v is not None)
+
+    def one(r):
+        return shape(assemble_read_annotated(reads[r], src_seq_length, src_seq_stride,
+                                             *(None if v is None else v[r] for v in given)))
     R = len(reads)
-    if weights is None:
-        bases, chunk_off, read_off, host = pack_assembly_input(reads)
-        out = [""] * R  # no bases at all: every device read is ""
-    elif mod_weights is None:
-        bases, chunk_off, read_off, host, qw = pack_assembly_input(reads, weights)
-        out = [("", "")] * R
-    else:
-        bases, chunk_off, read_off, host, qw, mw = pack_assembly_input(reads, weights, mod_weights)
-        out = [("", "", np.zeros(0, np.uint8)) for _ in range(R)]
-    todo = set(host)
+    if device is None or src_seq_stride >= src_seq_length:
+        return [one(r) for r in range(R)]
+    packed = pack_assembly_input(reads, weights, mod_weights, positions, src_seq_stride)
+    bases, chunk_off, read_off = packed[:3]
+    # no bases at all: every device read is empty
+    out = [shape(("", None if weights is None else "", None if mod_weights is None else np.zeros(0, np.uint8),
+                  None if positions is None else np.zeros(0, np.uint32)))] * R
+    todo = set(packed.host)
     if bases.size:
-        if weights is None:
-            seq, seq_len, status = _assemble_device(bases, chunk_off, read_off, device)
-        elif mod_weights is None:
-            seq, seq_len, status, qual = _assemble_device(bases, chunk_off, read_off, device, qw)
-        else:
-            seq, seq_len, status, qual, ml = _assemble_device(bases, chunk_off, read_off, device, qw, mw)
-        raw = seq.tobytes()
+        d = None
+        if weights is not None or positions is None:
+            d = _assemble_device(bases, chunk_off, read_off, device, packed.qw, packed.mw)
+        if positions is not None:  # a call of its own on the same packing; the same bases give the same status
+            p = _assemble_device(bases, chunk_off, read_off, device, bp=packed.bp)
+            d = p if d is None else d._replace(status=d.status | p.status, rpos=p.rpos)
+        raw, seq_len, status = d.seq.tobytes(), d.seq_len, d.status
+        extras = [(v, f) for v, f in ((d.qual, quality_string), (d.ml, np.copy), (d.rpos, np.copy)) if v is not None]
         start = chunk_off[read_off[:-1]]
         for r in range(R):
             if status[r] != 0:
                 todo.add(r)
             elif seq_len[r] > 0:
-                out[r] = raw[start[r]: start[r] + seq_len[r]].decode("ascii")
-                if weights is not None:
-                    out[r] = (out[r], quality_string(qual[start[r]: start[r] + seq_len[r]]))
-                if mod_weights is not None:
-                    out[r] = out[r] + (ml[start[r]: start[r] + seq_len[r]].copy(),)
+                s = slice(start[r], start[r] + seq_len[r])
+                seq = raw[s].decode("ascii")
+                out[r] = seq if plain else (seq,) + tuple(f(v[s]) for v, f in extras)
     if stats is not None:
         stats["reads"] = stats.get("reads", 0) + R
         stats["fallback"] = stats.get("fallback", 0) + len(todo)

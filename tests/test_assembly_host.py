@@ -26,7 +26,7 @@ def test_pack_assembly_input_offsets():
         [["A C G T", "T T T T T T"], ["C", "G G"]],               # n-best lists: x[0] only
         [["acgm"]],
     ]
-    bases, chunk_off, read_off, host = frontend.pack_assembly_input(reads)
+    bases, chunk_off, read_off, host = frontend.pack_assembly_input(reads)[:4]
     assert host == []
     assert bases.dtype == np.uint8 and chunk_off.dtype == np.int32 and read_off.dtype == np.int32
     assert bases.tobytes() == b"ACGGTACGTCacgm"
@@ -39,14 +39,15 @@ def test_pack_assembly_input_offsets():
 
 def test_pack_assembly_input_keeps_unpackable_reads_on_the_host():
     reads = [[["A C"], ["C G"]], [["A ç"], ["C"]], [["A"], [" "], ["C"]], [["G"]]]
-    bases, chunk_off, read_off, host = frontend.pack_assembly_input(reads)
+    bases, chunk_off, read_off, host = frontend.pack_assembly_input(reads)[:4]
     # non-ASCII text, and a hypothesis of spaces alone (the host path keeps it as an empty string in its
     # chunk list, where it moves the next chunk): packed with no chunks, listed for assemble_read
     assert host == [1, 2]
     assert list(read_off) == [0, 2, 2, 2, 3]
     assert bases.tobytes() == b"ACCGG" and list(chunk_off) == [0, 2, 4, 5]
     empty = frontend.pack_assembly_input([])
-    assert empty[0].size == 0 and list(empty[1]) == [0] and list(empty[2]) == [0] and empty[3] == []
+    assert empty.bases.size == 0 and list(empty.chunk_off) == [0] and list(empty.read_off) == [0] and empty.host == []
+    assert empty.qw is None and empty.mw is None and empty.bp is None
 
 
 @pytest.fixture(scope="module")

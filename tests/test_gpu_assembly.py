@@ -3,6 +3,7 @@ against the host path: the expected value is always frontend.assemble_read, and 
 identity."""
 import random
 
+import numpy as np
 import pytest
 import torch
 
@@ -18,9 +19,9 @@ def host(reads):
 
 def device_raw(reads):
     """(strings or None where status != 0, status) straight from one nd_assemble_reads call."""
-    bases, chunk_off, read_off, kept = frontend.pack_assembly_input(reads)
+    bases, chunk_off, read_off, kept = frontend.pack_assembly_input(reads)[:4]
     assert kept == []
-    seq, seq_len, status = frontend._assemble_device(bases, chunk_off, read_off, 0)
+    seq, seq_len, status = frontend._assemble_device(bases, chunk_off, read_off, 0)[:3]
     start = chunk_off[read_off[:-1]]
     out = []
     for r in range(len(reads)):
@@ -219,3 +220,23 @@ def test_cli_gpu_assembly_matches_host(tmp_path, capfd):
     fasta = [v for k, v in files["gpu"].items() if k.startswith("result")]
     assert any(v.split(b"\n", 1)[1] for v in fasta)  # not a comparison of empty reads
     assert "reads were assembled on the host" in capfd.readouterr().err
+
+
+def test_every_annotation_in_one_call_with_a_fallback():
+    """weights, mod_weights and positions together: one packing, two device calls (_m, then _p) and one host
+    fallback, equal to the host path."""
+    from tests.test_assembly_forms_host import make_group
+    reads, ws, ms, ps = (list(v) for v in make_group())
+    rng = random.Random(9)
+    t = "".join(rng.choice("ACGTM") for _ in range(230))
+    reads[5] = [[spaced(t[:200])], [spaced(t[190:230])]]  # a chunk of 200 chars: assembled on the host
+    ws[5] = ms[5] = ps[5] = [list(range(200)), list(range(40))]
+    stats = {}
+    got = frontend.assemble_reads(reads, LEN, STRIDE, device=0, stats=stats, weights=ws, mod_weights=ms, positions=ps)
+    exp = frontend.assemble_reads(reads, LEN, STRIDE, device=None, weights=ws, mod_weights=ms, positions=ps)
+    assert stats == {"reads": 6, "fallback": 1}
+    assert sum(len(e[0]) for e in exp) > 300 and len(exp[5][0]) > 200
+    for r, (g, e) in enumerate(zip(got, exp)):
+        assert len(g) == len(e) == 4 and g[:2] == e[:2], r
+        assert g[2].dtype == e[2].dtype == np.uint8 and g[2].tolist() == e[2].tolist(), r
+        assert g[3].dtype == e[3].dtype == np.uint32 and g[3].tolist() == e[3].tolist(), r

@@ -134,10 +134,10 @@ def device_raw_m(reads, ws, ms):
     """One nd_assemble_reads_m call and one nd_assemble_reads_q call on the same input: ((sequence, quality,
     ml) or None where status != 0, status, seq bytes, qual bytes, ml bytes); the q call's seq, qual, lengths
     and status are asserted identical."""
-    bases, chunk_off, read_off, kept, qw, mw = frontend.pack_assembly_input(reads, ws, ms)
+    bases, chunk_off, read_off, kept, qw, mw = frontend.pack_assembly_input(reads, ws, ms)[:6]
     assert kept == []
-    seq, seq_len, status, qual, ml = frontend._assemble_device(bases, chunk_off, read_off, 0, qw, mw)
-    seq0, seq_len0, status0, qual0 = frontend._assemble_device(bases, chunk_off, read_off, 0, qw)
+    seq, seq_len, status, qual, ml = frontend._assemble_device(bases, chunk_off, read_off, 0, qw, mw)[:5]
+    seq0, seq_len0, status0, qual0 = frontend._assemble_device(bases, chunk_off, read_off, 0, qw)[:4]
     assert (status == status0).all() and (seq_len == seq_len0).all()
     assert seq.tobytes() == seq0.tobytes() and qual.tobytes() == qual0.tobytes()
     start, end = chunk_off[read_off[:-1]], chunk_off[read_off[1:]]

@@ -131,10 +131,13 @@ def group():
 
 def test_assemble_p_raw_outputs_equal_the_plain_call(group):
     reads, pos, host = group
-    bases, chunk_off, read_off, kept, bp = frontend.pack_assembly_input(reads, positions=pos, src_seq_stride=STRIDE)
+    packed = frontend.pack_assembly_input(reads, positions=pos, src_seq_stride=STRIDE)
+    (bases, chunk_off, read_off, kept), bp = packed[:4], packed.bp
     assert kept == [] and bp.size == bases.size
-    seq0, len0, st0 = frontend._assemble_device(bases, chunk_off, read_off, 0)
-    seq, seq_len, status, rpos = frontend._assemble_device(bases, chunk_off, read_off, 0, bp=bp)
+    seq0, len0, st0 = frontend._assemble_device(bases, chunk_off, read_off, 0)[:3]
+    dev = frontend._assemble_device(bases, chunk_off, read_off, 0, bp=bp)
+    (seq, seq_len, status), rpos = dev[:3], dev.rpos
+    assert dev.qual is None and dev.ml is None
     assert seq.tobytes() == seq0.tobytes() and seq_len.tolist() == len0.tolist() and status.tolist() == st0.tolist()
     assert rpos.dtype == np.uint32 and rpos.size == bases.size
     start = chunk_off[read_off[:-1]]
@@ -154,7 +157,7 @@ def test_assemble_p_raw_outputs_equal_the_plain_call(group):
     with torch.cuda.stream(torch.cuda.Stream()):
         other = frontend._assemble_device(bases, chunk_off, read_off, 0, bp=bp)
     for o in (again, other):
-        assert o[3].tobytes() == rpos.tobytes() and o[0].tobytes() == seq.tobytes()
+        assert o.rpos.tobytes() == rpos.tobytes() and o.seq.tobytes() == seq.tobytes()
 
 
 def test_assemble_p_group_with_fallback_equals_host(group):

@@ -237,7 +237,9 @@ def test_assemble_read_p_sequence_is_assemble_reads():
 def test_pack_assembly_input_with_positions_and_host_group():
     reads = [[["A C"], [""], ["C G T"]], [["G"]], []]
     pos = [[[1, 2], [], [0, 5, 9]], [[7]], []]
-    bases, chunk_off, read_off, host, bp = frontend.pack_assembly_input(reads, positions=pos, src_seq_stride=60)
+    packed = frontend.pack_assembly_input(reads, positions=pos, src_seq_stride=60)
+    (bases, chunk_off, read_off, host), bp = packed[:4], packed.bp
+    assert packed.qw is None and packed.mw is None
     assert bases.tobytes() == b"ACCGTG" and host == []
     assert bp.dtype == np.uint32 and bp.tolist() == [1, 2, 120, 125, 129, 7]  # the empty chunk counts in ci
     assert chunk_off.tolist() == [0, 2, 2, 5, 6] and read_off.tolist() == [0, 3, 4, 4]

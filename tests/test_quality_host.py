@@ -191,10 +191,10 @@ def test_pack_assembly_input_with_weights():
     reads = [[["A C"], [""], ["G G T"]], [["é"]], [["T"]]]
     ws = [[[1, 2], [], [3, 4, 65535]], [[7]], [[9]]]
     plain = frontend.pack_assembly_input(reads)
-    bases, chunk_off, read_off, host, qw = frontend.pack_assembly_input(reads, ws)
-    assert len(plain) == 4 and host == plain[3] == [1]
-    assert bases.tobytes() == plain[0].tobytes() == b"ACGGTT"
-    assert (chunk_off == plain[1]).all() and (read_off == plain[2]).all()
+    bases, chunk_off, read_off, host, qw = frontend.pack_assembly_input(reads, ws)[:5]
+    assert plain.qw is None and host == plain.host == [1]
+    assert bases.tobytes() == plain.bases.tobytes() == b"ACGGTT"
+    assert (chunk_off == plain.chunk_off).all() and (read_off == plain.read_off).all()
     assert qw.dtype == np.uint16 and qw.tolist() == [1, 2, 3, 4, 65535, 9]
     with pytest.raises(ValueError):
         frontend.pack_assembly_input(reads, [[[1, 2], [], [3, 4]], [[7]], [[9]]])
