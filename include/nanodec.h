@@ -101,7 +101,8 @@ int nd_share_weights(nd_ctx* ctx, const nd_ctx* src);
  *   d_len     [B] i32 valid samples per chunk (src_lengths)
  *   d_span    [B] i32 padded length the reference batch would have had
  *             (= longest chunk of the reference batch; len <= span <= T).
- *             Positions >= span do not exist for that chunk.
+ *             Positions >= span do not exist for that chunk.  1 <= span:
+ *             the encoder's attention reads row span - 1 of the chunk.
  *   d_tokens  [B, max_len] i32 out;  d_score [B] f32 out
  *   d_logp    nullable [B, max_len, V] f32 out: per-step log-probs (pre min_len mask)
  *   stream    hipStream_t of the caller (void* here to keep HIP out of the ABI) */
@@ -805,6 +806,18 @@ int nd_op_fold_layernorm(const float* W, const float* bias, const float* ln_g, c
  * signal == 0.0 and keys >= span excluded; out [B*T, d]. */
 int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B,
                         int32_t T, void* stream);
+
+/* The same with both of the engine's forms in reach: exact != 0 runs the fp32
+ * kernel of nd_set_exact_fp32, exact == 0 the split-fp16 one, which sets
+ * *overflow (nullable device int32, never cleared here) to 1 when a live K or
+ * V element, or a live query element times log2(e) / sqrt(32), reaches 65504
+ * in magnitude; the fp32 kernel never writes the word.  Rows t < span of out
+ * are written, the others untouched; 1 <= span[b] (rows at or past span are
+ * not read for their values and may hold anything).  A null qkv, signal, span
+ * or out, or B < 1: ND_ERR_ARG before any HIP call; T outside 1..512:
+ * ND_ERR_ARG, nothing launched. */
+int nd_op_enc_attention_ex(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B,
+                           int32_t T, int32_t exact, int32_t* overflow, void* stream);
 
 /* Transformer encoder layer 0 up to (not including) W_o, as the engine runs
  * it: in closed form from the scalar samples (no x, no q | k | v rows), after

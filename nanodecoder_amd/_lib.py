@@ -134,6 +134,7 @@ SIGNATURES = {
     "nd_op_lstm_layer": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
     "nd_op_lstm_layer_f32": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _P]),
     "nd_op_enc_attention": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "nd_op_enc_attention_ex": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "nd_op_enc_layer0": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "nd_op_dec_self_attention": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _P]),
     "nd_op_dec_self_attention_beam": (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _P, _P]),

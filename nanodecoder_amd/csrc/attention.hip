@@ -373,12 +373,15 @@ enc_attention_h3_kernel(const float* __restrict__ qkv, const float* __restrict__
       vr[i] = ld4(row + 2 * ND_D);
     }
   };
+  // the wave's Q rows, clamped into the span like the K / V rows: a row at or past it does not exist for
+  // the chunk, so it reaches neither a result nor the range guard (its lanes carry row L - 1, unstored)
   auto issue_q = [&](int it) {
     const int h = it % ND_H, b = it / ND_H;
+    const int L = min(span[b], T);
     const size_t base = (size_t)b * T;
 #pragma unroll
     for (int j = 0; j < NQ; ++j) {
-      const float* qrow = qkv + (base + min((wave * NQ + j) * 32 + lr, T - 1)) * (3 * ND_D) + h * ND_DH + 8 * lh;
+      const float* qrow = qkv + (base + min((wave * NQ + j) * 32 + lr, L - 1)) * (3 * ND_D) + h * ND_DH + 8 * lh;
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
         qraw[j][2 * s2] = ld4(qrow + 16 * s2);

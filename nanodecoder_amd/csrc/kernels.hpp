@@ -155,7 +155,9 @@ hipError_t prepare_embed_qkv(const float* w_in, const float* b_in, const float* 
 // x[b*T+t][:] = signal[b][t] * w_in + b_in (Linear(1, d)); part: full-row stats
 hipError_t launch_enc_embed(const float* signal, const float* w_in, const float* b_in, float* x, float* part, int B,
                             int T, hipStream_t s);
-// flash attention over qkv [B*T, 768]; mask: signal == 0 (pad_val is not read), keys >= span excluded
+// flash attention over qkv [B*T, 768]; mask: signal == 0 (pad_val is not read), keys >= span excluded.
+// 1 <= span[b] is required: the split-fp16 kernel clamps its row loads to span - 1 (span = 0 would read the
+// row before the chunk); rows at or past span are read by neither form for their values.
 struct EncAttnArgs {
   const float* qkv = nullptr;
   SrcMask mask;

@@ -165,6 +165,14 @@ int nd_op_enc_attention(const float* qkv, const float* signal, const int32_t* sp
                                                            .T = T}, (hipStream_t)stream));
 }
 
+int nd_op_enc_attention_ex(const float* qkv, const float* signal, const int32_t* span, float* out, int32_t B,
+                           int32_t T, int32_t exact, int32_t* overflow, void* stream) {
+  if (!qkv || !signal || !span || !out || B < 1) return fail(ND_ERR_ARG, "enc_attention_ex: bad arguments");
+  return status("enc_attention_ex", nd::launch_enc_attention({.qkv = qkv, .mask = {signal, span}, .out = out, .B = B,
+                                                              .T = T, .exact = exact != 0, .ovf = overflow},
+                                                             (hipStream_t)stream));
+}
+
 int nd_op_enc_layer0(const float* signal, const int32_t* span, const float* w_in, const float* b_in,
                      const float* nwqkv, const float* nbqkv, float* out, int32_t B, int32_t T, float* ac_out,
                      double* scal_out, float* coef_out, void* stream) {

@@ -659,12 +659,17 @@ def op_gemm_split_q24(A: torch.Tensor, W: torch.Tensor, bias=None, norm=False):
     return img
 
 
-def op_enc_attention(qkv: torch.Tensor, signal: torch.Tensor, span: torch.Tensor):
+def op_enc_attention(qkv: torch.Tensor, signal: torch.Tensor, span: torch.Tensor, exact: bool = False, ovf=None,
+                     out=None):
+    """The encoder's self-attention (nd_op_enc_attention_ex): the split-fp16 kernel, or with exact the fp32
+    one.  ovf: an int32 device tensor, the range guard word (set to 1, never cleared).  out: written as it is
+    given ([>= B*T, 256] f32: rows t >= span and any rows past B*T keep what they held); zeros when None."""
     B, T = signal.shape
-    out = torch.zeros(B * T, qkv.shape[1] // 3, dtype=torch.float32, device=qkv.device)
+    if out is None:
+        out = torch.zeros(B * T, qkv.shape[1] // 3, dtype=torch.float32, device=qkv.device)
     s = ctypes.c_void_p(torch.cuda.current_stream(qkv.device).cuda_stream)
-    _lib.check(_lib.lib().nd_op_enc_attention(_ptr(qkv), _ptr(signal), _ptr(span.to(torch.int32)), _ptr(out), B, T, s),
-               "nd_op_enc_attention")
+    _lib.check(_lib.lib().nd_op_enc_attention_ex(_ptr(qkv), _ptr(signal), _ptr(span.to(torch.int32)), _ptr(out), B, T,
+                                                 int(bool(exact)), _ptr(ovf), s), "nd_op_enc_attention_ex")
     return out
 
 

@@ -85,6 +85,25 @@ def test_lstm_layer_refuses_bad_arguments(L, entry, kw):
     _refused(L, rc, b"lstm_layer: bad arguments")
 
 
+def _enc_attention_ex(L, qkv=True, signal=True, span=True, out=True, B=1, T=4, exact=0):
+    opt = lambda on: _buf() if on else None
+    return L.nd_op_enc_attention_ex(opt(qkv), opt(signal), opt(span), opt(out), B, T, exact, None, None)
+
+
+@pytest.mark.parametrize("exact", [0, 1])
+@pytest.mark.parametrize("kw", [dict(qkv=False), dict(signal=False), dict(span=False), dict(out=False), dict(B=0)])
+def test_enc_attention_ex_refuses_bad_arguments(L, kw, exact):
+    """each null pointer, no chunks: the entry's own checks, for either form"""
+    _refused(L, _enc_attention_ex(L, exact=exact, **kw), b"enc_attention_ex: bad arguments")
+
+
+@pytest.mark.parametrize("exact", [0, 1])
+@pytest.mark.parametrize("T", [0, 513])
+def test_enc_attention_ex_launcher_refuses_chunk_length(L, T, exact):
+    _refused(L, _enc_attention_ex(L, T=T, exact=exact), b"enc_attention_ex: ")
+    assert b"bad arguments" not in L.nd_last_error()
+
+
 # ----------------------------------------------------------------- output head and search entries
 def _state(null=None):
     """An nd_beam_state whose members all point at one small host array (never read by a refused call)."""
