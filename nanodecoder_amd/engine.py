@@ -735,7 +735,7 @@ def op_pack_p16h(W: torch.Tensor):
 
 
 def op_enc_ffn(y, W1, b1, W2, b2, ln_g, ln_b, att=None, Wo=None, bo=None, inplace=False, Wq=None, bq=None,
-               lnq_g=None, lnq_b=None):
+               lnq_g=None, lnq_b=None, x=None, part=None, qkv=None):
     """The encoder's fused FFN block (nd_op_enc_ffn): x = y + W2 relu(W1
     LN(y) + b1) + b2 for row-major y [M, 256], the LN affine folded and both
     weights packed to P16H images here as the engine does at load time.
@@ -744,22 +744,31 @@ def op_enc_ffn(y, W1, b1, W2, b2, ln_g, ln_b, att=None, Wo=None, bo=None, inplac
     inplace: x is written over y, as the engine does.  With Wq, bq, lnq_g,
     lnq_b too the next layer's projection LN(x) Wq^T + bq is computed in the
     same launch and returned as a fourth value.
+    x ([>= M, 256]), part ([>= M, 16, 2]), qkv ([>= M, 768]): written as they are given (rows past M and the
+    part slots past the first keep what they held); allocated here when None.
     Returns (x, row stats [M, 2] = {mean, M2}, overflow flag[, qkv])."""
     M, F = y.shape[0], W1.shape[0]
+    if inplace and x is not None:
+        raise ValueError("op_enc_ffn: inplace writes x over y; no x to give")
     W1f, b1f = op_fold_layernorm(W1, b1, ln_g, ln_b)
     w1h, w1s = op_pack_p16h(W1f)
     w2h, w2s = op_pack_p16h(W2)
-    x = y if inplace else torch.empty_like(y)
-    part = torch.zeros(M, 16, 2, dtype=torch.float32, device=y.device)
+    if x is None:
+        x = y if inplace else torch.empty_like(y)
+    if part is None:
+        part = torch.zeros(M, 16, 2, dtype=torch.float32, device=y.device)
     ov = torch.zeros(1, dtype=torch.int32, device=y.device)
     s = ctypes.c_void_p(torch.cuda.current_stream(y.device).cuda_stream)
     if Wo is not None:
         woh, wos = op_pack_p16h(Wo)
-        qh, qs, qb, qkv = None, 1.0, None, None
+        qh, qs, qb = None, 1.0, None
         if Wq is not None:
             Wqf, qb = op_fold_layernorm(Wq, bq, lnq_g, lnq_b)
             qh, qs = op_pack_p16h(Wqf)
-            qkv = torch.empty(M, Wq.shape[0], dtype=torch.float32, device=y.device)
+            if qkv is None:
+                qkv = torch.empty(M, Wq.shape[0], dtype=torch.float32, device=y.device)
+        else:
+            qkv = None
         _lib.check(_lib.lib().nd_op_enc_ffn_wo(_ptr(att), _ptr(y), _ptr(woh), wos, _ptr(bo), _ptr(w1h), w1s,
                                                _ptr(b1f), _ptr(w2h), w2s, _ptr(b2), _ptr(x), _ptr(part),
                                                _ptr(qh) if qh is not None else None, qs,
@@ -767,26 +776,31 @@ def op_enc_ffn(y, W1, b1, W2, b2, ln_g, ln_b, att=None, Wo=None, bo=None, inplac
                                                _ptr(qkv) if qkv is not None else None, M, F, _ptr(ov), s),
                    "nd_op_enc_ffn_wo")
         if qkv is not None:
-            return x, part[:, 0, :], ov, qkv
+            return x, part[:M, 0, :], ov, qkv
     else:
         _lib.check(_lib.lib().nd_op_enc_ffn(_ptr(y), _ptr(w1h), w1s, _ptr(b1f), _ptr(w2h), w2s, _ptr(b2), _ptr(x),
                                             _ptr(part), M, F, _ptr(ov), s), "nd_op_enc_ffn")
-    return x, part[:, 0, :], ov
+    return x, part[:M, 0, :], ov
 
 
-def op_dec_ffn(yp, W1, b1, W2, b2, ln_g, ln_b, nsplit, skip=None, skip_rpc=1, tickets=None, slab=None):
+def op_dec_ffn(yp, W1, b1, W2, b2, ln_g, ln_b, nsplit, skip=None, skip_rpc=1, tickets=None, slab=None, x=None,
+               part=None):
     """The beam decoder's fused FFN block (nd_op_dec_ffn) on P16-packed rows
     yp [M16, 256] (M16 % 16 == 0): x = y + W2 relu(W1 LN(y) + b1) + b2 with d_ff
     split over nsplit workgroups per 128-row block.  Weights folded / packed
     here as the engine does at load time.  Returns (x packed, row stats
     [M16, 2] = {mean, M2}, overflow flag, tickets) -- pass the tickets back
-    to reuse them (zero between launches)."""
+    to reuse them (zero between launches).  x ([>= M16, 256], P16) and part ([>= M16, 16, 2]): written as they
+    are given (rows past M16, dead row blocks and the part slots past the first keep what they held); when
+    None, x is allocated filled with NaN and part with zeros."""
     M, F = yp.shape[0], W1.shape[0]
     W1f, b1f = op_fold_layernorm(W1, b1, ln_g, ln_b)
     w1h, w1s = op_pack_p16h(W1f)
     w2h, w2s = op_pack_p16h(W2)
-    x = torch.full_like(yp, float("nan"))
-    part = torch.zeros(M, 16, 2, dtype=torch.float32, device=yp.device)
+    if x is None:
+        x = torch.full_like(yp, float("nan"))
+    if part is None:
+        part = torch.zeros(M, 16, 2, dtype=torch.float32, device=yp.device)
     ov = torch.zeros(1, dtype=torch.int32, device=yp.device)
     if tickets is None:
         tickets = torch.zeros((M + 127) // 128, dtype=torch.int32, device=yp.device)
@@ -797,7 +811,7 @@ def op_dec_ffn(yp, W1, b1, W2, b2, ln_g, ln_b, nsplit, skip=None, skip_rpc=1, ti
     _lib.check(_lib.lib().nd_op_dec_ffn(_ptr(yp), _ptr(w1h), w1s, _ptr(b1f), _ptr(w2h), w2s, _ptr(b2), _ptr(x),
                                         _ptr(part), M, F, nsplit, _ptr(slab), _ptr(tickets), _ptr(skip), skip_rpc,
                                         _ptr(ov), s), "nd_op_dec_ffn")
-    return x, part[:, 0, :], ov, tickets
+    return x, part[:M, 0, :], ov, tickets
 
 
 def op_gemm_p16(Ap, Wp, bias, M, N, K, Rp=None, part_in=None, relu=False, part_out=None, Wh=None, wscale=1.0,

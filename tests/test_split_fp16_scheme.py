@@ -19,6 +19,17 @@ error sits below that for |x| ~ 1 (the LayerNorm'd operands are split after
 the normalisation, before the affine folded into W: rows of scale ~1 whatever
 gamma is).  tests/test_gpu_parity.py::test_gemm_split_small_rows_follow_the_scheme
 holds the GPU kernel to this restatement (fp16 subnormals preserved, not flushed).
+
+That is a statement about the split alone; it is silent on the accumulation.
+Where the residual is the accumulator's initial value (ffn.hip: (y + b2) 2^s,
+and (x + bo) 2^s_o under the Wo fold) it is not rounded once, as in x + f(.),
+but at every MFMA term added to it: 3 d_ff / 32 times, 24 more under the Wo
+fold.  That loss is above the split error and above plain fp32: a random walk
+of half-ulp roundings of |x|, about 4 E32 in the numpy model at d_ff 2048 and
+unit scale and about 10 E32 when the residual stream is 64 times the FFN's
+contribution, 7.6-16 and 15-26 E32 on an MI355X (the MFMA rounds more than
+once per term).  tests/test_ffn_scheme.py models and bounds it,
+tests/test_gpu_ffn.py holds the kernel to the bound; DESIGN.md section 5.
 """
 import numpy as np
 
