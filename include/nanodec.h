@@ -569,6 +569,74 @@ int nd_align_fit(const uint8_t* d_call_or, const int32_t* d_call_off, const uint
                  const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span, uint8_t* d_ops,
                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream);
 
+/* Consensus of the mapped reads: the alignment above with the reference
+ * position of every call base kept (nd_align_fit_pos), the pile of all pairs on
+ * the reference (nd_pileup_add), and the call of a consensus base per position
+ * (nd_pileup_call).  The reference evaluates its consensus outside its own code
+ * (scripts/analysis.sh); no reference equivalent.  No context needed.  Integers
+ * throughout: the results do not depend on the grid, the order of the pairs or
+ * the stream, and equal the host rule of nanodecoder_amd/accuracy.py
+ * (fit_pos_host, pile_add_host, consensus_host).
+ *
+ * nd_align_fit_pos is nd_align_fit with one more output; every other output is
+ * bit for bit nd_align_fit's.
+ *   d_rpos    [d_call_off[P]] i32, laid out like d_ops: for oriented call base
+ *             i the position in d_ref it sits on.  A diagonal step at cell
+ *             (i + 1, j): w0 + j - 1, the base it is matched or mismatched to;
+ *             an up step (an insertion) at column j: w0 + j - 1, the base to
+ *             its left, w0 - 1 on the column-0 border; -1 for every base of a
+ *             pair whose d_status[p] != 0
+ * The deleted reference bases are the positions of the span that no diagonal
+ * step took; they lie strictly between two diagonal steps of the pair.
+ * nd_align_fit_pos_work_bytes equals nd_align_fit_work_bytes; statuses and
+ * argument errors are nd_align_fit's, and a null d_rpos is ND_ERR_ARG.
+ *
+ * nd_pileup_add.  d_pile [9, ref_len] u32, plane by plane: A, C, G, T, D, iA,
+ * iC, iG, iT.  A base with op 0 or 1 is a diagonal base.  Every pair with
+ * d_status[p] == 0 adds:
+ *   a diagonal base: +1 in the plane of its code at its rpos; a call byte other
+ *     than A, C, G, T adds nothing;
+ *   deleted positions: +1 in D at every position strictly between the rpos of
+ *     two consecutive diagonal bases of the pair;
+ *   an insertion run with a diagonal base of the pair on both sides: +1 in the
+ *     i plane of the run's first base (if it is A, C, G or T), at the rpos of
+ *     the diagonal base before it.  Leading and trailing insertions are not
+ *     piled, and a longer insertion is named by its first base only.
+ * A position outside [0, ref_len) is skipped wherever it would add.  The table
+ * accumulates over calls; the caller zeroes it once.  One thread per call base,
+ * unsigned integer atomics, one launch on `stream`: no allocation, no
+ * synchronisation.  P == 0 or ref_len == 0 returns ND_OK at once; a negative P
+ * or ref_len or a null buffer return ND_ERR_ARG before any HIP call.
+ *
+ * nd_pileup_call.  At position r, cov = A + C + G + T + D.
+ *   d_cons    [ref_len] u8: 255 when cov < min_cov (uncalled); otherwise the
+ *             index 0..4 (4 = deleted) of the largest of the five counts, the
+ *             lowest index on a tie
+ *   d_ins     [ref_len] u8: when r is called and 2 (iA + iC + iG + iT) > cov,
+ *             the index 0..3 of the largest of the four i counts, the lowest on
+ *             a tie: an inserted base after r; otherwise 255
+ *   d_cov     [ref_len] i32: cov
+ *   d_rec     [R, 6] i64, zeroed by the call itself: per record of d_rec_off
+ *             [R + 1] the sums over its positions {called, match, sub, del,
+ *             ins, cov_sum}: match = cons is the code of d_ref[r]; sub = cons <
+ *             4 and is not (a reference byte other than A, C, G, T counts as
+ *             sub); del = cons == 4; ins = the called insertions; cov_sum = cov
+ *             over the called positions
+ * Consensus identity is match / (match + sub + del + ins).  A memset and one
+ * launch on `stream`: sums per workgroup first, then one 64-bit atomic per
+ * workgroup, record touched and sum; no allocation, no synchronisation.  R == 0
+ * or ref_len == 0 returns ND_OK at once; min_cov < 1, a negative size or a null
+ * buffer return ND_ERR_ARG before any HIP call. */
+int64_t nd_align_fit_pos_work_bytes(int32_t P, int64_t cells);
+int nd_align_fit_pos(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ref, int32_t ref_len,
+                     const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span,
+                     uint8_t* d_ops, int32_t* d_rpos, int32_t* d_status, void* d_work, int64_t work_bytes,
+                     void* stream);
+int nd_pileup_add(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ops, const int32_t* d_rpos,
+                  const int32_t* d_status, int32_t P, uint32_t* d_pile, int32_t ref_len, void* stream);
+int nd_pileup_call(const uint32_t* d_pile, const uint8_t* d_ref, int32_t ref_len, const int32_t* d_rec_off, int32_t R,
+                   int32_t min_cov, uint8_t* d_cons, uint8_t* d_ins, int32_t* d_cov, int64_t* d_rec, void* stream);
+
 /* Encoder forward only; writes the memory bank [B, T, d_model] (rows
  * t >= span are unspecified).  Replaces Translator._run_encoder
  * (translate/translator.py:542-559).  Used by parity tests. */

@@ -93,6 +93,10 @@ SIGNATURES = {
     "nd_locate_segs": (_I, [_P, _P, _I, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "nd_align_fit_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
     "nd_align_fit": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "nd_align_fit_pos_work_bytes": (ctypes.c_int64, [_I, ctypes.c_int64]),
+    "nd_align_fit_pos": (_I, [_P, _P, _P, _I, _P, _I, ctypes.c_int64, _P, _P, _P, _P, _P, _P, ctypes.c_int64, _P]),
+    "nd_pileup_add": (_I, [_P, _P, _P, _P, _P, _I, _P, _I, _P]),
+    "nd_pileup_call": (_I, [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P]),
     "nd_encode": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
     "nd_set_graphs": (_I, [_P, _I]),
     "nd_set_timing": (_I, [_P, _I]),

@@ -456,9 +456,22 @@ def fit_host(call, window):
     """(counts int32 [5], (t_start, t_end), ops uint8 [n]) of a call against a window by the fit rule: numpy over
     the rows (D[i][j] = j + the running minimum of min(diagonal, up)[k] - k), one direction byte per cell, then
     the traceback."""
+    return _fit(call, window, 0)[:3]
+
+
+def fit_pos_host(call, window, w0=0):
+    """fit_host plus rpos int32 [n], the reference position of every call base for a window that starts at ``w0``
+    of the reference: a diagonal step at cell (i + 1, j) gives w0 + j - 1 (the base matched or mismatched to), an
+    up step at column j the same (the base to the left of the inserted one; w0 - 1 on the column-0 border).  The
+    rule of nd_align_fit_pos."""
+    return _fit(call, window, w0)
+
+
+def _fit(call, window, w0):
     a, b = _bytes(call), _bytes(window)
     n, m = int(a.size), int(b.size)
     ops = np.zeros(n, np.uint8)
+    rpos = np.full(n, int(w0) - 1, np.int32)
     dirs = np.zeros((n, m), np.uint8)  # cell (i, j) at [i - 1, j - 1]: 0 diagonal, 1 up, 2 left
     prev = np.zeros(m + 1, np.int32)   # D[0][j] = 0
     ramp = np.arange(m + 1, dtype=np.int32)
@@ -480,6 +493,8 @@ def fit_host(call, window):
             n_ins += i
             break
         d = dirs[i - 1, j - 1]
+        if d != 2:
+            rpos[i - 1] = w0 + j - 1
         if d == 0:
             if a[i - 1] != b[j - 1]:
                 ops[i - 1] = OP_SUB
@@ -495,14 +510,15 @@ def fit_host(call, window):
         else:
             n_del += 1
             j -= 1
-    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), (j, jstar), ops
+    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), (j, jstar), ops, rpos
 
 
-def map_host(call, ref):
+def map_host(call, ref, pile=None):
     """(counts int32 [5], segment records, ops uint8 [n]) of one call: its segments located and fitted on the
     host.  A segment record is (seg_start, seg_end, strand, rec, ref_start, ref_end, votes, counts) with the
     reference interval in the concatenation's coordinates; only mapped segments have one.  ops is per base of the
-    call as written (a strand-1 segment's reversed back), OP_UNMAPPED in an unmapped segment."""
+    call as written (a strand-1 segment's reversed back), OP_UNMAPPED in an unmapped segment.  ``pile`` (a
+    [9, total] uint32 table, Pileup) takes every mapped segment by pile_add_host."""
     a = _bytes(call)
     total, recs, ops = np.zeros(5, np.int32), [], np.full(a.size, OP_UNMAPPED, np.uint8)
     for s0, s1 in segments(a.size):
@@ -510,17 +526,20 @@ def map_host(call, ref):
         if not mapped:
             continue
         oriented = a[s0:s1] if strand == 0 else reverse_complement(a[s0:s1])
-        counts, (t0, t1), o = fit_host(oriented, ref.seq[w0:w1])
+        counts, (t0, t1), o, rpos = _fit(oriented, ref.seq[w0:w1], w0)
+        if pile is not None:
+            pile_add_host(pile, oriented, o, rpos)
         ops[s0:s1] = o if strand == 0 else o[::-1]
         total += counts
         recs.append((s0, s1, strand, ref.record_of(w0), w0 + t0, w0 + t1, votes, counts))
     return total, recs, ops
 
 
-def _map_device(call, seg_off, ref, device, want_ops):
+def _map_device(call, seg_off, ref, device, want_ops, pile=None):
     """nd_locate_segs, then nd_align_fit, on the CURRENT stream of ``device`` with no host round trip in between:
     (hit int32 [P, 4], status int32 [P], counts int32 [P, 5], span int32 [P, 2], oriented ops uint8 [bytes] or
-    None) on the host."""
+    None) on the host.  With ``pile`` (a Pileup's table on that device) the fit is nd_align_fit_pos and
+    nd_pileup_add follows it on the same stream."""
     import ctypes
 
     import torch
@@ -543,16 +562,25 @@ def _map_device(call, seg_off, ref, device, want_ops):
             call_d[: call.size].copy_(_pinned(call), non_blocking=True)
         or_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
         out_d = torch.zeros(P * 12, dtype=torch.int32, device=dev)  # hit [P, 4], status [P], counts [P, 5], span [P, 2]
-        ops_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev) if want_ops else None
+        ops_d = (torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
+                 if want_ops or pile is not None else None)
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
         stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         hit_d, status_d, counts_d, span_d = out_d, out_d[4 * P:], out_d[5 * P:], out_d[10 * P:]
         _lib.check(L.nd_locate_segs(p(call_d), p(off_d), P, p(code_d), p(pos_d), int(code_d.numel()), p(rec_d),
                                     int(rec_d.numel()) - 1, p(hit_d), p(status_d), p(or_d), stream), "nd_locate_segs")
-        _lib.check(L.nd_align_fit(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d), p(span_d),
-                                  p(ops_d) if want_ops else None, p(status_d), p(work_d), work_bytes, stream),
-                   "nd_align_fit")
+        if pile is None:
+            _lib.check(L.nd_align_fit(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d),
+                                      p(span_d), p(ops_d) if want_ops else None, p(status_d), p(work_d), work_bytes,
+                                      stream), "nd_align_fit")
+        else:
+            rpos_d = torch.empty(call.size + 1, dtype=torch.int32, device=dev)
+            _lib.check(L.nd_align_fit_pos(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d),
+                                          p(span_d), p(ops_d), p(rpos_d), p(status_d), p(work_d), work_bytes, stream),
+                       "nd_align_fit_pos")
+            _lib.check(L.nd_pileup_add(p(or_d), p(off_d), p(ops_d), p(rpos_d), p(status_d), P, p(pile), ref.total,
+                                       stream), "nd_pileup_add")
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         ops = ops_d.cpu().numpy()[: call.size] if want_ops else None
     return (out[: 4 * P].reshape(P, 4).copy(), out[4 * P: 5 * P].copy(), out[5 * P: 10 * P].reshape(P, 5).copy(),
@@ -565,9 +593,14 @@ def map_reads(calls, ref, device=None, want_ops=False, stats=None):
     Otherwise all segments of all reads are one nd_locate_segs call and one nd_align_fit call on the current torch
     stream of ``device``: a read of any length runs there.  ``stats`` (a dict) gets "reads", "segments" and
     "unmapped" (segments) increased."""
+    return _map_reads(calls, ref, device, want_ops, stats, None)
+
+
+def _map_reads(calls, ref, device, want_ops, stats, pile):
+    """map_reads; ``pile``, a Pileup's table (on the host or on ``device``), takes every mapped segment."""
     calls = [_bytes(c) for c in calls]
     if device is None:
-        res = [map_host(c, ref) for c in calls]
+        res = [map_host(c, ref, pile) for c in calls]
     else:
         segs = [segments(c.size) for c in calls]
         seg_off = np.zeros(sum(len(s) for s in segs) + 1, np.int64)
@@ -582,7 +615,8 @@ def map_reads(calls, ref, device=None, want_ops=False, stats=None):
         res = []
         if calls:
             flat = np.concatenate(calls) if base else np.zeros(0, np.uint8)
-            hit, status, counts, span, ops_or = _map_device(flat, seg_off.astype(np.int32), ref, device, want_ops)
+            hit, status, counts, span, ops_or = _map_device(flat, seg_off.astype(np.int32), ref, device, want_ops,
+                                                            pile)
             if (status & ~MAP_STATUS_UNMAPPED).any():
                 raise RuntimeError("nd_align_fit status %s" % sorted(set(status.tolist())))
             k = 0
@@ -618,3 +652,205 @@ def paf_line(name, n_called, rec, ref):
     return "%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tvt:i:%d\n" % (
         name, n_called, s0, s1, "-" if strand else "+", ref.names[r], int(ref.rec_off[r + 1]) - base, t0 - base,
         t1 - base, c[1], c[1] + c[2] + c[3] + c[4], votes)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Consensus accuracy (-consensus under -truth_ref): the mapped reads of the whole run piled up on the reference,
+# a consensus base called per position, and what differs from the reference.  Integer rules, on the host
+# (fit_pos_host, pile_add_host, consensus_host) or on the device (nd_align_fit_pos, csrc/align.hip; nd_pileup_add,
+# nd_pileup_call, csrc/pileup.hip) with the same integers.
+#
+# positions : rpos[i] of every oriented call base of a fitted pair (fit_pos_host): the reference base a diagonal
+#             step matches or mismatches it to; for an inserted base the reference base to its left.
+# pile      : [9, total] uint32, planes A, C, G, T, D, iA, iC, iG, iT.  Per mapped segment: a diagonal base (op 0
+#             or 1) +1 in the plane of its code at its rpos (a byte other than A, C, G, T adds nothing); +1 in D at
+#             every position strictly between the rpos of two consecutive diagonal bases; for an insertion run
+#             between two diagonal bases +1 in the i plane of the run's first base at the rpos of the diagonal base
+#             before it.  Leading and trailing insertions are not piled; a longer insertion is named by its first
+#             base only; a position outside [0, total) is skipped wherever it would add.
+# call      : cov = A + C + G + T + D; below min_cov: cons = ins = 255 (uncalled); else cons = the index 0..4 (4 =
+#             deleted) of the largest of the five, the lowest on a tie, and ins = the index of the largest of the
+#             four i counts (the lowest on a tie) when 2 (iA + iC + iG + iT) > cov, else 255.
+# records   : {called, match, sub, del, ins, cov_sum} int64 per reference record: match = cons is the reference
+#             base's code, sub = cons < 4 and is not (a reference byte other than A, C, G, T counts here), del =
+#             cons == 4, ins = the called insertions, cov_sum = cov over the called positions.
+# identity  : match / (match + sub + del + ins), per record and pooled (identity above, with dist unused).
+PILE_PLANES = 9
+PILE_DEL = 4
+PILE_INS = 5
+CONS_NONE = 255
+_LETTERS = np.frombuffer(b"ACGT", np.uint8)
+
+
+def pile_add_host(pile, call, ops, rpos):
+    """One fitted pair (status 0) added to ``pile`` ([9, total] uint32, in place) by the rule above: ``call`` the
+    oriented bytes, ``ops`` and ``rpos`` as fit_pos_host gives them.  The rule of nd_pileup_add."""
+    a = _bytes(call)
+    ops = np.asarray(ops, np.uint8).reshape(-1)
+    rpos = np.asarray(rpos, np.int64).reshape(-1)
+    total = pile.shape[1]
+    diag = np.flatnonzero(ops <= OP_SUB)
+    if diag.size == 0:
+        return
+    r = rpos[diag]
+    inside = (r >= 0) & (r < total)
+    code = _CODE[a[diag]]
+    ok = inside & (code < 4)
+    np.add.at(pile, (code[ok], r[ok]), 1)
+    # consecutive diagonal bases k < i with nothing but insertions in between
+    k, i = diag[:-1], diag[1:]
+    n_ins = np.concatenate([[0], np.cumsum(ops == OP_INS)])
+    pair = n_ins[i] - n_ins[k + 1] == i - k - 1
+    k, i, rk, ri, rk_inside = k[pair], i[pair], r[:-1][pair], r[1:][pair], inside[:-1][pair]
+    lo = np.clip(rk + 1, 0, total)
+    hi = np.maximum(np.clip(ri, 0, total), lo)
+    step = np.zeros(total + 1, np.int64)
+    np.add.at(step, lo, 1)
+    np.add.at(step, hi, -1)
+    pile[PILE_DEL] += np.cumsum(step[:-1]).astype(np.uint32)
+    run = i - k > 1
+    first = _CODE[a[np.minimum(k + 1, a.size - 1)]]
+    ok = run & rk_inside & (first < 4)
+    np.add.at(pile, (PILE_INS + first[ok].astype(np.int64), rk[ok]), 1)
+
+
+def _record_sums(ref, cons, ins, cov):
+    """rec int64 [R, 6] = {called, match, sub, del, ins, cov_sum} of the rule above."""
+    called = cons != CONS_NONE
+    match = called & (cons == _CODE[ref.seq])
+    dele = cons == PILE_DEL
+    cols = [called, match, called & ~match & ~dele, dele, ins != CONS_NONE]
+    sums = [np.concatenate([[0], np.cumsum(c, dtype=np.int64)]) for c in cols]
+    sums.append(np.concatenate([[0], np.cumsum(np.where(called, cov, 0), dtype=np.int64)]))
+    off = ref.rec_off.astype(np.int64)
+    return np.stack([c[off[1:]] - c[off[:-1]] for c in sums], axis=1).reshape(len(off) - 1, 6)
+
+
+def consensus_host(pile, ref, min_cov):
+    """(cons uint8 [total], ins uint8 [total], cov int32 [total], rec int64 [R, 6]) of a pile by the rule above.
+    The rule of nd_pileup_call."""
+    if min_cov < 1:
+        raise ValueError("min_cov must be at least 1")
+    t = np.asarray(pile).astype(np.int64)
+    cov = t[:PILE_INS].sum(axis=0)
+    called = cov >= min_cov
+    cons = np.where(called, np.argmax(t[:PILE_INS], axis=0), CONS_NONE).astype(np.uint8)  # argmax: the lowest index
+    has = called & (2 * t[PILE_INS:].sum(axis=0) > cov)
+    ins = np.where(has, np.argmax(t[PILE_INS:], axis=0), CONS_NONE).astype(np.uint8)
+    return cons, ins, cov.astype(np.int32), _record_sums(ref, cons, ins, cov)  # cov_sum from the 64-bit cov
+
+
+class Pileup:
+    """The pile of a whole run on ``ref``.  ``device=None`` keeps the table on the host and uses the host rule;
+    otherwise the table is a tensor on ``device`` for the life of the object and every add is nd_locate_segs,
+    nd_align_fit_pos and nd_pileup_add on the current torch stream, with no host round trip beyond map_reads' own."""
+
+    def __init__(self, ref, device=None):
+        self.ref, self.device = ref, device
+        if device is None:
+            self._pile = np.zeros((PILE_PLANES, ref.total), np.uint32)
+        else:
+            import torch
+            self._dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+            self._pile = torch.zeros(PILE_PLANES * ref.total + 1, dtype=torch.int32, device=self._dev)
+
+    def add(self, calls, want_ops=False, stats=None):
+        """map_reads(calls, ref, device, want_ops, stats), its results, with every mapped segment piled."""
+        return _map_reads(calls, self.ref, self.device, want_ops, stats, self._pile)
+
+    def counts(self):
+        """The table as a [9, total] uint32 numpy array (a copy)."""
+        if self.device is None:
+            return self._pile.copy()
+        return self._pile[:-1].cpu().numpy().view(np.uint32).reshape(PILE_PLANES, self.ref.total)
+
+    def call(self, min_cov):
+        """(cons, ins, cov, rec) as consensus_host gives them: on a device by nd_pileup_call."""
+        if min_cov < 1:
+            raise ValueError("min_cov must be at least 1")
+        if self.device is None:
+            return consensus_host(self._pile, self.ref, min_cov)
+        import ctypes
+
+        import torch
+
+        from . import _lib
+        total, R = self.ref.total, len(self.ref.names)
+        with torch.cuda.device(self._dev):
+            seq_d, rec_off_d = self.ref.on_device(self._dev)[:2]
+            cc_d = torch.full((2 * total + 1,), CONS_NONE, dtype=torch.uint8, device=self._dev)  # cons, ins
+            cov_d = torch.zeros(total + 1, dtype=torch.int32, device=self._dev)
+            rec_d = torch.zeros(R * 6 + 1, dtype=torch.int64, device=self._dev)
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
+            p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+            _lib.check(_lib.lib().nd_pileup_call(p(self._pile), p(seq_d), total, p(rec_off_d), R, int(min_cov),
+                                                 p(cc_d), p(cc_d[total:]), p(cov_d), p(rec_d), stream),
+                       "nd_pileup_call")
+            cc, cov, rec = cc_d.cpu().numpy(), cov_d.cpu().numpy(), rec_d.cpu().numpy()
+        return cc[:total].copy(), cc[total: 2 * total].copy(), cov[:total].copy(), rec[: R * 6].reshape(R, 6).copy()
+
+
+def _ratio(match, sub, dele, ins):
+    den = int(match) + int(sub) + int(dele) + int(ins)
+    return int(match) / den if den else 0.0
+
+
+def consensus_fasta(ref, cons, ins):
+    """The text of consensus.fasta: one record per reference record that has a called position, ``>NAME called=N
+    identity=F``; the sequence covers the whole record, N where uncalled, deleted positions left out, a called
+    insertion after its position."""
+    rec = _record_sums(ref, cons, ins, np.zeros(cons.size, np.int32))
+    base = np.zeros(256, np.uint8)
+    base[:4], base[CONS_NONE] = _LETTERS, ord("N")
+    after = np.zeros(256, np.uint8)
+    after[:4] = _LETTERS
+    both = np.stack([base[cons], after[ins]], axis=1)
+    out = []
+    for r, name in enumerate(ref.names):
+        if rec[r, 0] == 0:
+            continue
+        part = both[int(ref.rec_off[r]): int(ref.rec_off[r + 1])].reshape(-1)
+        out.append(">%s called=%d identity=%.6f\n%s\n" % (name, rec[r, 0], _ratio(*rec[r, 1:5]),
+                                                         part[part != 0].tobytes().decode("ascii")))
+    return "".join(out)
+
+
+def variant_lines(ref, cons, ins, cov, pile):
+    """The lines of variants.tsv, in reference order: ``record, pos (1-based), ref, alt, cov, count`` for every
+    called position whose consensus differs from the reference (a substitution ``A G``, a deletion ``A -``) and,
+    after the position's own line, for a called insertion after it (``- G``).  count is the winning count of
+    ``pile`` (Pileup.counts)."""
+    differs = (cons != CONS_NONE) & ((cons != _CODE[ref.seq]) | (ins != CONS_NONE))
+    out = []
+    for r in np.flatnonzero(differs):
+        k = ref.record_of(r)
+        name, pos = ref.names[k], int(r) - int(ref.rec_off[k]) + 1
+        c = int(cons[r])
+        if c != _CODE[ref.seq[r]]:
+            out.append("%s\t%d\t%s\t%s\t%d\t%d\n" % (name, pos, chr(ref.seq[r]), "ACGT-"[c], cov[r], pile[c, r]))
+        if ins[r] != CONS_NONE:
+            out.append("%s\t%d\t-\t%s\t%d\t%d\n" % (name, pos, "ACGT"[int(ins[r])], cov[r],
+                                                      pile[PILE_INS + int(ins[r]), r]))
+    return out
+
+
+def coverage_lines(ref, rec):
+    """The lines of coverage.tsv: ``record, length, called, mean_cov (cov_sum / called, %.2f), match, sub, del,
+    ins, identity (%.6f)`` per reference record, and a last line ``total``."""
+    def line(name, length, v):
+        v = [int(x) for x in v]
+        return "%s\t%d\t%d\t%.2f\t%d\t%d\t%d\t%d\t%.6f\n" % (name, length, v[0], v[5] / v[0] if v[0] else 0.0,
+                                                               v[1], v[2], v[3], v[4], _ratio(*v[1:5]))
+    out = [line(name, int(ref.rec_off[r + 1]) - int(ref.rec_off[r]), rec[r]) for r, name in enumerate(ref.names)]
+    out.append(line("total", ref.total, np.asarray(rec, np.int64).reshape(-1, 6).sum(axis=0)))
+    return out
+
+
+def consensus_summary(ref, rec, min_cov, n_variants):
+    """The log's line of -consensus: the reference bases called, the mean coverage, the pooled consensus identity
+    with its four counts, and the number of variant lines."""
+    v = [int(x) for x in np.asarray(rec, np.int64).reshape(-1, 6).sum(axis=0)]
+    return ("-consensus: %d of %d reference bases called at coverage >= %d, mean coverage %.2f; consensus identity "
+            "%.6f (%d matches, %d substitutions, %d deletions, %d insertions); %d variant lines"
+            % (v[0], ref.total, min_cov, v[5] / v[0] if v[0] else 0.0, _ratio(*v[1:5]), v[1], v[2], v[3], v[4],
+               n_variants))

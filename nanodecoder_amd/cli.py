@@ -11,7 +11,9 @@ on (translate.py:97-98).  ``-pack_reads N`` translates N reads per engine pass.
 ``-truth FILE`` aligns every read that has a known sequence in FILE to it and
 writes save_data/accuracy.tsv (with ``-fastq`` quality_calibration.tsv too).
 ``-truth_ref FILE`` maps every read to a shared reference instead (segments of
-at most 4096 bases, either strand) and also writes save_data/mapping.paf.
+at most 4096 bases, either strand) and also writes save_data/mapping.paf;
+with ``-consensus`` the mapped segments are piled up on the reference and the
+run ends with save_data/consensus.fasta, variants.tsv and coverage.tsv.
 """
 from __future__ import annotations
 
@@ -176,9 +178,10 @@ ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled /
 ALIGN_STATS = {"reads": 0, "fallback": 0}     # -truth: reads aligned / of them on the host after a device status
 # -truth, this run: the known sequences (None without the flag), the reads written with and without one, the sums
 # of matches and alignment lengths, and with -fastq the called bases and errors per predicted quality
-# (-truth_ref: "ref" the shared reference, "missing" the reads written without a mapped segment)
+# (-truth_ref: "ref" the shared reference, "missing" the reads written without a mapped segment; -consensus: "pile"
+# the run's accuracy.Pileup)
 TRUTH = {"seqs": None, "ref": None, "evaluated": 0, "missing": 0, "match": 0, "length": 0, "bases": None,
-         "errors": None}
+         "errors": None, "pile": None}
 MAP_STATS = {"reads": 0, "segments": 0, "unmapped": 0}  # -truth_ref, written reads: their segments, those unmapped
 
 
@@ -211,7 +214,10 @@ def _evaluate_group_ref(opt, names, seqs, fastq):
     called = [accuracy.normalise(text(seqs[k])) for k in todo]
     device = None if getattr(opt, "truth_align", "gpu") == "cpu" else max(0, opt.gpu)
     try:
-        counts, recs, ops = accuracy.map_reads(called, ref, device=device, want_ops=fastq)
+        if TRUTH["pile"] is not None:  # -consensus: the same mapping, its segments piled as they are aligned
+            counts, recs, ops = TRUTH["pile"].add(called, want_ops=fastq)
+        else:
+            counts, recs, ops = accuracy.map_reads(called, ref, device=device, want_ops=fastq)
     except Exception as e:
         for k in todo:
             print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
@@ -289,6 +295,21 @@ def _account(entry):
         TRUTH["errors"] += e
 
 
+def _write_consensus(opt, logger):
+    """-consensus, at the end of the run: the pile is called and save_data/consensus.fasta, variants.tsv and
+    coverage.tsv are written, with the log's line."""
+    ref, pile, min_cov = TRUTH["ref"], TRUTH["pile"], opt.consensus_min_cov
+    cons, ins, cov, rec = pile.call(min_cov)
+    variants = accuracy.variant_lines(ref, cons, ins, cov, pile.counts())
+    with open(os.path.join(opt.save_data, "consensus.fasta"), "w") as f:
+        f.write(accuracy.consensus_fasta(ref, cons, ins))
+    with open(os.path.join(opt.save_data, "variants.tsv"), "w") as f:
+        f.writelines(variants)
+    with open(os.path.join(opt.save_data, "coverage.tsv"), "w") as f:
+        f.writelines(accuracy.coverage_lines(ref, rec))
+    logger.info(accuracy.consensus_summary(ref, rec, min_cov, len(variants)))
+
+
 def main(opt=None):
     opt = opt or parse_translate_opts()
     if getattr(opt, "fastq", False) and opt.attn_debug:
@@ -303,6 +324,10 @@ def main(opt=None):
         raise ValueError("-truth_ref is not available together with -attn_debug")
     if getattr(opt, "truth_ref", "") and getattr(opt, "truth", ""):
         raise ValueError("-truth_ref and -truth exclude each other")
+    if getattr(opt, "consensus", False) and not getattr(opt, "truth_ref", ""):
+        raise ValueError("-consensus needs -truth_ref")
+    if getattr(opt, "consensus", False) and getattr(opt, "consensus_min_cov", 5) < 1:
+        raise ValueError("-consensus_min_cov must be at least 1")
     logger = init_logger(opt.log_file)
     ASSEMBLY_STATS.update(reads=0, fallback=0)
     ALIGN_STATS.update(reads=0, fallback=0)
@@ -311,7 +336,10 @@ def main(opt=None):
                  ref=accuracy.read_reference(opt.truth_ref) if getattr(opt, "truth_ref", "") else None,
                  evaluated=0, missing=0,
                  match=0, length=0, bases=np.zeros(accuracy.Q_LEVELS, np.int64),
-                 errors=np.zeros(accuracy.Q_LEVELS, np.int64))
+                 errors=np.zeros(accuracy.Q_LEVELS, np.int64), pile=None)
+    if getattr(opt, "consensus", False):
+        TRUTH["pile"] = accuracy.Pileup(TRUTH["ref"], device=None if getattr(opt, "truth_align", "gpu") == "cpu"
+                                        else max(0, opt.gpu))
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
         os.makedirs(os.path.join(opt.save_data, sub), exist_ok=True)
     from .translator import build_translator
@@ -356,6 +384,8 @@ def main(opt=None):
                     % (TRUTH["evaluated"], TRUTH["missing"], MAP_STATS["segments"] - MAP_STATS["unmapped"],
                        MAP_STATS["unmapped"], TRUTH["match"] / TRUTH["length"] if TRUTH["length"] else 0.0,
                        TRUTH["match"], TRUTH["length"]))
+    if TRUTH["pile"] is not None:
+        _write_consensus(opt, logger)
     if TRUTH["seqs"] is not None:
         if getattr(opt, "fastq", False):
             with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:

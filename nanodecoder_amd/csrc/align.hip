@@ -52,6 +52,12 @@
 // threads reduce (D[n][j], j) over j = 0..m (D[n][0] = n, the padded columns j > m left out) to the smallest key.  A pair whose status has bit 0 set on entry (unmapped) is skipped.  The global
 // form's instantiation holds none of this.
 //
+// The pos form (nd_align_fit_pos, POS = true): the fit form with one more output, rpos[i] = the reference position
+// of oriented call base i in ref's coordinates.  The traceback is where j is known: a diagonal step at cell
+// (i + 1, j) and an up step at column j both give w0 + j - 1 (the base matched or mismatched to, and the base to
+// the left of an inserted one), the column-0 border gives w0 - 1, and a pair that is not aligned gives -1.  Only
+// stores next to those of op[]: the other instantiations hold none of it.
+//
 // LDS: 2 x 8208 (sequences) + 16416 (strip row) + 16384 (block rows) + 1024 (window) + 8 = 50,248 bytes static
 // (the fit form: + 4).
 #include <type_traits>
@@ -136,13 +142,14 @@ __device__ __forceinline__ unsigned aln_dir_word(const unsigned* __restrict__ fu
   return (unsigned)(v >> (bit0 & 7)) & ((1u << (2 * r)) - 1u);
 }
 
-template <bool FIT>
+template <bool FIT, bool POS>
 __global__ void __launch_bounds__(ALN_THREADS)
 align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ call_off,
              const unsigned char* __restrict__ truth, const int* __restrict__ truth_off,
              const long long* __restrict__ off, long long capacity, unsigned char* __restrict__ dirs,
              int* __restrict__ counts, unsigned char* __restrict__ ops, int* __restrict__ status,
-             int* __restrict__ span, int ref_len) {
+             int* __restrict__ span, int ref_len, int* __restrict__ rpos) {
+  static_assert(FIT || !POS, "positions belong to the fit form");
   __shared__ __align__(16) unsigned char sa[ALIGN_MAX_LEN + 16], sb[ALIGN_MAX_LEN + 16];
   __shared__ __align__(16) unsigned short srow[ALIGN_MAX_LEN + 16];  // srow[j - 1] = D[the strip's top row][j]
   __shared__ __align__(16) unsigned short sx[2][ALN_THREADS][16];    // [step parity][thread]: its block's bottom row
@@ -154,6 +161,7 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
   int n, ob, m;
   const int dims = aln_dims<FIT>(call_off, truth_off, status, ref_len, p, n, ob, m);
   unsigned char* op = ops ? ops + oa : nullptr;
+  int* rp = POS ? rpos + oa : nullptr;  // the pos form: the reference position of every oriented call base
   int bad = 0;
   if (FIT && dims) bad = dims;
   else if (n < 0 || m < 0 || n > ALIGN_MAX_LEN || m > ALIGN_MAX_LEN) bad = FIT ? 4 : 1;
@@ -164,6 +172,8 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
     if (FIT && tid < 2) span[(size_t)p * 2 + tid] = -1;
     if (op)
       for (int x = tid; x < n; x += ALN_THREADS) op[x] = 0;
+    if constexpr (POS)
+      for (int x = tid; x < n; x += ALN_THREADS) rp[x] = -1;
     return;
   }
   if (tid == 0) status[p] = 0;
@@ -346,11 +356,13 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
           n_sub += sub;
           n_match += 1 - sub;
           if (op) op[i - 1] = (unsigned char)sub;
+          if constexpr (POS) rp[i - 1] = ob + j - 1;  // the reference base it is matched or mismatched to
           --i;
           --j;
         } else if (d == 1u) {
           ++n_ins;
           if (op) op[i - 1] = 2;
+          if constexpr (POS) rp[i - 1] = ob + j - 1;  // the reference base to its left
           --i;
         } else {
           ++n_del;
@@ -364,6 +376,8 @@ align_kernel(const unsigned char* __restrict__ call, const int* __restrict__ cal
   const int ri = s_ij[0], rj = s_ij[1];  // a border: the rest of column 0 is insertions, the rest of row 0 deletions
   if (op)
     for (int x = tid; x < ri; x += ALN_THREADS) op[x] = 2;
+  if constexpr (POS)
+    for (int x = tid; x < ri; x += ALN_THREADS) rp[x] = ob - 1;
   if (tid == 0) {
     n_ins += max(ri, 0);
     if constexpr (FIT) {  // row 0 consumes nothing: the path starts at column rj of the window
@@ -394,15 +408,16 @@ hipError_t launch_align_seqs(const unsigned char* call, const int* call_off, con
   const long long head = 8ll * (P + 1);  // the offsets; the directions follow
   hipLaunchKernelGGL(align_offsets_kernel<false>, dim3(1), dim3(ALN_THREADS), 0, s, call_off, truth_off, P, off,
                      (const int*)nullptr, 0);
-  hipLaunchKernelGGL(align_kernel<false>, dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, truth, truth_off, off,
-                     align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops, status,
-                     (int*)nullptr, 0);
+  hipLaunchKernelGGL((align_kernel<false, false>), dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, truth, truth_off,
+                     off, align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops,
+                     status, (int*)nullptr, 0, (int*)nullptr);
   return hipGetLastError();
 }
 
-hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
-                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                            int* status, void* work, hipStream_t s) {
+// rpos == nullptr: nd_align_fit, the instantiation without positions
+static hipError_t launch_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                             const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                             int* status, void* work, int* rpos, hipStream_t s) {
   if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0 || !call_off ||
       (P > 0 && (!call || !ref || !hit || !counts || !span || !status || !work)))
     return hipErrorInvalidValue;
@@ -411,10 +426,28 @@ hipError_t launch_align_fit(const unsigned char* call, const int* call_off, cons
   const long long head = 8ll * (P + 1);
   hipLaunchKernelGGL(align_offsets_kernel<true>, dim3(1), dim3(ALN_THREADS), 0, s, call_off, hit, P, off,
                      (const int*)status, ref_len);
-  hipLaunchKernelGGL(align_kernel<true>, dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, ref, hit, off,
-                     align_work_bytes(P, cells) - head, static_cast<unsigned char*>(work) + head, counts, ops, status,
-                     span, ref_len);
+  const long long capacity = align_work_bytes(P, cells) - head;
+  unsigned char* dirs = static_cast<unsigned char*>(work) + head;
+  if (rpos)
+    hipLaunchKernelGGL((align_kernel<true, true>), dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, ref, hit, off,
+                       capacity, dirs, counts, ops, status, span, ref_len, rpos);
+  else
+    hipLaunchKernelGGL((align_kernel<true, false>), dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, ref, hit, off,
+                       capacity, dirs, counts, ops, status, span, ref_len, (int*)nullptr);
   return hipGetLastError();
+}
+
+hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                            int* status, void* work, hipStream_t s) {
+  return launch_fit(call, call_off, ref, ref_len, hit, P, cells, counts, span, ops, status, work, nullptr, s);
+}
+
+hipError_t launch_align_fit_pos(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                                const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                                int* status, int* rpos, void* work, hipStream_t s) {
+  if (P > 0 && !rpos) return hipErrorInvalidValue;
+  return launch_fit(call, call_off, ref, ref_len, hit, P, cells, counts, span, ops, status, work, rpos, s);
 }
 
 }  // namespace nd

@@ -483,6 +483,19 @@ hipError_t launch_locate_segs(const unsigned char* call, const int* call_off, in
 hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
                             const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
                             int* status, void* work, hipStream_t s);
+// the fit form with one more output: rpos [call_off[P]] = the reference position of every oriented call base (the
+// base matched or mismatched to; for an inserted base the one to its left), -1 for a pair that is not aligned
+hipError_t launch_align_fit_pos(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                                const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                                int* status, int* rpos, void* work, hipStream_t s);
+// consensus of the mapped reads (pileup.hip states the rule): pile [9, ref_len] u32, planes A, C, G, T, D, iA, iC,
+// iG, iT; add piles the pairs of status 0 by their ops and rpos (one launch), call reads the pile into cons, ins
+// (u8, 255 = none), cov and rec [R, 6] = {called, match, sub, del, ins, cov_sum}, which it zeroes itself
+hipError_t launch_pileup_add(const unsigned char* call, const int* call_off, const unsigned char* ops, const int* rpos,
+                             const int* status, int P, unsigned* pile, int ref_len, hipStream_t s);
+hipError_t launch_pileup_call(const unsigned* pile, const unsigned char* ref, int ref_len, const int* rec_off, int R,
+                              int min_cov, unsigned char* cons, unsigned char* ins, int* cov, long long* rec,
+                              hipStream_t s);
 // average self-attention (aan.hip): xn = LN_1(x), avg = (xn + step prev) / (step + 1)
 // (prev from hist[anc[r][step-1]][step-1], avg stored at hist[r][step]), avg's
 // row statistics (one partial); then q1 = sig(g_in) xn + sig(g_f) a + x (+ stats)

@@ -1,5 +1,5 @@
 // libnanodec_hip.so — the op-level entry points (nd_op_*, nd_normalize_reads, nd_window_reads,
-// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions, nd_align_seqs, nd_locate_segs, nd_align_fit): launches on the caller's stream, with no context.
+// nd_assemble_reads, nd_assemble_reads_q, nd_assemble_reads_m, nd_assemble_reads_p, nd_token_weights, nd_token_mod_weights, nd_token_positions, nd_align_seqs, nd_locate_segs, nd_align_fit, nd_align_fit_pos, nd_pileup_add, nd_pileup_call): launches on the caller's stream, with no context.
 // The nd_op_* calls exist for the op-level tests.
 #include "engine.hpp"
 
@@ -456,6 +456,50 @@ int nd_align_fit(const uint8_t* d_call_or, const int32_t* d_call_off, const uint
   if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_fit: d_work must be 8-byte aligned");
   return status("align_fit", nd::launch_align_fit(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells, d_counts,
                                                   d_span, d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int64_t nd_align_fit_pos_work_bytes(int32_t P, int64_t cells) { return nd_align_seqs_work_bytes(P, cells); }
+
+int nd_align_fit_pos(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ref, int32_t ref_len,
+                     const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span,
+                     uint8_t* d_ops, int32_t* d_rpos, int32_t* d_status, void* d_work, int64_t work_bytes,
+                     void* stream) {
+  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0)
+    return fail(ND_ERR_ARG, "align_fit_pos: P, cells and ref_len must be >= 0 and cells <= 2^60");
+  if (P == 0) return ND_OK;
+  const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
+  if (work_bytes < need)
+    return fail(ND_ERR_ARG, "align_fit_pos: work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_align_fit_pos_work_bytes asks for");
+  if (!d_call_or || !d_call_off || !d_ref || !d_hit || !d_counts || !d_span || !d_rpos || !d_status || !d_work)
+    return fail(ND_ERR_ARG, "align_fit_pos: null buffer");
+  if (reinterpret_cast<uintptr_t>(d_work) & 7)
+    return fail(ND_ERR_ARG, "align_fit_pos: d_work must be 8-byte aligned");
+  return status("align_fit_pos", nd::launch_align_fit_pos(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells,
+                                                          d_counts, d_span, d_ops, d_status, d_rpos, d_work,
+                                                          (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_pileup_add(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ops, const int32_t* d_rpos,
+                  const int32_t* d_status, int32_t P, uint32_t* d_pile, int32_t ref_len, void* stream) {
+  if (P < 0 || ref_len < 0) return fail(ND_ERR_ARG, "pileup_add: P and ref_len must be >= 0");
+  if (P == 0 || ref_len == 0) return ND_OK;
+  if (!d_call_or || !d_call_off || !d_ops || !d_rpos || !d_status || !d_pile)
+    return fail(ND_ERR_ARG, "pileup_add: null buffer");
+  return status("pileup_add", nd::launch_pileup_add(d_call_or, d_call_off, d_ops, d_rpos, d_status, P, d_pile,
+                                                    ref_len, (hipStream_t)stream), ND_ERR_HIP);
+}
+
+int nd_pileup_call(const uint32_t* d_pile, const uint8_t* d_ref, int32_t ref_len, const int32_t* d_rec_off, int32_t R,
+                   int32_t min_cov, uint8_t* d_cons, uint8_t* d_ins, int32_t* d_cov, int64_t* d_rec, void* stream) {
+  if (ref_len < 0 || R < 0 || min_cov < 1)
+    return fail(ND_ERR_ARG, "pileup_call: ref_len and R must be >= 0 and min_cov >= 1");
+  if (R == 0 || ref_len == 0) return ND_OK;
+  if (!d_pile || !d_ref || !d_rec_off || !d_cons || !d_ins || !d_cov || !d_rec)
+    return fail(ND_ERR_ARG, "pileup_call: null buffer");
+  return status("pileup_call", nd::launch_pileup_call(d_pile, d_ref, ref_len, d_rec_off, R, min_cov, d_cons, d_ins,
+                                                      d_cov, reinterpret_cast<long long*>(d_rec),
+                                                      (hipStream_t)stream), ND_ERR_HIP);
 }
 
 int nd_phred_ratios(double* out, int32_t n) {

@@ -110,6 +110,18 @@ def translate_parser() -> argparse.ArgumentParser:
               "summed over its mapped segments) and every mapped segment a line of save_data/mapping.paf (12 PAF "
               "columns and vt:i: = the locate votes); with -fastq, quality_calibration.tsv as with -truth, from the "
               "mapped segments; not together with -truth or -attn_debug")
+    _add(g, "consensus", action="store_true",
+         help="with -truth_ref: pile every mapped segment of the run up on the reference (on the device with "
+              "-truth_align gpu: align.hip, pileup.hip; cpu = the same rule in numpy), call a consensus base per "
+              "position and write save_data/consensus.fasta (N where uncalled, deletions left out, insertions "
+              "added), save_data/variants.tsv (record, pos, ref, alt, cov, count) and save_data/coverage.tsv (per "
+              "record: length, called, mean_cov, match, sub, del, ins, identity; a last line total); the log ends "
+              "with the consensus identity; a group's reads are piled when they are mapped, so a read whose write "
+              "fails later stays in the pile, and reads skipped as already done on a resumed run are not in it; an "
+              "insertion longer than one base is named by its first base; the other outputs are unchanged")
+    _add(g, "consensus_min_cov", type=int, default=5,
+         help="-consensus: the fewest reads (A + C + G + T + deleted) a reference position needs to be called; at "
+              "least 1")
     return p
 
 
