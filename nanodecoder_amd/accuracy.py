@@ -27,7 +27,11 @@ device) and states those rules there.
 """
 from __future__ import annotations
 
+import ctypes
 import math
+import os
+from dataclasses import dataclass, field
+from typing import NamedTuple
 
 import numpy as np
 
@@ -51,49 +55,69 @@ def _bytes(seq) -> np.ndarray:
     return np.frombuffer(bytes(seq), np.uint8)
 
 
-def align_host(call, truth):
-    """(counts int32 [5], ops uint8 [n]) of one pair by the rule above: numpy over the anti-diagonals i + j = d
-    (three of them live at a time), one direction byte per cell, then the traceback.  The host path, the
-    fallback of align_reads and the tests' oracle."""
+class _Device:
+    """What every device call below needs of torch: ``dev`` (``device`` an index, a string or a torch.device),
+    the current stream and a tensor's address as the C entries take them, and the upload of byte arrays."""
+
+    def __init__(self, device):
+        import torch
+        self.dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+    def stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+
+    @staticmethod
+    def ptr(t):
+        return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+    def upload(self, *arrays):
+        """Per uint8 array a zeroed tensor one byte longer (an empty one still has an address) with the bytes
+        copied in from pinned memory on the current stream: all tensors first, then the copies."""
+        import torch
+
+        from .frontend import _pinned
+        out = [torch.zeros(a.size + 1, dtype=torch.uint8, device=self.dev) for a in arrays]
+        for t, a in zip(out, arrays):
+            if a.size:
+                t[: a.size].copy_(_pinned(a), non_blocking=True)
+        return out
+
+
+def _dp(call, truth, free, w0=0):
+    """(counts int32 [5], (t_start, t_end), ops uint8 [n], rpos int32 [n]) of one pair: the recurrence and the
+    direction order of the rule above, global (``free`` False) or with free ends on the truth side (the fit rule
+    below, ``truth`` a window that starts at ``w0`` of the reference).  numpy over the rows (D[i][j] = j + the
+    running minimum of min(diagonal, up)[k] - k), one direction byte per cell, then the traceback.  The two forms
+    differ in row 0 (D[0][j] = j, or 0), in where the path starts ((n, m), or (n, j*)) and in what is left when i
+    reaches 0 at column j (j deletions, or nothing)."""
     a, b = _bytes(call), _bytes(truth)
     n, m = int(a.size), int(b.size)
     ops = np.zeros(n, np.uint8)
-    dirs = np.zeros(n * m, np.uint8)  # cell (i, j) at (i - 1) * m + (j - 1): 0 diagonal, 1 up, 2 left
-    if n and m:
-        # diagonal d as an array over i: X[i] = D[i][d - i]
-        prev2 = np.zeros(n + 1, np.int32)  # d - 2
-        prev = np.zeros(n + 1, np.int32)   # d - 1
-        prev[0] = 1                        # D[0][1]
-        prev[1] = 1                        # D[1][0]
-        rb = b[::-1]
-        for d in range(2, n + m + 1):
-            cur = np.zeros(n + 1, np.int32)
-            if d <= m:
-                cur[0] = d
-            if d <= n:
-                cur[d] = d
-            lo, hi = max(1, d - m), min(n, d - 1)  # the inner cells' rows
-            # j = d - i runs from d - lo down to d - hi: b[j - 1] read backwards
-            cost = (a[lo - 1: hi] != rb[m - (d - lo): m - (d - hi) + 1]).astype(np.int32)
-            diag = prev2[lo - 1: hi] + cost
-            up = prev[lo - 1: hi] + 1
-            left = prev[lo: hi + 1] + 1
-            best = np.minimum(diag, np.minimum(up, left))
-            cur[lo: hi + 1] = best
-            i = np.arange(lo, hi + 1, dtype=np.int64)
-            dirs[(i - 1) * m + (d - i - 1)] = np.where(diag == best, 0, np.where(up == best, 1, 2)).astype(np.uint8)
-            prev2, prev = prev, cur
-    i, j = n, m
+    rpos = np.full(n, int(w0) - 1, np.int32)
+    dirs = np.zeros((n, m), np.uint8)  # cell (i, j) at [i - 1, j - 1]: 0 diagonal, 1 up, 2 left
+    ramp = np.arange(m + 1, dtype=np.int32)
+    prev = np.zeros(m + 1, np.int32) if free else ramp  # D[0][j]
+    for i in range(1, n + 1):
+        t = np.empty(m + 1, np.int32)
+        t[0] = i
+        diag = prev[:-1] + (b != a[i - 1])
+        up = prev[1:] + 1
+        np.minimum(diag, up, out=t[1:])
+        cur = np.minimum.accumulate(t - ramp) + ramp
+        dirs[i - 1] = np.where(diag == cur[1:], 0, np.where(up == cur[1:], 1, 2))
+        prev = cur
+    t_end = int(np.argmin(prev)) if free else m  # argmin: the smallest j of the minimum; row 0 of zeros gives 0
+    i, j = n, t_end
     n_match = n_sub = n_ins = n_del = 0
-    while i > 0 or j > 0:
+    while i > 0:
         if j == 0:
             ops[:i] = OP_INS
             n_ins += i
             break
-        if i == 0:
-            n_del += j
-            break
-        d = dirs[(i - 1) * m + (j - 1)]
+        d = dirs[i - 1, j - 1]
+        if d != 2:
+            rpos[i - 1] = w0 + j - 1
         if d == 0:
             if a[i - 1] != b[j - 1]:
                 ops[i - 1] = OP_SUB
@@ -109,7 +133,16 @@ def align_host(call, truth):
         else:
             n_del += 1
             j -= 1
-    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), ops
+    if not free:  # row 0 at column j: the rest of the truth is missing from the call
+        n_del, j = n_del + j, 0
+    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), (j, t_end), ops, rpos
+
+
+def align_host(call, truth):
+    """(counts int32 [5], ops uint8 [n]) of one pair by the rule above.  The host path, the fallback of
+    align_reads and the tests' oracle."""
+    counts, _, ops, _ = _dp(call, truth, False)
+    return counts, ops
 
 
 def pack_align_input(calls, truths):
@@ -134,13 +167,12 @@ def pack_align_input(calls, truths):
 def _align_device(call, call_off, truth, truth_off, cells, device, want_ops=True):
     """One nd_align_seqs call on the CURRENT stream of ``device``: (counts int32 [P, 5], status int32 [P], ops
     uint8 [bytes] or None) on the host."""
-    import ctypes
-
     import torch
 
     from . import _lib
     from .frontend import _pinned
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    d = _Device(device)
+    dev, p = d.dev, d.ptr
     P = len(call_off) - 1
     L = _lib.lib()
     work_bytes = int(L.nd_align_seqs_work_bytes(P, int(cells)))
@@ -148,21 +180,12 @@ def _align_device(call, call_off, truth, truth_off, cells, device, want_ops=True
         raise ValueError("nd_align_seqs_work_bytes refused P = %d, cells = %d" % (P, cells))
     with torch.cuda.device(dev):
         off_d = _pinned(np.concatenate([call_off, truth_off])).to(dev, non_blocking=True)
-        # one byte more than the bases: an empty side still has an address
-        call_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
-        truth_d = torch.zeros(truth.size + 1, dtype=torch.uint8, device=dev)
-        if call.size:
-            call_d[: call.size].copy_(_pinned(call), non_blocking=True)
-        if truth.size:
-            truth_d[: truth.size].copy_(_pinned(truth), non_blocking=True)
+        call_d, truth_d = d.upload(call, truth)
         out_d = torch.empty(P * 6, dtype=torch.int32, device=dev)  # counts [P, 5], status [P]
         ops_d = torch.empty(call.size + 1, dtype=torch.uint8, device=dev) if want_ops else None
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
         _lib.check(L.nd_align_seqs(p(call_d), p(off_d), p(truth_d), p(off_d[P + 1:]), P, int(cells), p(out_d),
-                                   p(ops_d) if want_ops else None, p(out_d[5 * P:]), p(work_d), work_bytes, stream),
-                   "nd_align_seqs")
+                                   p(ops_d), p(out_d[5 * P:]), p(work_d), work_bytes, d.stream()), "nd_align_seqs")
         out = out_d.cpu().numpy()  # synchronises the stream: the device tensors above are done with
         ops = ops_d.cpu().numpy()[: call.size] if want_ops else None
     return out[: 5 * P].reshape(P, 5).copy(), out[5 * P:].copy(), ops
@@ -212,24 +235,28 @@ def identity(counts):
     return float(out) if out.ndim == 0 else out
 
 
-def read_truth(path):
-    """{read name: sequence} of a FASTA file: records may span lines, the first word of the header is the read
-    name, and the sequence is normalised (upper case, M written as C).  Text before the first header is
-    ignored; a repeated name keeps its last record."""
-    out, name, parts = {}, None, []
+def fasta_records(path):
+    """(name, sequence) of every record of a FASTA file, in the file's order: records may span lines, the first
+    word of the header is the name ("" for a header without one), and the sequence is normalised (upper case, M
+    written as C).  Text before the first header is ignored, and so are blank lines."""
+    name, parts = None, []
     with open(path) as f:
         for line in f:
             line = line.strip()
             if line.startswith(">"):
                 if name is not None:
-                    out[name] = normalise("".join(parts))
+                    yield name, normalise("".join(parts))
                 words = line[1:].split()
                 name, parts = (words[0] if words else ""), []
             elif name is not None and line:
                 parts.append(line)
     if name is not None:
-        out[name] = normalise("".join(parts))
-    return out
+        yield name, normalise("".join(parts))
+
+
+def read_truth(path):
+    """{read name: sequence} of a FASTA file (fasta_records); a repeated name keeps its last record."""
+    return dict(fasta_records(path))
 
 
 def quality_table(quals, ops):
@@ -339,8 +366,7 @@ def build_index(seq, rec_off, device=None):
         key = np.sort(key)
     else:
         import torch
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        key = torch.sort(torch.from_numpy(key).to(dev))[0].cpu().numpy()
+        key = torch.sort(torch.from_numpy(key).to(_Device(device).dev))[0].cpu().numpy()
     code = (key >> 32).astype(np.uint32)
     first = np.flatnonzero(np.r_[True, code[1:] != code[:-1]]) if code.size else np.zeros(0, np.int64)
     runs = np.diff(np.r_[first, code.size])
@@ -396,23 +422,9 @@ class Reference:
 
 def read_reference(path):
     """The Reference of a FASTA file: every record in the file's order (a repeated name stays a record of its
-    own), named by the first word of its header, normalised as read_truth does.  More than MAP_REF_MAX bases in
-    total is a ValueError."""
-    names, seqs, parts = [], [], None
-    with open(path) as f:
-        for line in f:
-            line = line.strip()
-            if line.startswith(">"):
-                if parts is not None:
-                    seqs.append(normalise("".join(parts)))
-                words = line[1:].split()
-                names.append(words[0] if words else "")
-                parts = []
-            elif parts is not None and line:
-                parts.append(line)
-    if parts is not None:
-        seqs.append(normalise("".join(parts)))
-    return Reference(names, seqs)
+    own), as fasta_records gives them.  More than MAP_REF_MAX bases in total is a ValueError."""
+    records = list(fasta_records(path))
+    return Reference([name for name, _ in records], [seq for _, seq in records])
 
 
 def segments(n):
@@ -453,10 +465,8 @@ def locate_host(seg, ref):
 
 
 def fit_host(call, window):
-    """(counts int32 [5], (t_start, t_end), ops uint8 [n]) of a call against a window by the fit rule: numpy over
-    the rows (D[i][j] = j + the running minimum of min(diagonal, up)[k] - k), one direction byte per cell, then
-    the traceback."""
-    return _fit(call, window, 0)[:3]
+    """(counts int32 [5], (t_start, t_end), ops uint8 [n]) of a call against a window by the fit rule."""
+    return _dp(call, window, True)[:3]
 
 
 def fit_pos_host(call, window, w0=0):
@@ -464,75 +474,51 @@ def fit_pos_host(call, window, w0=0):
     of the reference: a diagonal step at cell (i + 1, j) gives w0 + j - 1 (the base matched or mismatched to), an
     up step at column j the same (the base to the left of the inserted one; w0 - 1 on the column-0 border).  The
     rule of nd_align_fit_pos."""
-    return _fit(call, window, w0)
+    return _dp(call, window, True, w0)
 
 
-def _fit(call, window, w0):
-    a, b = _bytes(call), _bytes(window)
-    n, m = int(a.size), int(b.size)
-    ops = np.zeros(n, np.uint8)
-    rpos = np.full(n, int(w0) - 1, np.int32)
-    dirs = np.zeros((n, m), np.uint8)  # cell (i, j) at [i - 1, j - 1]: 0 diagonal, 1 up, 2 left
-    prev = np.zeros(m + 1, np.int32)   # D[0][j] = 0
-    ramp = np.arange(m + 1, dtype=np.int32)
-    for i in range(1, n + 1):
-        t = np.empty(m + 1, np.int32)
-        t[0] = i
-        diag = prev[:-1] + (b != a[i - 1])
-        up = prev[1:] + 1
-        np.minimum(diag, up, out=t[1:])
-        cur = np.minimum.accumulate(t - ramp) + ramp
-        dirs[i - 1] = np.where(diag == cur[1:], 0, np.where(up == cur[1:], 1, 2))
-        prev = cur
-    jstar = int(np.argmin(prev)) if n else 0
-    i, j = n, jstar
-    n_match = n_sub = n_ins = n_del = 0
-    while i > 0:
-        if j == 0:
-            ops[:i] = OP_INS
-            n_ins += i
-            break
-        d = dirs[i - 1, j - 1]
-        if d != 2:
-            rpos[i - 1] = w0 + j - 1
-        if d == 0:
-            if a[i - 1] != b[j - 1]:
-                ops[i - 1] = OP_SUB
-                n_sub += 1
-            else:
-                n_match += 1
-            i -= 1
-            j -= 1
-        elif d == 1:
-            ops[i - 1] = OP_INS
-            n_ins += 1
-            i -= 1
-        else:
-            n_del += 1
-            j -= 1
-    return np.asarray([n_sub + n_ins + n_del, n_match, n_sub, n_ins, n_del], np.int32), (j, jstar), ops, rpos
+class Segment(NamedTuple):
+    """A mapped segment of a call: [seg_start, seg_end) of the call as written, its strand, the reference record
+    and the aligned reference interval in the concatenation's coordinates, the locate votes and the fit's counts."""
+    seg_start: int
+    seg_end: int
+    strand: int
+    rec: int
+    ref_start: int
+    ref_end: int
+    votes: int
+    counts: np.ndarray
 
 
 def map_host(call, ref, pile=None):
     """(counts int32 [5], segment records, ops uint8 [n]) of one call: its segments located and fitted on the
-    host.  A segment record is (seg_start, seg_end, strand, rec, ref_start, ref_end, votes, counts) with the
-    reference interval in the concatenation's coordinates; only mapped segments have one.  ops is per base of the
-    call as written (a strand-1 segment's reversed back), OP_UNMAPPED in an unmapped segment.  ``pile`` (a
-    [9, total] uint32 table, Pileup) takes every mapped segment by pile_add_host."""
-    a = _bytes(call)
-    total, recs, ops = np.zeros(5, np.int32), [], np.full(a.size, OP_UNMAPPED, np.uint8)
-    for s0, s1 in segments(a.size):
-        mapped, strand, w0, w1, votes = locate_host(a[s0:s1], ref)
+    host.  Only mapped segments have a record (Segment).  ops is per base of the call as written (a strand-1
+    segment's reversed back), OP_UNMAPPED in an unmapped segment.  ``pile`` (a [9, total] uint32 table, Pileup)
+    takes every mapped segment by pile_add_host."""
+    counts, recs, ops = map_reads([call], ref, want_ops=True, pile=pile)
+    return counts[0], recs[0], ops[0]
+
+
+def _map_segments_host(call, seg_off, ref, pile=None):
+    """What _map_device returns, by the host rule: segment k is call[seg_off[k] .. seg_off[k + 1])."""
+    P = len(seg_off) - 1
+    hit, status = np.zeros((P, 4), np.int32), np.zeros(P, np.int32)
+    counts, span = np.zeros((P, 5), np.int32), np.zeros((P, 2), np.int32)
+    ops = np.zeros(call.size, np.uint8)
+    for k in range(P):
+        q = call[seg_off[k]: seg_off[k + 1]]
+        mapped, strand, w0, w1, votes = locate_host(q, ref)
+        hit[k] = strand, w0, w1, votes
         if not mapped:
+            status[k] = MAP_STATUS_UNMAPPED
             continue
-        oriented = a[s0:s1] if strand == 0 else reverse_complement(a[s0:s1])
-        counts, (t0, t1), o, rpos = _fit(oriented, ref.seq[w0:w1], w0)
+        oriented = q if strand == 0 else reverse_complement(q)
+        counts[k], (t0, t1), o, rpos = _dp(oriented, ref.seq[w0:w1], True, w0)
+        span[k] = w0 + t0, w0 + t1
+        ops[seg_off[k]: seg_off[k + 1]] = o
         if pile is not None:
             pile_add_host(pile, oriented, o, rpos)
-        ops[s0:s1] = o if strand == 0 else o[::-1]
-        total += counts
-        recs.append((s0, s1, strand, ref.record_of(w0), w0 + t0, w0 + t1, votes, counts))
-    return total, recs, ops
+    return hit, status, counts, span, ops
 
 
 def _map_device(call, seg_off, ref, device, want_ops, pile=None):
@@ -540,13 +526,12 @@ def _map_device(call, seg_off, ref, device, want_ops, pile=None):
     (hit int32 [P, 4], status int32 [P], counts int32 [P, 5], span int32 [P, 2], oriented ops uint8 [bytes] or
     None) on the host.  With ``pile`` (a Pileup's table on that device) the fit is nd_align_fit_pos and
     nd_pileup_add follows it on the same stream."""
-    import ctypes
-
     import torch
 
     from . import _lib
     from .frontend import _pinned
-    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    d = _Device(device)
+    dev, p = d.dev, d.ptr
     P = len(seg_off) - 1
     n = np.diff(seg_off).astype(np.int64)
     cells = int((n * (n + 2 * MAP_PAD + (2 << MAP_BIN_SHIFT))).sum())
@@ -557,23 +542,19 @@ def _map_device(call, seg_off, ref, device, want_ops, pile=None):
     with torch.cuda.device(dev):
         seq_d, rec_d, code_d, pos_d = ref.on_device(dev)
         off_d = _pinned(seg_off).to(dev, non_blocking=True)
-        call_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
-        if call.size:
-            call_d[: call.size].copy_(_pinned(call), non_blocking=True)
+        call_d, = d.upload(call)
         or_d = torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
         out_d = torch.zeros(P * 12, dtype=torch.int32, device=dev)  # hit [P, 4], status [P], counts [P, 5], span [P, 2]
         ops_d = (torch.zeros(call.size + 1, dtype=torch.uint8, device=dev)
                  if want_ops or pile is not None else None)
         work_d = torch.empty(work_bytes, dtype=torch.uint8, device=dev)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        stream = d.stream()
         hit_d, status_d, counts_d, span_d = out_d, out_d[4 * P:], out_d[5 * P:], out_d[10 * P:]
         _lib.check(L.nd_locate_segs(p(call_d), p(off_d), P, p(code_d), p(pos_d), int(code_d.numel()), p(rec_d),
                                     int(rec_d.numel()) - 1, p(hit_d), p(status_d), p(or_d), stream), "nd_locate_segs")
         if pile is None:
             _lib.check(L.nd_align_fit(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d),
-                                      p(span_d), p(ops_d) if want_ops else None, p(status_d), p(work_d), work_bytes,
-                                      stream), "nd_align_fit")
+                                      p(span_d), p(ops_d), p(status_d), p(work_d), work_bytes, stream), "nd_align_fit")
         else:
             rpos_d = torch.empty(call.size + 1, dtype=torch.int32, device=dev)
             _lib.check(L.nd_align_fit_pos(p(or_d), p(off_d), p(seq_d), ref.total, p(hit_d), P, cells, p(counts_d),
@@ -587,57 +568,45 @@ def _map_device(call, seg_off, ref, device, want_ops, pile=None):
             out[10 * P:].reshape(P, 2).copy(), ops)
 
 
-def map_reads(calls, ref, device=None, want_ops=False, stats=None):
+def map_reads(calls, ref, device=None, want_ops=False, stats=None, pile=None):
     """The rule for a list of calls: (counts int32 [reads, 5], per read its list of segment records, per read its
-    ops or None without ``want_ops``), each as map_host gives them.  ``device=None`` is map_host read by read.
-    Otherwise all segments of all reads are one nd_locate_segs call and one nd_align_fit call on the current torch
-    stream of ``device``: a read of any length runs there.  ``stats`` (a dict) gets "reads", "segments" and
-    "unmapped" (segments) increased."""
-    return _map_reads(calls, ref, device, want_ops, stats, None)
-
-
-def _map_reads(calls, ref, device, want_ops, stats, pile):
-    """map_reads; ``pile``, a Pileup's table (on the host or on ``device``), takes every mapped segment."""
+    ops or None without ``want_ops``), each as map_host gives them.  ``device=None`` is the host rule segment by
+    segment.  Otherwise all segments of all reads are one nd_locate_segs call and one nd_align_fit call on the
+    current torch stream of ``device``: a read of any length runs there.  ``stats`` (a dict) gets "reads",
+    "segments" and "unmapped" (segments) increased.  ``pile``, a Pileup's table (on the host or on ``device``),
+    takes every mapped segment."""
     calls = [_bytes(c) for c in calls]
-    if device is None:
-        res = [map_host(c, ref, pile) for c in calls]
+    segs = [segments(c.size) for c in calls]
+    base = np.zeros(len(calls) + 1, np.int64)
+    base[1:] = np.cumsum([c.size for c in calls], dtype=np.int64)
+    seg_off = np.asarray([0] + [base[r] + s1 for r, sg in enumerate(segs) for _, s1 in sg], np.int64)
+    flat = np.concatenate(calls) if base[-1] else np.zeros(0, np.uint8)
+    if device is None or not calls:
+        hit, status, counts, span, ops_or = _map_segments_host(flat, seg_off, ref, pile)
     else:
-        segs = [segments(c.size) for c in calls]
-        seg_off = np.zeros(sum(len(s) for s in segs) + 1, np.int64)
-        base, k = 0, 0
-        for c, sg in zip(calls, segs):
-            for _, s1 in sg:
-                k += 1
-                seg_off[k] = base + s1
-            base += int(c.size)
-        if base >= 2 ** 31:
+        if base[-1] >= 2 ** 31:
             raise ValueError("more than 2^31 - 1 bases in one mapping call")
-        res = []
-        if calls:
-            flat = np.concatenate(calls) if base else np.zeros(0, np.uint8)
-            hit, status, counts, span, ops_or = _map_device(flat, seg_off.astype(np.int32), ref, device, want_ops,
-                                                            pile)
-            if (status & ~MAP_STATUS_UNMAPPED).any():
-                raise RuntimeError("nd_align_fit status %s" % sorted(set(status.tolist())))
-            k = 0
-            for c, sg in zip(calls, segs):
-                total, recs, ops = np.zeros(5, np.int32), [], np.full(c.size, OP_UNMAPPED, np.uint8)
-                for s0, s1 in sg:
-                    if status[k] == 0:
-                        strand, w0 = int(hit[k, 0]), int(hit[k, 1])
-                        total += counts[k]
-                        recs.append((s0, s1, strand, ref.record_of(w0), int(span[k, 0]), int(span[k, 1]),
-                                     int(hit[k, 3]), counts[k].copy()))
-                        if want_ops:
-                            o = ops_or[seg_off[k]: seg_off[k + 1]]
-                            ops[s0:s1] = o if strand == 0 else o[::-1]
-                    k += 1
-                res.append((total, recs, ops))
+        hit, status, counts, span, ops_or = _map_device(flat, seg_off.astype(np.int32), ref, device, want_ops, pile)
+        if (status & ~MAP_STATUS_UNMAPPED).any():
+            raise RuntimeError("nd_align_fit status %s" % sorted(set(status.tolist())))
+    res, k = [], 0
+    for c, sg in zip(calls, segs):
+        total, recs, ops = np.zeros(5, np.int32), [], np.full(c.size, OP_UNMAPPED, np.uint8)
+        for s0, s1 in sg:
+            if status[k] == 0:
+                strand, w0 = int(hit[k, 0]), int(hit[k, 1])
+                total += counts[k]
+                recs.append(Segment(s0, s1, strand, ref.record_of(w0), int(span[k, 0]), int(span[k, 1]),
+                                    int(hit[k, 3]), counts[k].copy()))
+                if ops_or is not None:
+                    o = ops_or[seg_off[k]: seg_off[k + 1]]
+                    ops[s0:s1] = o if strand == 0 else o[::-1]
+            k += 1
+        res.append((total, recs, ops))
     if stats is not None:
-        nseg = sum(len(segments(c.size)) for c in calls)
         stats["reads"] = stats.get("reads", 0) + len(calls)
-        stats["segments"] = stats.get("segments", 0) + nseg
-        stats["unmapped"] = stats.get("unmapped", 0) + nseg - sum(len(r[1]) for r in res)
+        stats["segments"] = stats.get("segments", 0) + k
+        stats["unmapped"] = stats.get("unmapped", 0) + k - sum(len(r[1]) for r in res)
     counts = np.asarray([r[0] for r in res], np.int32).reshape(len(calls), 5)
     return counts, [r[1] for r in res], ([r[2] for r in res] if want_ops else None)
 
@@ -646,12 +615,13 @@ def paf_line(name, n_called, rec, ref):
     """One line of mapping.paf for a segment record: the 12 PAF columns (query coordinates on the read as written,
     target coordinates inside the record, matches, block length = match + sub + ins + del, mapq 255) and vt:i: =
     the locate votes."""
-    s0, s1, strand, r, t0, t1, votes, counts = rec
-    c = [int(v) for v in counts]
-    base = int(ref.rec_off[r])
+    rec = Segment(*rec)
+    c = [int(v) for v in rec.counts]
+    base = int(ref.rec_off[rec.rec])
     return "%s\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%d\t%d\t%d\t255\tvt:i:%d\n" % (
-        name, n_called, s0, s1, "-" if strand else "+", ref.names[r], int(ref.rec_off[r + 1]) - base, t0 - base,
-        t1 - base, c[1], c[1] + c[2] + c[3] + c[4], votes)
+        name, n_called, rec.seg_start, rec.seg_end, "-" if rec.strand else "+", ref.names[rec.rec],
+        int(ref.rec_off[rec.rec + 1]) - base, rec.ref_start - base, rec.ref_end - base, c[1],
+        c[1] + c[2] + c[3] + c[4], rec.votes)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -751,12 +721,12 @@ class Pileup:
             self._pile = np.zeros((PILE_PLANES, ref.total), np.uint32)
         else:
             import torch
-            self._dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-            self._pile = torch.zeros(PILE_PLANES * ref.total + 1, dtype=torch.int32, device=self._dev)
+            self._d = _Device(device)
+            self._pile = torch.zeros(PILE_PLANES * ref.total + 1, dtype=torch.int32, device=self._d.dev)
 
     def add(self, calls, want_ops=False, stats=None):
         """map_reads(calls, ref, device, want_ops, stats), its results, with every mapped segment piled."""
-        return _map_reads(calls, self.ref, self.device, want_ops, stats, self._pile)
+        return map_reads(calls, self.ref, self.device, want_ops, stats, self._pile)
 
     def counts(self):
         """The table as a [9, total] uint32 numpy array (a copy)."""
@@ -770,29 +740,21 @@ class Pileup:
             raise ValueError("min_cov must be at least 1")
         if self.device is None:
             return consensus_host(self._pile, self.ref, min_cov)
-        import ctypes
-
         import torch
 
         from . import _lib
         total, R = self.ref.total, len(self.ref.names)
-        with torch.cuda.device(self._dev):
-            seq_d, rec_off_d = self.ref.on_device(self._dev)[:2]
-            cc_d = torch.full((2 * total + 1,), CONS_NONE, dtype=torch.uint8, device=self._dev)  # cons, ins
-            cov_d = torch.zeros(total + 1, dtype=torch.int32, device=self._dev)
-            rec_d = torch.zeros(R * 6 + 1, dtype=torch.int64, device=self._dev)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self._dev).cuda_stream)
-            p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        dev, p = self._d.dev, self._d.ptr
+        with torch.cuda.device(dev):
+            seq_d, rec_off_d = self.ref.on_device(dev)[:2]
+            cc_d = torch.full((2 * total + 1,), CONS_NONE, dtype=torch.uint8, device=dev)  # cons, ins
+            cov_d = torch.zeros(total + 1, dtype=torch.int32, device=dev)
+            rec_d = torch.zeros(R * 6 + 1, dtype=torch.int64, device=dev)
             _lib.check(_lib.lib().nd_pileup_call(p(self._pile), p(seq_d), total, p(rec_off_d), R, int(min_cov),
-                                                 p(cc_d), p(cc_d[total:]), p(cov_d), p(rec_d), stream),
+                                                 p(cc_d), p(cc_d[total:]), p(cov_d), p(rec_d), self._d.stream()),
                        "nd_pileup_call")
             cc, cov, rec = cc_d.cpu().numpy(), cov_d.cpu().numpy(), rec_d.cpu().numpy()
         return cc[:total].copy(), cc[total: 2 * total].copy(), cov[:total].copy(), rec[: R * 6].reshape(R, 6).copy()
-
-
-def _ratio(match, sub, dele, ins):
-    den = int(match) + int(sub) + int(dele) + int(ins)
-    return int(match) / den if den else 0.0
 
 
 def consensus_fasta(ref, cons, ins):
@@ -810,7 +772,7 @@ def consensus_fasta(ref, cons, ins):
         if rec[r, 0] == 0:
             continue
         part = both[int(ref.rec_off[r]): int(ref.rec_off[r + 1])].reshape(-1)
-        out.append(">%s called=%d identity=%.6f\n%s\n" % (name, rec[r, 0], _ratio(*rec[r, 1:5]),
+        out.append(">%s called=%d identity=%.6f\n%s\n" % (name, rec[r, 0], identity(rec[r, :5]),
                                                          part[part != 0].tobytes().decode("ascii")))
     return "".join(out)
 
@@ -840,7 +802,7 @@ def coverage_lines(ref, rec):
     def line(name, length, v):
         v = [int(x) for x in v]
         return "%s\t%d\t%d\t%.2f\t%d\t%d\t%d\t%d\t%.6f\n" % (name, length, v[0], v[5] / v[0] if v[0] else 0.0,
-                                                               v[1], v[2], v[3], v[4], _ratio(*v[1:5]))
+                                                               v[1], v[2], v[3], v[4], identity(v[:5]))
     out = [line(name, int(ref.rec_off[r + 1]) - int(ref.rec_off[r]), rec[r]) for r, name in enumerate(ref.names)]
     out.append(line("total", ref.total, np.asarray(rec, np.int64).reshape(-1, 6).sum(axis=0)))
     return out
@@ -852,5 +814,134 @@ def consensus_summary(ref, rec, min_cov, n_variants):
     v = [int(x) for x in np.asarray(rec, np.int64).reshape(-1, 6).sum(axis=0)]
     return ("-consensus: %d of %d reference bases called at coverage >= %d, mean coverage %.2f; consensus identity "
             "%.6f (%d matches, %d substitutions, %d deletions, %d insertions); %d variant lines"
-            % (v[0], ref.total, min_cov, v[5] / v[0] if v[0] else 0.0, _ratio(*v[1:5]), v[1], v[2], v[3], v[4],
+            % (v[0], ref.total, min_cov, v[5] / v[0] if v[0] else 0.0, identity(v[:5]), v[1], v[2], v[3], v[4],
                n_variants))
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The evaluation of a run (translate.py -truth, -truth_ref, -consensus): what a read's evaluation leaves for its
+# writer, and the object that holds the run's truth, device choice, pile and sums.
+@dataclass
+class ReadEntry:
+    """One assembled read's evaluation.  ``line`` is its line of accuracy.tsv, None for a read without a known
+    sequence (-truth) or without a mapped segment (-truth_ref); ``quality`` and ``ops`` are there under -fastq;
+    ``paf_lines``, ``segments`` and ``mapped`` (of those segments) belong to -truth_ref."""
+    line: str | None = None
+    counts: np.ndarray | None = None
+    quality: str | None = None
+    ops: np.ndarray | None = None
+    paf_lines: list = field(default_factory=list)
+    segments: int = 0
+    mapped: int = 0
+
+
+class Evaluation:
+    """-truth or -truth_ref for one run: ``opt`` gives the file, where to align (-truth_align, -gpu) and
+    -consensus.  evaluate() aligns or maps a translated group, account() takes a read's entry into the run's sums
+    once the read is written, finish() writes the end-of-run files and log lines."""
+
+    def __init__(self, opt):
+        self.seqs = read_truth(opt.truth) if opt.truth else None
+        self.ref = read_reference(opt.truth_ref) if opt.truth_ref else None
+        self.device = None if opt.truth_align == "cpu" else max(0, opt.gpu)
+        self.pile = Pileup(self.ref, device=self.device) if opt.consensus else None
+        self.min_cov = opt.consensus_min_cov
+        self.align_stats = {"reads": 0, "fallback": 0}  # -truth: reads aligned / of them on the host after a status
+        # the written reads: those with a line and those without one; under -truth_ref their segments and the
+        # unmapped ones; the sums of matches and alignment columns; the called bases and errors per quality
+        self.evaluated = self.missing = self.segments = self.unmapped = self.match = self.length = 0
+        self.bases, self.errors = np.zeros(Q_LEVELS, np.int64), np.zeros(Q_LEVELS, np.int64)
+
+    def evaluate(self, names, seqs, fastq):
+        """Per read of a group None (not evaluated: no assembled sequence, or the evaluation raised) or its
+        ReadEntry.  ``seqs`` are the reads as frontend.assemble_reads gives them (None: not assembled), with the
+        quality string second under ``fastq``.  -truth: every read with a known sequence is aligned to it, one
+        device call for the group or the host rule.  -truth_ref: every read is mapped to the reference, all
+        segments of the group in one locate call and one fit call or by the host rule, and piled under
+        -consensus as it is mapped."""
+        res = [None] * len(names)
+        todo = []
+        for k, name in enumerate(names):
+            if seqs[k] is None:
+                continue
+            if self.ref is None and name not in self.seqs:
+                res[k] = ReadEntry()  # written, without a truth
+            else:
+                todo.append(k)
+        if not todo:
+            return res
+        called = [normalise(seqs[k] if isinstance(seqs[k], str) else seqs[k][0]) for k in todo]
+        try:
+            if self.ref is None:
+                truths = [self.seqs[names[k]] for k in todo]
+                counts, ops = align_reads(called, truths, device=self.device, want_ops=fastq, stats=self.align_stats)
+                recs = [None] * len(todo)
+            elif self.pile is not None:
+                counts, recs, ops = self.pile.add(called, want_ops=fastq)
+            else:
+                counts, recs, ops = map_reads(called, self.ref, device=self.device, want_ops=fastq)
+        except Exception as e:
+            for k in todo:
+                print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
+            return res
+        for x, k in enumerate(todo):
+            name, n = names[k], len(called[x])
+            entry = ReadEntry(counts=counts[x])
+            if self.ref is None:
+                entry.line = accuracy_line(name, n, len(truths[x]), counts[x])
+            else:
+                entry.segments, entry.mapped = len(segments(n)), len(recs[x])
+                if recs[x]:
+                    entry.line = accuracy_line(name, n, sum(r.ref_end - r.ref_start for r in recs[x]), counts[x])
+                    entry.paf_lines = [paf_line(name, n, r, self.ref) for r in recs[x]]
+            if fastq and entry.line is not None:
+                entry.quality, entry.ops = seqs[k][1], ops[x]
+            res[k] = entry
+        return res
+
+    def account(self, entry):
+        """A written read's entry into the run's sums."""
+        if entry is None:
+            return
+        self.segments += entry.segments
+        self.unmapped += entry.segments - entry.mapped
+        if entry.line is None:
+            self.missing += 1
+            return
+        self.evaluated += 1
+        self.match += int(entry.counts[1])
+        self.length += int(entry.counts[1:5].sum())
+        if entry.quality is not None:
+            quality, ops = entry.quality, entry.ops
+            if self.ref is not None:  # the bases of the mapped segments only
+                keep = ops != OP_UNMAPPED
+                quality, ops = np.frombuffer(quality.encode("ascii"), np.uint8)[keep].tobytes(), ops[keep]
+            b, e = quality_table(quality, ops)
+            self.bases += b
+            self.errors += e
+
+    def finish(self, save_data, fastq, logger):
+        """The end of the run: quality_calibration.tsv under ``fastq``, the mode's line of the log and, under
+        -consensus, the pile called into consensus.fasta, variants.tsv and coverage.tsv with their line."""
+        if fastq:
+            with open(os.path.join(save_data, "quality_calibration.tsv"), "w") as f:
+                f.writelines(calibration_lines(self.bases, self.errors))
+        pooled = "pooled identity %.6f (%d matches over %d alignment columns)" % (
+            self.match / self.length if self.length else 0.0, self.match, self.length)
+        if self.ref is None:
+            logger.info("-truth: %d reads evaluated, %d without a truth, %d host fallbacks (a read or a truth above "
+                        "%d bases); %s" % (self.evaluated, self.missing, self.align_stats["fallback"], ALIGN_MAX_LEN,
+                                           pooled))
+        else:
+            logger.info("-truth_ref: %d reads evaluated, %d reads unmapped, %d segments mapped, %d unmapped; %s"
+                        % (self.evaluated, self.missing, self.segments - self.unmapped, self.unmapped, pooled))
+        if self.pile is not None:
+            cons, ins, cov, rec = self.pile.call(self.min_cov)
+            variants = variant_lines(self.ref, cons, ins, cov, self.pile.counts())
+            with open(os.path.join(save_data, "consensus.fasta"), "w") as f:
+                f.write(consensus_fasta(self.ref, cons, ins))
+            with open(os.path.join(save_data, "variants.tsv"), "w") as f:
+                f.writelines(variants)
+            with open(os.path.join(save_data, "coverage.tsv"), "w") as f:
+                f.writelines(coverage_lines(self.ref, rec))
+            logger.info(consensus_summary(self.ref, rec, self.min_cov, len(variants)))

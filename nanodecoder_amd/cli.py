@@ -24,8 +24,6 @@ import os
 import sys
 import time
 
-import numpy as np
-
 from . import accuracy, frontend
 from .opts import parse_translate_opts
 
@@ -93,7 +91,7 @@ def _n_chunks(opt, src, gpu_fe):
     return len(frontend.windows(len(src[1]), opt.src_seq_length, opt.src_seq_stride))
 
 
-def _run_group(opt, translator, pending, gpu_fe):
+def _run_group(opt, translator, pending, gpu_fe, evaluation, assembly_stats):
     """Front end (device) + translate for one packed group, with the
     per-group error isolation of translate.py:97-98.  -frontend gpu: the raw
     reads go to the translator, which normalises and windows every engine
@@ -101,7 +99,7 @@ def _run_group(opt, translator, pending, gpu_fe):
     -attn_debug (its file needs each chunk's samples on the host) the chunks
     come back to the host first."""
     if gpu_fe and not opt.attn_debug:
-        return _translate_group(opt, translator, pending, raw=True)
+        return _translate_group(opt, translator, pending, evaluation, assembly_stats, raw=True)
     if gpu_fe:
         try:
             pending = _gpu_chunks(opt, pending)
@@ -109,7 +107,7 @@ def _run_group(opt, translator, pending, gpu_fe):
             for g in pending:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    return _translate_group(opt, translator, pending)
+    return _translate_group(opt, translator, pending, evaluation, assembly_stats)
 
 
 def _extract(args):
@@ -174,17 +172,6 @@ def write_output(opt, file_src, all_predictions, time_translate, sequence=None, 
         return False
 
 
-ASSEMBLY_STATS = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled / of them on the host, this run
-ALIGN_STATS = {"reads": 0, "fallback": 0}     # -truth: reads aligned / of them on the host after a device status
-# -truth, this run: the known sequences (None without the flag), the reads written with and without one, the sums
-# of matches and alignment lengths, and with -fastq the called bases and errors per predicted quality
-# (-truth_ref: "ref" the shared reference, "missing" the reads written without a mapped segment; -consensus: "pile"
-# the run's accuracy.Pileup)
-TRUTH = {"seqs": None, "ref": None, "evaluated": 0, "missing": 0, "match": 0, "length": 0, "bases": None,
-         "errors": None, "pile": None}
-MAP_STATS = {"reads": 0, "segments": 0, "unmapped": 0}  # -truth_ref, written reads: their segments, those unmapped
-
-
 def _assemble_missing(opt, outs, seqs, weights, mods, positions):
     """The reads of ``seqs`` still None, assembled by the host functions write_output would use."""
     for k, o in enumerate(outs):
@@ -199,152 +186,25 @@ def _assemble_missing(opt, outs, seqs, weights, mods, positions):
                 seqs[k] = None
 
 
-def _evaluate_group_ref(opt, names, seqs, fastq):
-    """-truth_ref for one translated group: every assembled read is mapped to the shared reference, all
-    segments of the group in one locate call and one fit call (-truth_align gpu) or by the host rule.  Returns per
-    read None, or (its accuracy.tsv line, None for a read without a mapped segment; the summed counts; quality
-    string or None; ops or None; its mapping.paf lines; (its segments, those of them mapped)).  The run's sums
-    take a read's entry only once the read is written (_account)."""
-    ref = TRUTH["ref"]
-    todo = [k for k in range(len(names)) if seqs[k] is not None]
-    res = [None] * len(names)
-    if not todo:
-        return res
-    text = lambda q: q if isinstance(q, str) else q[0]  # noqa: E731
-    called = [accuracy.normalise(text(seqs[k])) for k in todo]
-    device = None if getattr(opt, "truth_align", "gpu") == "cpu" else max(0, opt.gpu)
-    try:
-        if TRUTH["pile"] is not None:  # -consensus: the same mapping, its segments piled as they are aligned
-            counts, recs, ops = TRUTH["pile"].add(called, want_ops=fastq)
-        else:
-            counts, recs, ops = accuracy.map_reads(called, ref, device=device, want_ops=fastq)
-    except Exception as e:
-        for k in todo:
-            print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
-        return res
-    for x, k in enumerate(todo):
-        nseg = (len(accuracy.segments(len(called[x]))), len(recs[x]))
-        if not recs[x]:
-            res[k] = (None, counts[x], None, None, [], nseg)
-            continue
-        span = sum(r[5] - r[4] for r in recs[x])
-        res[k] = (accuracy.accuracy_line(names[k], len(called[x]), span, counts[x]), counts[x],
-                  seqs[k][1] if fastq else None, ops[x] if fastq else None,
-                  [accuracy.paf_line(names[k], len(called[x]), r, ref) for r in recs[x]], nseg)
-    return res
-
-
-def _evaluate_group(opt, group, outs, seqs, weights, mods, positions):
-    """-truth for one translated group: the reads of ``seqs`` still None (-assembly cpu) are assembled here, by
-    the host functions write_output would use, and every read that has a known sequence is aligned to it: one
-    device call for the group (-truth_align gpu) or the host rule.  Returns per read None, or (its accuracy.tsv
-    line, counts, quality string or None, ops or None).  A read whose assembly raises stays None in ``seqs``:
-    write_output assembles it again and reports it."""
-    fastq = weights[0] is not None if weights else False
-    names = [g[0].split(".txt")[0] for g in group]
-    _assemble_missing(opt, outs, seqs, weights, mods, positions)
-    if TRUTH["ref"] is not None:
-        return _evaluate_group_ref(opt, names, seqs, fastq)
-    todo = [k for k in range(len(group)) if seqs[k] is not None and names[k] in TRUTH["seqs"]]
-    res = [None] * len(group)
-    for k in range(len(group)):
-        if seqs[k] is not None and names[k] not in TRUTH["seqs"]:
-            res[k] = ()  # written, without a truth
-    if not todo:
-        return res
-    text = lambda q: q if isinstance(q, str) else q[0]  # noqa: E731
-    called = [accuracy.normalise(text(seqs[k])) for k in todo]
-    truths = [TRUTH["seqs"][names[k]] for k in todo]
-    device = None if getattr(opt, "truth_align", "gpu") == "cpu" else max(0, opt.gpu)
-    try:
-        counts, ops = accuracy.align_reads(called, truths, device=device, want_ops=fastq, stats=ALIGN_STATS)
-    except Exception as e:
-        for k in todo:
-            print("!!!error!!!accuracy: " + names[k] + " (%r)" % (e,))
-        return res
-    for x, k in enumerate(todo):
-        res[k] = (accuracy.accuracy_line(names[k], len(called[x]), len(truths[x]), counts[x]), counts[x],
-                  seqs[k][1] if fastq else None, ops[x] if fastq else None)
-    return res
-
-
-def _account(entry):
-    """A written read's -truth entry (_evaluate_group) into the run's sums."""
-    if entry is None:
-        return
-    if not entry:
-        TRUTH["missing"] += 1
-        return
-    line, counts, quality, ops = entry[:4]
-    if len(entry) > 4:  # -truth_ref
-        MAP_STATS["reads"] += 1
-        MAP_STATS["segments"] += entry[5][0]
-        MAP_STATS["unmapped"] += entry[5][0] - entry[5][1]
-        if line is None:
-            TRUTH["missing"] += 1
-            return
-    TRUTH["evaluated"] += 1
-    TRUTH["match"] += int(counts[1])
-    TRUTH["length"] += int(counts[1]) + int(counts[2]) + int(counts[3]) + int(counts[4])
-    if quality is not None:
-        if len(entry) > 4:  # -truth_ref: the bases of the mapped segments only
-            keep = ops != accuracy.OP_UNMAPPED
-            quality, ops = np.frombuffer(quality.encode("ascii"), np.uint8)[keep].tobytes(), ops[keep]
-        b, e = accuracy.quality_table(quality, ops)
-        TRUTH["bases"] += b
-        TRUTH["errors"] += e
-
-
-def _write_consensus(opt, logger):
-    """-consensus, at the end of the run: the pile is called and save_data/consensus.fasta, variants.tsv and
-    coverage.tsv are written, with the log's line."""
-    ref, pile, min_cov = TRUTH["ref"], TRUTH["pile"], opt.consensus_min_cov
-    cons, ins, cov, rec = pile.call(min_cov)
-    variants = accuracy.variant_lines(ref, cons, ins, cov, pile.counts())
-    with open(os.path.join(opt.save_data, "consensus.fasta"), "w") as f:
-        f.write(accuracy.consensus_fasta(ref, cons, ins))
-    with open(os.path.join(opt.save_data, "variants.tsv"), "w") as f:
-        f.writelines(variants)
-    with open(os.path.join(opt.save_data, "coverage.tsv"), "w") as f:
-        f.writelines(accuracy.coverage_lines(ref, rec))
-    logger.info(accuracy.consensus_summary(ref, rec, min_cov, len(variants)))
-
-
 def main(opt=None):
     opt = opt or parse_translate_opts()
-    if getattr(opt, "fastq", False) and opt.attn_debug:
-        raise ValueError("-fastq is not available together with -attn_debug")
-    if getattr(opt, "mod_probs", False) and opt.attn_debug:
-        raise ValueError("-mod_probs is not available together with -attn_debug")
-    if getattr(opt, "moves", False) and opt.attn_debug:
-        raise ValueError("-moves is not available together with -attn_debug")
-    if getattr(opt, "truth", "") and opt.attn_debug:
-        raise ValueError("-truth is not available together with -attn_debug")
-    if getattr(opt, "truth_ref", "") and opt.attn_debug:
-        raise ValueError("-truth_ref is not available together with -attn_debug")
-    if getattr(opt, "truth_ref", "") and getattr(opt, "truth", ""):
+    for flag in ("fastq", "mod_probs", "moves", "truth", "truth_ref"):
+        if getattr(opt, flag) and opt.attn_debug:
+            raise ValueError("-%s is not available together with -attn_debug" % flag)
+    if opt.truth_ref and opt.truth:
         raise ValueError("-truth_ref and -truth exclude each other")
-    if getattr(opt, "consensus", False) and not getattr(opt, "truth_ref", ""):
+    if opt.consensus and not opt.truth_ref:
         raise ValueError("-consensus needs -truth_ref")
-    if getattr(opt, "consensus", False) and getattr(opt, "consensus_min_cov", 5) < 1:
+    if opt.consensus and opt.consensus_min_cov < 1:
         raise ValueError("-consensus_min_cov must be at least 1")
     logger = init_logger(opt.log_file)
-    ASSEMBLY_STATS.update(reads=0, fallback=0)
-    ALIGN_STATS.update(reads=0, fallback=0)
-    MAP_STATS.update(reads=0, segments=0, unmapped=0)
-    TRUTH.update(seqs=accuracy.read_truth(opt.truth) if getattr(opt, "truth", "") else None,
-                 ref=accuracy.read_reference(opt.truth_ref) if getattr(opt, "truth_ref", "") else None,
-                 evaluated=0, missing=0,
-                 match=0, length=0, bases=np.zeros(accuracy.Q_LEVELS, np.int64),
-                 errors=np.zeros(accuracy.Q_LEVELS, np.int64), pile=None)
-    if getattr(opt, "consensus", False):
-        TRUTH["pile"] = accuracy.Pileup(TRUTH["ref"], device=None if getattr(opt, "truth_align", "gpu") == "cpu"
-                                        else max(0, opt.gpu))
+    evaluation = accuracy.Evaluation(opt) if opt.truth or opt.truth_ref else None
+    assembly_stats = {"reads": 0, "fallback": 0}  # -assembly gpu: reads assembled / of them on the host
     for sub in ("", "result", "segment") + (("attention",) if opt.attn_debug else ()):  # translate.py:64-71
         os.makedirs(os.path.join(opt.save_data, sub), exist_ok=True)
     from .translator import build_translator
     translator = build_translator(opt, report_score=False, logger=logger)
-    if getattr(opt, "mod_probs", False):
+    if opt.mod_probs:
         translator._check_supported(mods=True)  # ValueError for a vocabulary without C or M, before any read
     todo, done = list_reads(opt)
     logger.info("%d reads have already translated, remains %d read\n" % (done, len(todo)))
@@ -352,7 +212,7 @@ def main(opt=None):
     ctx = multiprocessing.get_context("spawn")
     t_start = time.time()
     n_done = 0
-    gpu_fe = getattr(opt, "frontend", "cpu") == "gpu"
+    gpu_fe = opt.frontend == "gpu"
     # -pack_reads 0: flush once the pending reads fill the engine batch
     cap = int(getattr(translator, "max_batch", 0) or 256)
     with ctx.Pool(max(1, opt.thread)) as pool:
@@ -367,33 +227,16 @@ def main(opt=None):
             n_chunks += _n_chunks(opt, src, gpu_fe)
             full = len(pending) >= opt.pack_reads if opt.pack_reads > 0 else n_chunks >= cap
             if full:
-                n_done += _run_group(opt, translator, pending, gpu_fe)
+                n_done += _run_group(opt, translator, pending, gpu_fe, evaluation, assembly_stats)
                 pending, n_chunks = [], 0
         if pending:
-            n_done += _run_group(opt, translator, pending, gpu_fe)
+            n_done += _run_group(opt, translator, pending, gpu_fe, evaluation, assembly_stats)
     logger.info("translated %d reads in %.1f s" % (n_done, time.time() - t_start))
-    if getattr(opt, "assembly", "cpu") == "gpu":
+    if opt.assembly == "gpu":
         logger.info("-assembly gpu: %d of %d reads were assembled on the host (fallback: a chunk of 200 or more "
-                    "bases, or text outside ACGTM)" % (ASSEMBLY_STATS["fallback"], ASSEMBLY_STATS["reads"]))
-    if TRUTH["ref"] is not None:
-        if getattr(opt, "fastq", False):
-            with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:
-                f.writelines(accuracy.calibration_lines(TRUTH["bases"], TRUTH["errors"]))
-        logger.info("-truth_ref: %d reads evaluated, %d reads unmapped, %d segments mapped, %d unmapped; pooled "
-                    "identity %.6f (%d matches over %d alignment columns)"
-                    % (TRUTH["evaluated"], TRUTH["missing"], MAP_STATS["segments"] - MAP_STATS["unmapped"],
-                       MAP_STATS["unmapped"], TRUTH["match"] / TRUTH["length"] if TRUTH["length"] else 0.0,
-                       TRUTH["match"], TRUTH["length"]))
-    if TRUTH["pile"] is not None:
-        _write_consensus(opt, logger)
-    if TRUTH["seqs"] is not None:
-        if getattr(opt, "fastq", False):
-            with open(os.path.join(opt.save_data, "quality_calibration.tsv"), "w") as f:
-                f.writelines(accuracy.calibration_lines(TRUTH["bases"], TRUTH["errors"]))
-        logger.info("-truth: %d reads evaluated, %d without a truth, %d host fallbacks (a read or a truth above %d "
-                    "bases); pooled identity %.6f (%d matches over %d alignment columns)"
-                    % (TRUTH["evaluated"], TRUTH["missing"], ALIGN_STATS["fallback"], accuracy.ALIGN_MAX_LEN,
-                       TRUTH["match"] / TRUTH["length"] if TRUTH["length"] else 0.0, TRUTH["match"], TRUTH["length"]))
+                    "bases, or text outside ACGTM)" % (assembly_stats["fallback"], assembly_stats["reads"]))
+    if evaluation is not None:
+        evaluation.finish(opt.save_data, opt.fastq, logger)
     return n_done
 
 
@@ -408,7 +251,10 @@ def _translate_attn(opt, translator, group):
     return outs
 
 
-def _translate_group(opt, translator, group, raw=False):
+def _translate_group(opt, translator, group, evaluation, assembly_stats, raw=False):
+    """One packed group translated and written.  ``evaluation`` (accuracy.Evaluation, or None without -truth and
+    -truth_ref) evaluates the group's reads before they are written and takes a read's entry into its sums once
+    the read is written; ``assembly_stats`` is the run's -assembly gpu count."""
     t0 = time.time()
     mod_probs = bool(getattr(opt, "mod_probs", False))
     fastq = bool(getattr(opt, "fastq", False)) or mod_probs  # the methylation values travel beside the qualities
@@ -443,28 +289,26 @@ def _translate_group(opt, translator, group, raw=False):
         # the whole group in one device call; a read left None (its host fallback raised) is assembled
         # again by write_output, which reports that read's error as -assembly cpu does
         try:
-            seqs = frontend.assemble_reads([o[1] for o in outs], opt.src_seq_length, opt.src_seq_stride,
-                                           device=max(0, opt.gpu), stats=ASSEMBLY_STATS, defer_errors=True,
-                                           **(dict(weights=weights) if fastq else {}),
-                                           **(dict(mod_weights=mods) if mod_probs else {}),
-                                           **(dict(positions=positions) if moves else {}))
+            seqs = list(frontend.assemble_reads([o[1] for o in outs], opt.src_seq_length, opt.src_seq_stride,
+                                                device=max(0, opt.gpu), stats=assembly_stats, defer_errors=True,
+                                                **(dict(weights=weights) if fastq else {}),
+                                                **(dict(mod_weights=mods) if mod_probs else {}),
+                                                **(dict(positions=positions) if moves else {})))
         except Exception as e:
             for g in group:
                 print("!!!error!!!data src: " + g[0].split(".txt")[0] + " (%r)" % (e,))
             return 0
-    if TRUTH["seqs"] is None and TRUTH["ref"] is None:
-        for g, o, seq, w, mw, ps in zip(group, outs, seqs, weights, mods, positions):
-            write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
-                         **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}))
-        return len(group)
-    seqs = list(seqs)
-    acc = _evaluate_group(opt, group, outs, seqs, weights, mods, positions)
+    acc = [None] * len(group)
+    if evaluation is not None:
+        # the reads still None (-assembly cpu) are assembled here; one whose assembly raises stays None:
+        # write_output assembles it again and reports it
+        _assemble_missing(opt, outs, seqs, weights, mods, positions)
+        acc = evaluation.evaluate([g[0].split(".txt")[0] for g in group], seqs, fastq)
     for g, o, seq, w, mw, ps, a in zip(group, outs, seqs, weights, mods, positions, acc):
+        lines = dict(accuracy_line=a.line, paf_lines=a.paf_lines) if a is not None else {}
         if write_output(opt, g[0], o[1], dt * len(o[1]) / total, sequence=seq, weights=w,
-                        **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}),
-                        **(dict(accuracy_line=a[0]) if a else {}),
-                        **(dict(paf_lines=a[4]) if a and len(a) > 4 else {})):
-            _account(a)
+                        **(dict(mods=mw) if mod_probs else {}), **(dict(moves=ps) if moves else {}), **lines) and lines:
+            evaluation.account(a)
     return len(group)
 
 

@@ -415,9 +415,9 @@ hipError_t launch_align_seqs(const unsigned char* call, const int* call_off, con
 }
 
 // rpos == nullptr: nd_align_fit, the instantiation without positions
-static hipError_t launch_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
-                             const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                             int* status, void* work, int* rpos, hipStream_t s) {
+hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
+                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
+                            int* status, int* rpos, void* work, hipStream_t s) {
   if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0 || !call_off ||
       (P > 0 && (!call || !ref || !hit || !counts || !span || !status || !work)))
     return hipErrorInvalidValue;
@@ -435,19 +435,6 @@ static hipError_t launch_fit(const unsigned char* call, const int* call_off, con
     hipLaunchKernelGGL((align_kernel<true, false>), dim3(P), dim3(ALN_THREADS), 0, s, call, call_off, ref, hit, off,
                        capacity, dirs, counts, ops, status, span, ref_len, (int*)nullptr);
   return hipGetLastError();
-}
-
-hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
-                            const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                            int* status, void* work, hipStream_t s) {
-  return launch_fit(call, call_off, ref, ref_len, hit, P, cells, counts, span, ops, status, work, nullptr, s);
-}
-
-hipError_t launch_align_fit_pos(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
-                                const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                                int* status, int* rpos, void* work, hipStream_t s) {
-  if (P > 0 && !rpos) return hipErrorInvalidValue;
-  return launch_fit(call, call_off, ref, ref_len, hit, P, cells, counts, span, ops, status, work, rpos, s);
 }
 
 }  // namespace nd

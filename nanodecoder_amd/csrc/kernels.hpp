@@ -479,15 +479,12 @@ hipError_t launch_locate_segs(const unsigned char* call, const int* call_off, in
 // the fit form of the alignment (align.hip): pair p is call[call_off[p] .. call_off[p+1]) against ref[hit[p][1] ..
 // hit[p][2]) with free ends on the reference side; a pair whose status has bit 0 set on entry is skipped; span
 // [P, 2] = the aligned reference interval in ref's coordinates; status bit 1: cells understated, bit 2: a side
-// above ALIGN_MAX_LEN or a window outside [0, ref_len]
+// above ALIGN_MAX_LEN or a window outside [0, ref_len].  rpos (nullable: the form without positions) is one more
+// output: rpos [call_off[P]] = the reference position of every oriented call base (the base matched or mismatched
+// to; for an inserted base the one to its left), -1 for a pair that is not aligned
 hipError_t launch_align_fit(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
                             const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                            int* status, void* work, hipStream_t s);
-// the fit form with one more output: rpos [call_off[P]] = the reference position of every oriented call base (the
-// base matched or mismatched to; for an inserted base the one to its left), -1 for a pair that is not aligned
-hipError_t launch_align_fit_pos(const unsigned char* call, const int* call_off, const unsigned char* ref, int ref_len,
-                                const int* hit, int P, long long cells, int* counts, int* span, unsigned char* ops,
-                                int* status, int* rpos, void* work, hipStream_t s);
+                            int* status, int* rpos, void* work, hipStream_t s);
 // consensus of the mapped reads (pileup.hip states the rule): pile [9, ref_len] u32, planes A, C, G, T, D, iA, iC,
 // iG, iT; add piles the pairs of status 0 by their ops and rpos (one launch), call reads the pile into cons, ins
 // (u8, 255 = none), cov and rec [R, 6] = {called, match, sub, del, ins, cov_sum}, which it zeroes itself

@@ -409,19 +409,36 @@ int64_t nd_align_seqs_work_bytes(int32_t P, int64_t cells) {
   return P >= 0 && cells >= 0 && cells <= ALIGN_MAX_CELLS ? (int64_t)nd::align_work_bytes(P, cells) : -1;
 }
 
-int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_t* d_truth,
-                  const int32_t* d_truth_off, int32_t P, int64_t cells, int32_t* d_counts, uint8_t* d_ops,
-                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
-  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS)
-    return fail(ND_ERR_ARG, "align_seqs: P and cells must be >= 0 and cells <= 2^60");
+// The argument checks of nd_align_seqs, nd_align_fit and nd_align_fit_pos, in the order every one of them tests:
+// the sizes (``ref_len`` null for nd_align_seqs, which has none), P == 0 (ND_OK, nothing to launch), the work
+// area's size, the required buffers (``d_work`` among them) and the work area's alignment.  ``launch`` is set
+// when the entry is to go on.
+static int align_check(const char* entry, const int32_t* ref_len, int32_t P, int64_t cells, int64_t work_bytes,
+                       const void* d_work, std::initializer_list<const void*> required, bool& launch) {
+  const std::string name(entry);
+  launch = false;
+  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || (ref_len && *ref_len < 0))
+    return fail(ND_ERR_ARG, name + (ref_len ? ": P, cells and ref_len" : ": P and cells") +
+                                " must be >= 0 and cells <= 2^60");
   if (P == 0) return ND_OK;
   const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
   if (work_bytes < need)
-    return fail(ND_ERR_ARG, "align_seqs: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_align_seqs_work_bytes asks for");
-  if (!d_call || !d_call_off || !d_truth || !d_truth_off || !d_counts || !d_status || !d_work)
-    return fail(ND_ERR_ARG, "align_seqs: null buffer");
-  if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_seqs: d_work must be 8-byte aligned");
+    return fail(ND_ERR_ARG, name + ": work_bytes " + std::to_string(work_bytes) + " below the " +
+                                std::to_string(need) + " nd_" + name + "_work_bytes asks for");
+  for (const void* b : required)
+    if (!b) return fail(ND_ERR_ARG, name + ": null buffer");
+  if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, name + ": d_work must be 8-byte aligned");
+  launch = true;
+  return ND_OK;
+}
+
+int nd_align_seqs(const uint8_t* d_call, const int32_t* d_call_off, const uint8_t* d_truth,
+                  const int32_t* d_truth_off, int32_t P, int64_t cells, int32_t* d_counts, uint8_t* d_ops,
+                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
+  bool launch;
+  const int rc = align_check("align_seqs", nullptr, P, cells, work_bytes, d_work,
+                             {d_call, d_call_off, d_truth, d_truth_off, d_counts, d_status, d_work}, launch);
+  if (!launch) return rc;
   return status("align_seqs", nd::launch_align_seqs(d_call, d_call_off, d_truth, d_truth_off, P, cells, d_counts,
                                                     d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
 }
@@ -444,18 +461,13 @@ int64_t nd_align_fit_work_bytes(int32_t P, int64_t cells) { return nd_align_seqs
 int nd_align_fit(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ref, int32_t ref_len,
                  const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span, uint8_t* d_ops,
                  int32_t* d_status, void* d_work, int64_t work_bytes, void* stream) {
-  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0)
-    return fail(ND_ERR_ARG, "align_fit: P, cells and ref_len must be >= 0 and cells <= 2^60");
-  if (P == 0) return ND_OK;
-  const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "align_fit: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_align_fit_work_bytes asks for");
-  if (!d_call_or || !d_call_off || !d_ref || !d_hit || !d_counts || !d_span || !d_status || !d_work)
-    return fail(ND_ERR_ARG, "align_fit: null buffer");
-  if (reinterpret_cast<uintptr_t>(d_work) & 7) return fail(ND_ERR_ARG, "align_fit: d_work must be 8-byte aligned");
+  bool launch;
+  const int rc = align_check("align_fit", &ref_len, P, cells, work_bytes, d_work,
+                             {d_call_or, d_call_off, d_ref, d_hit, d_counts, d_span, d_status, d_work}, launch);
+  if (!launch) return rc;
   return status("align_fit", nd::launch_align_fit(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells, d_counts,
-                                                  d_span, d_ops, d_status, d_work, (hipStream_t)stream), ND_ERR_HIP);
+                                                  d_span, d_ops, d_status, nullptr, d_work, (hipStream_t)stream),
+                ND_ERR_HIP);
 }
 
 int64_t nd_align_fit_pos_work_bytes(int32_t P, int64_t cells) { return nd_align_seqs_work_bytes(P, cells); }
@@ -464,20 +476,13 @@ int nd_align_fit_pos(const uint8_t* d_call_or, const int32_t* d_call_off, const 
                      const int32_t* d_hit, int32_t P, int64_t cells, int32_t* d_counts, int32_t* d_span,
                      uint8_t* d_ops, int32_t* d_rpos, int32_t* d_status, void* d_work, int64_t work_bytes,
                      void* stream) {
-  if (P < 0 || cells < 0 || cells > ALIGN_MAX_CELLS || ref_len < 0)
-    return fail(ND_ERR_ARG, "align_fit_pos: P, cells and ref_len must be >= 0 and cells <= 2^60");
-  if (P == 0) return ND_OK;
-  const int64_t need = (int64_t)nd::align_work_bytes(P, cells);
-  if (work_bytes < need)
-    return fail(ND_ERR_ARG, "align_fit_pos: work_bytes " + std::to_string(work_bytes) + " below the " +
-                                std::to_string(need) + " nd_align_fit_pos_work_bytes asks for");
-  if (!d_call_or || !d_call_off || !d_ref || !d_hit || !d_counts || !d_span || !d_rpos || !d_status || !d_work)
-    return fail(ND_ERR_ARG, "align_fit_pos: null buffer");
-  if (reinterpret_cast<uintptr_t>(d_work) & 7)
-    return fail(ND_ERR_ARG, "align_fit_pos: d_work must be 8-byte aligned");
-  return status("align_fit_pos", nd::launch_align_fit_pos(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells,
-                                                          d_counts, d_span, d_ops, d_status, d_rpos, d_work,
-                                                          (hipStream_t)stream), ND_ERR_HIP);
+  bool launch;  // d_rpos is required here: the launcher takes a null one for the form without positions
+  const int rc = align_check("align_fit_pos", &ref_len, P, cells, work_bytes, d_work,
+                             {d_call_or, d_call_off, d_ref, d_hit, d_counts, d_span, d_rpos, d_status, d_work}, launch);
+  if (!launch) return rc;
+  return status("align_fit_pos", nd::launch_align_fit(d_call_or, d_call_off, d_ref, ref_len, d_hit, P, cells,
+                                                      d_counts, d_span, d_ops, d_status, d_rpos, d_work,
+                                                      (hipStream_t)stream), ND_ERR_HIP);
 }
 
 int nd_pileup_add(const uint8_t* d_call_or, const int32_t* d_call_off, const uint8_t* d_ops, const int32_t* d_rpos,

@@ -141,6 +141,26 @@ def test_read_truth(tmp_path):
     assert accuracy.normalise("acMmT") == "ACCCT"
 
 
+def test_fasta_records(tmp_path):
+    f = tmp_path / "records.fasta"
+    f.write_text("; a comment before the first record\n>read1 some description\nacgt\nACMm\n\nTT\n>read2\n"
+                 "GGCC\n>empty\n>read3\tx\nnnA\n>\nac\n>read2 again\n\ntt\nM\n")
+    records = [("read1", "ACGTACCCTT"), ("read2", "GGCC"), ("empty", ""), ("read3", "NNA"), ("", "AC"),
+               ("read2", "TTC")]
+    assert list(accuracy.fasta_records(str(f))) == records
+    # a repeated name: the last record for read_truth, a record of its own for read_reference
+    assert accuracy.read_truth(str(f)) == {"read1": "ACGTACCCTT", "read2": "TTC", "empty": "", "read3": "NNA",
+                                           "": "AC"}
+    ref = accuracy.read_reference(str(f))
+    assert ref.names == [n for n, _ in records] and ref.seq.tobytes() == "".join(s for _, s in records).encode()
+    assert ref.rec_off.tolist() == [0, 10, 14, 14, 17, 19, 22]
+    f.write_text("junk\n>chr1 first\nacgt\nACMm\n>chr2\nGGNN\n\nTT\n>chr1\nAC\n")  # test_read_reference's file
+    assert list(accuracy.fasta_records(str(f))) == [("chr1", "ACGTACCC"), ("chr2", "GGNNTT"), ("chr1", "AC")]
+    f.write_text("no header at all\nACGT\n")
+    assert list(accuracy.fasta_records(str(f))) == [] and accuracy.read_truth(str(f)) == {}
+    assert accuracy.read_reference(str(f)).names == [] and accuracy.read_reference(str(f)).total == 0
+
+
 def test_quality_table_and_empirical_q():
     #        Q: 0    1    1    40   40   40
     quals = "!" + '"' + '"' + "III"

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from nanodecoder_amd import accuracy, cli, opts
-from tests.test_accuracy_host import _Eng, fasta_sequence, make_reads, mutate, random_seq
+from tests.test_accuracy_host import (_Eng, fasta_sequence, host_pairs, make_reads, mutate, plain_align,
+                                      random_seq)
 
 A = accuracy
 
@@ -307,6 +308,62 @@ def test_map_reads_host_path(planted):
     assert [int(v) for v in line[1:4]] == [len(calls[1]), 0, len(calls[1])] and int(line[6]) == 25000
     assert [int(line[7]), int(line[8])] == [r[4] - 35000, r[5] - 35000]
     assert int(line[9]) == r[7][1] and int(line[10]) == int(r[7][1:].sum()) and line[12] == "vt:i:%d" % r[6]
+
+
+def test_map_host_is_map_reads_of_one_call_and_records_have_names():
+    rng = np.random.default_rng(41)
+    seqs = [random_seq(rng, 2500), random_seq(rng, 1500)]
+    ref = A.Reference(["a", "b"], seqs)
+    calls = [mutate(rng, seqs[0][700:1100], 0.1),
+             A.reverse_complement(mutate(rng, seqs[1][300:800], 0.1)).tobytes().decode(),
+             random_seq(rng, 300), "ACGT", ""]
+    n_records = 0
+    for c in calls:
+        counts, recs, ops = A.map_host(c, ref)
+        rc, rr, ro = A.map_reads([c], ref, want_ops=True)
+        assert counts.dtype == np.int32 and counts.tolist() == rc[0].tolist() and len(rc) == len(rr) == len(ro) == 1
+        assert ops.dtype == np.uint8 and ops.tobytes() == ro[0].tobytes() and ops.size == len(c)
+        assert [(r[:7], r[7].tolist()) for r in recs] == [(r[:7], r[7].tolist()) for r in rr[0]]
+        for r in recs:
+            n_records += 1
+            assert isinstance(r, tuple) and len(r) == 8 and A.Segment._fields == (
+                "seg_start", "seg_end", "strand", "rec", "ref_start", "ref_end", "votes", "counts")
+            assert (r.seg_start, r.seg_end, r.strand, r.rec, r.ref_start, r.ref_end, r.votes) == r[:7]
+            assert r.counts is r[7] and r.counts.dtype == np.int32
+    assert n_records == 2 and [bool(A.map_host(c, ref)[1]) for c in calls] == [True, True, False, False, False]
+
+
+# ---------------------------------------------------------------- one DP for the global and the fit form
+def dp_pairs(seed=17):
+    """host_pairs(), FIT_FIXED and 200 seeded pairs of a two-letter alphabet (ties everywhere), lengths 0..40."""
+    rng = np.random.default_rng(seed)
+    pairs = host_pairs() + FIT_FIXED
+    for _ in range(200):
+        n, m = (int(v) for v in rng.integers(0, 41, 2))
+        pairs.append((random_seq(rng, n, "AC"), random_seq(rng, m, "AC")))
+    return pairs
+
+
+def test_one_dp_equals_both_plain_tables():
+    pairs = dp_pairs()
+    assert any(not a and b for a, b in pairs) and any(a and not b for a, b in pairs)
+    assert sum(len(a) > len(b) for a, b in pairs[-200:]) > 50 and ("", "") in pairs
+    for call, truth in pairs:
+        counts, ops = A.align_host(call, truth)
+        assert counts.dtype == np.int32 and ops.dtype == np.uint8
+        assert [counts.tolist(), ops.tolist()] == list(plain_align(call, truth)), (call, truth)
+        counts, span, ops = A.fit_host(call, truth)
+        assert counts.dtype == np.int32 and ops.dtype == np.uint8
+        assert (counts.tolist(), tuple(span), ops.tolist()) == plain_fit(call, truth), (call, truth)
+        pc, ps, po, rpos = A.fit_pos_host(call, truth, 100)
+        assert (pc.tolist(), tuple(ps), po.tolist()) == (counts.tolist(), tuple(span), ops.tolist())
+        assert rpos.dtype == np.int32 and rpos.size == len(call)
+        # the positions: from the span's start to its end, a diagonal base past the one before, an inserted one not
+        last = 100 + span[0] - 1
+        for o, r in zip(po.tolist(), rpos.tolist()):
+            assert r >= last if o == 2 else r > last
+            last = r
+        assert last == 100 + span[1] - 1 or not len(call)
 
 
 # ---------------------------------------------------------------- translate.py -truth_ref
