@@ -281,10 +281,10 @@ def _translate_group(opt, translator, group, evaluation, assembly_stats, raw=Fal
     dt = time.time() - t0
     total = max(1, sum(len(o[1]) for o in outs))
     seqs = [None] * len(outs)
-    weights = [o[2] for o in outs] if fastq else [None] * len(outs)  # -fastq: per chunk, its bases' weights
-    mods = [o[3] for o in outs] if mod_probs else [None] * len(outs)  # -mod_probs: their modification weights
-    # -moves: their chunk-relative signal positions, the last entry
-    positions = [o[2 + int(fastq) + int(mod_probs)] for o in outs] if moves else [None] * len(outs)
+    # per read: with -fastq per chunk its bases' weights, with -mod_probs their modification weights, with -moves
+    # their chunk-relative signal positions; None for what was not asked
+    parts = [translator.split_result(o, **want) for o in outs]
+    weights, mods, positions = ([p[k] for p in parts] for k in (2, 3, 4))
     if getattr(opt, "assembly", "cpu") == "gpu":
         # the whole group in one device call; a read left None (its host fallback raised) is assembled
         # again by write_output, which reports that read's error as -assembly cpu does

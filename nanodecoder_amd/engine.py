@@ -112,6 +112,14 @@ class Engine:
             self._ext = torch.cuda.ExternalStream(self._L.nd_stream(self._h), device=self.device)
         return self._ext
 
+    def stream_of(self, result) -> torch.cuda.Stream:
+        """The stream ``result``'s call ran on: the caller's current stream, which every call joins."""
+        return torch.cuda.current_stream(self.device)
+
+    def next_stream(self) -> torch.cuda.Stream:
+        """The stream the next call will run on (as stream_of)."""
+        return torch.cuda.current_stream(self.device)
+
     def set_ctx_path(self, path: int):
         """0: memory-bank context attention for greedy (default), 1: per-layer K/V always."""
         _lib.check(self._L.nd_set_ctx_path(self._h, int(path)), "nd_set_ctx_path")
@@ -513,6 +521,14 @@ class EnginePool:
         """Order ``stream`` (default: the current stream) after ``result``'s call."""
         (stream or torch.cuda.current_stream()).wait_event(result["event"])
         return result
+
+    def stream_of(self, result) -> torch.cuda.Stream:
+        """The stream ``result``'s call ran on: its lane's."""
+        return self.engines[result["lane"]].stream
+
+    def next_stream(self) -> torch.cuda.Stream:
+        """The stream the next call will run on: the next lane's."""
+        return self.engines[self._next].stream
 
     def translate_greedy(self, signal, lengths, spans=None, **kw):
         return self._call("translate_greedy", signal, lengths, spans, **kw)

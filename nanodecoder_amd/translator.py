@@ -23,9 +23,11 @@ per-chunk results, far higher throughput than one read at a time).
 """
 from __future__ import annotations
 
+import collections
+import contextlib
 import json
 import os
-from typing import Iterable, List, Optional, Sequence
+from typing import Iterable, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -34,6 +36,8 @@ from . import checkpoint
 from .engine import Engine
 from .engine import Engine as _HipEngine  # the real engine class (tests substitute Engine)
 from .engine import EnginePool
+
+_REAL_ENGINES = (_HipEngine, EnginePool)
 
 
 class GNMTGlobalScorer:
@@ -45,6 +49,49 @@ class GNMTGlobalScorer:
         self.beta = float(getattr(opt, "beta", 0.0))
         self.length_penalty = str(getattr(opt, "length_penalty", "none") or "none")
         self.coverage_penalty = str(getattr(opt, "coverage_penalty", "none") or "none")
+
+
+class Request(NamedTuple):
+    """What one public call was asked to return beside each chunk's scores and tokens: the attention rows
+    (``attn_debug``), the token weights of the best hypothesis (``qualities``), their modification weights
+    (``mods``) and the tokens' signal positions (``moves``).  Translator._request builds it, every job carries
+    it.  ``join`` and ``split`` are the one place that knows the layout of a result, per chunk and per read
+    alike: (scores, predictions), then of weights, modification weights and positions, in this order, those
+    that were asked."""
+    attn: bool = False
+    weights: bool = False
+    mods: bool = False
+    positions: bool = False
+
+    def asked(self, weights, mod_weights, positions) -> tuple:
+        """Of one value per optional output, those of the outputs that were asked, in the layout's order."""
+        return tuple(v for v, on in zip((weights, mod_weights, positions), self[1:]) if on)
+
+    def join(self, scores, predictions, weights, mod_weights, positions):
+        return (scores, predictions) + self.asked(weights, mod_weights, positions)
+
+    def split(self, result):
+        """(scores, predictions, weights, mod_weights, positions) of a result, None for what was not asked."""
+        rest = iter(result[2:])
+        return (result[0], result[1]) + tuple(next(rest) if on else None for on in self[1:])
+
+
+def _asked(**flags):
+    """The keywords of ``flags`` that are set, each as True.  Optional outputs cross to the engine object only
+    this way: a call that was not asked for one passes exactly the keywords it always has (the stand-in
+    engines of the host tests take no others)."""
+    return {k: True for k, on in flags.items() if on}
+
+
+def _lane(r):
+    """The ``lane=`` keyword of token_weights / token_mod_weights / token_positions for the result ``r`` of an
+    EnginePool call, so they follow that call on its lane's stream; nothing for a single Engine."""
+    return {"lane": r["lane"]} if "lane" in r else {}
+
+
+def _flagged(overflow) -> bool:
+    """Is a call's overflow word (nd_take_overflow; None where the engine has none) set?"""
+    return overflow is not None and int(overflow.reshape(-1)[0]) != 0
 
 
 def parse_chunk(c) -> np.ndarray:
@@ -176,6 +223,26 @@ class Translator(object):
         # batch carries text src (translation.py:42-47), which nano data never
         # does (src is None, :73-81), so predictions are unchanged
 
+    def _request(self, attn_debug: bool = False, qualities: bool = False, mods: bool = False,
+                 moves: bool = False) -> Request:
+        """The Request of one public call, after the refusals: qualities or positions together with
+        attn_debug, ``mods`` without C and M in the vocabulary, beam qualities on an average-attention
+        decoder.  ``mods`` implies ``qualities`` here, and nowhere else."""
+        qualities = bool(qualities or mods)  # the methylation values travel beside the qualities
+        if qualities:
+            if attn_debug:
+                raise ValueError("qualities are not available together with attn_debug")
+            self._check_supported(qualities=True, mods=bool(mods))
+        if moves and attn_debug:
+            raise ValueError("signal positions are not available together with attn_debug")
+        return Request(bool(attn_debug), qualities, bool(mods), bool(moves))
+
+    def split_result(self, result, qualities: bool = False, mods: bool = False, moves: bool = False):
+        """(scores, predictions, weights, mod_weights, positions) of one read's result from translate_reads /
+        translate_raw_reads (or of one chunk's from stream_reads) called with the same ``qualities``, ``mods``
+        and ``moves``; None for what was not asked."""
+        return self._request(qualities=qualities, mods=mods, moves=moves).split(result)
+
     def setAttnFile(self, out_file_attn):
         self.out_file_attn = out_file_attn
 
@@ -202,60 +269,67 @@ class Translator(object):
         return sig_t.numpy(), L_t.numpy(), S_t.numpy(), (sig_t, L_t, S_t)
 
     def _real_engine(self) -> bool:
-        return isinstance(self.engine, (_HipEngine, EnginePool))
+        return isinstance(self.engine, _REAL_ENGINES)
 
     def _depth(self) -> int:
         """Engine calls kept in flight by stream_reads: one per EnginePool lane."""
         return max(1, int(getattr(self.engine, "lanes", 1)))
 
-    def _submit(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
-                attn: bool = False, qual: bool = False, mods: bool = False, moves: bool = False):
-        """Stage up to max_batch chunks with their reference spans (and, for
-        the classic Beam, their reference batch ids) and enqueue the engine
-        call.  Greedy and sampling calls return before the device finishes;
-        ``_finish`` collects the results.  ``qual``: the token weights of each
-        chunk's best hypothesis are wanted too, ``mods`` (with ``qual``) their
-        modification weights as well, ``moves`` the tokens' signal positions
-        (see stream_reads)."""
-        n = len(chunks)
-        lens = np.array([len(c) for c in chunks], np.int32)
-        if (lens < 1).any():
-            raise ValueError("empty signal chunk")
+    def _batch_dims(self, n: int, spans, cap: Optional[int] = None):
+        """(B, T, spans as int32) of an engine batch of n chunks: T the longest span rounded up to 64 samples,
+        B the bucket of n under ``cap`` (max_batch when not given)."""
         spans = np.asarray(spans, np.int32)
         if spans.max() > self.engine.max_src_len:
             raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
         T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
-        B = _bucket(n, self.engine.max_batch)
+        return _bucket(n, cap or self.engine.max_batch), T, spans
+
+    def _pack(self, chunks: List[np.ndarray], spans: Sequence[int], cap: Optional[int] = None):
+        """Stage one engine batch (_stage): the chunks with their reference spans in its first rows.  Returns
+        what the engine gets, signal [B, T], chunk lengths [B] and spans [B] (pinned tensors for a real
+        engine), then B and the chunk lengths as numpy."""
+        n = len(chunks)
+        lens = np.array([len(c) for c in chunks], np.int32)
+        if (lens < 1).any():
+            raise ValueError("empty signal chunk")
+        B, T, spans = self._batch_dims(n, spans, cap)
         sig, L, S, dev_in = self._stage(B, T)
         for i, c in enumerate(chunks):
             sig[i, : len(c)] = c
         L[:n], S[:n] = lens, spans
         if dev_in is not None:
             sig, L, S = dev_in
-        job = self._enqueue(sig, L, S, B, n, lens, groups, attn, dev_in, qual, **({"mods": True} if mods else {}),
-                            **({"moves": True} if moves else {}))
-        job["again"] = lambda: self._submit(chunks, spans, groups, attn, qual, mods, moves)
+        return sig, L, S, B, lens
+
+    def _submit(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
+                req: Request = Request()):
+        """Stage up to max_batch chunks with their reference spans (and, for
+        the classic Beam, their reference batch ids) and enqueue the engine
+        call.  Greedy and sampling calls return before the device finishes;
+        ``_finish`` collects the results, those ``req`` asks for among them
+        (see stream_reads)."""
+        sig, L, S, B, lens = self._pack(chunks, spans)
+        job = self._enqueue(sig, L, S, B, len(chunks), lens, groups, req, (sig, L, S))
+        job["again"] = lambda: self._submit(chunks, spans, groups, req)
         return job
 
-    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, attn: bool, inputs, qual: bool = False,
-                 mods: bool = False, moves: bool = False):
+    def _enqueue(self, sig, L, S, B: int, n: int, lens: np.ndarray, groups, req: Request, inputs):
         """The engine call for one staged batch (signal [B, T], chunk lengths
         and spans [B]; the first n rows are chunks), its results copied to
-        pinned host buffers on the call's own stream.  ``qual``: a greedy or
-        sampling call also returns its log-probs and the chosen tokens'
-        weights (nd_token_weights) follow it on its stream; a beam call's
-        inputs are kept for the scoring pass of ``_beam_weights``.  ``mods``:
-        the tokens' modification weights (nd_token_mod_weights) follow the
-        weights, from the same log-probs.  ``moves``: the call also returns
-        its attention, the tokens' positions (nd_token_positions, of
-        hypothesis 0 for a beam call) follow it on its stream, and only those
-        [B, S] positions are copied out, not the attention."""
-        job = dict(n=n, lens=lens, attn=attn, B=B, inputs=inputs, qual=qual, mods=mods, moves=moves)
-        if moves:
-            attn = True  # the engine call's return_attn; job["attn"] stays what the caller asked for
-        # without qualities the engine sees exactly the arguments it always has
-        want = dict(return_logp=True) if qual else {}
+        pinned host buffers on the call's own stream.  ``req.weights``: a
+        greedy or sampling call also returns its log-probs and the chosen
+        tokens' weights (nd_token_weights) follow it on its stream; a beam
+        call's inputs are kept for the scoring pass of ``_beam_weights``.
+        ``req.mods``: the tokens' modification weights (nd_token_mod_weights)
+        follow the weights, from the same log-probs.  ``req.positions``: the
+        call also returns its attention, the tokens' positions
+        (nd_token_positions, of hypothesis 0 for a beam call) follow it on its
+        stream, and only those [B, S] positions are copied out, not the
+        attention."""
+        job = dict(n=n, lens=lens, req=req, B=B, inputs=inputs)
+        attn = req.attn or req.positions  # the engine call's return_attn
         if self.beam_size == 1:
+            want = _asked(return_logp=req.weights)
             if not (self.random_sampling_temp == 0.0 or self.sample_from_topk == 1):
                 # sample_with_temperature's random branch (translator.py:376-393)
                 self._draws += 1
@@ -266,12 +340,11 @@ class Translator(object):
             else:
                 r = self.engine.translate_greedy(sig, L, S, max_len=self.max_length, min_len=self.min_length,
                                                  return_attn=attn, **want)
-            if qual:
-                lane = {"lane": r["lane"]} if "lane" in r else {}
-                r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"], **lane)
-                if mods:
-                    r["mod_weights"] = self.engine.token_mod_weights(r["tokens"], r["logp"], *self._cm_ids(), **lane)
-            if moves:
+            if req.weights:
+                r["weights"] = self.engine.token_weights(r["tokens"], logp=r["logp"], **_lane(r))
+            if req.mods:
+                r["mod_weights"] = self.engine.token_mod_weights(r["tokens"], r["logp"], *self._cm_ids(), **_lane(r))
+            if req.positions:
                 self._positions(r, S)
             job.update(kind="greedy", r=r)
         else:
@@ -307,10 +380,10 @@ class Translator(object):
                     alpha=gs.alpha, max_len=self.max_length, min_len=self.min_length,
                     coverage_penalty=gs.coverage_penalty, beta=gs.beta, stepwise_penalty=self.stepwise_penalty,
                     block_ngram_repeat=self.block_ngram_repeat, ignore_ids=exclusion, cut=cut, return_attn=attn)
-            if moves:
+            if req.positions:
                 self._positions(r, S, hyp0=True)
             job.update(kind="beam", r=r, grp=grp, sorted_rows=sorted_rows, cut=cut)
-            if qual:
+            if req.weights:
                 job["eng_in"] = (sig, L, S)
         if self._real_engine():
             self._copy_out(job)
@@ -322,8 +395,7 @@ class Translator(object):
         """The token positions [B, S] of a call's result ``r`` (Engine.token_positions on the call's stream, its
         EnginePool lane), in r["positions"]; the attention they came from is dropped from the result, so it is
         not copied to the host."""
-        lane = {"lane": r["lane"]} if "lane" in r else {}
-        r["positions"] = self.engine.token_positions(r["attn"], spans, hyp0=hyp0, **lane)
+        r["positions"] = self.engine.token_positions(r["attn"], spans, hyp0=hyp0, **_lane(r))
         r["attn"] = None
 
     def _cm_ids(self):
@@ -336,8 +408,7 @@ class Translator(object):
         stream the single Engine joined), then an event: ``_host`` waits on
         that event alone, never on calls submitted after this one."""
         r = job["r"]
-        st = self.engine.engines[r["lane"]].stream if "lane" in r else \
-            torch.cuda.current_stream(self.engine.device)
+        st = self.engine.stream_of(r)
         host = {}
         with torch.cuda.stream(st):
             for k in self._HOST_KEYS:
@@ -360,95 +431,101 @@ class Translator(object):
         r = job["r"]  # stand-in engines: host tensors
         return [None if r.get(k) is None else r[k].cpu().numpy() for k in names]
 
-    def _rerun_exact(self, job, finish=None):
+    @contextlib.contextmanager
+    def _exact_fp32(self):
         """Split-fp16 range guard (nd_take_overflow): a call in which some
         split activation reached |x| >= 65504 (fp16's range; the reference's
-        fp32 is still finite there) runs again with every product in exact
-        fp32, and its results replace the flagged ones."""
+        fp32 is still finite there) runs again inside this block, with every
+        product in exact fp32, and its results replace the flagged ones.  The
+        mode is switched off again however the block ends."""
         self.engine.set_exact_fp32(True)
         try:
-            again = job["again"]()
-            again["exact"] = True
-            return (finish or self._finish)(again)
+            yield
         finally:
             self.engine.set_exact_fp32(False)
 
-    def _overflowed(self, job, ov):
-        return ov is not None and int(ov.reshape(-1)[0]) != 0 and not job.get("exact")
+    def _run_guarded(self, call, exact: bool = False):
+        """The result of the engine call ``call()`` once the device has finished it, under the range guard
+        (_exact_fp32): a flagged call runs once more in exact fp32, unless ``exact`` says that the mode is on
+        already."""
+        def run():
+            r = call()
+            if "event" in r:  # an EnginePool call returns before its outputs exist
+                r["event"].synchronize()
+            return r
+        r = run()
+        if _flagged(r.get("overflow")) and not exact:
+            with self._exact_fp32():
+                r = run()
+        return r
 
-    def _finish(self, job):
-        """Per chunk (scores[n_best], token lists[n_best]) and, with ``attn``,
-        the attention rows of each hypothesis ([steps, cut] arrays, cut as the
-        reference's results["attention"] has it)."""
-        n, lens, attn = job["n"], job["lens"], job["attn"]
-        qual, mods = job.get("qual", False), job.get("mods", False)
-        out = []
-        if job["kind"] == "greedy":
-            tok, sc, at, ov = self._host(job, "tokens", "scores", "attn", "overflow")
-            if self._overflowed(job, ov):
-                return self._rerun_exact(job)
-            moves = job.get("moves", False)
-            ps = self._host(job, "positions")[0] if moves else None
-            tail = (lambda i: (self._char_weights(tok[i].tolist(), ps[i], np.int32),)) if moves else (lambda i: ())
-            if qual:
-                w = self._host(job, "weights")[0].view(np.uint16)
-                if mods:
-                    mw = self._host(job, "mod_weights")[0].view(np.uint16)
-                    return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i]),
-                             self._char_weights(tok[i].tolist(), mw[i])) + tail(i) for i in range(n)]
-                return [([float(sc[i])], [tok[i].tolist()], self._char_weights(tok[i].tolist(), w[i])) + tail(i)
-                        for i in range(n)]
-            if moves:
-                return [([float(sc[i])], [tok[i].tolist()]) + tail(i) for i in range(n)]
-            for i in range(n):
-                if attn:  # results["attention"]: rows cut at the chunk's length (translator.py:491-501)
-                    out.append(([float(sc[i])], [tok[i].tolist()], [at[i, :, : lens[i]]]))
-                else:
-                    out.append(([float(sc[i])], [tok[i].tolist()]))
-            return out
-        grp, sorted_rows, cut, beam = job["grp"], job["sorted_rows"], job["cut"], self.beam_size
+    def _finish(self, job, arrays: bool = False):
+        """Per chunk (scores[n_best], token lists[n_best]), then what the call's Request asked for: the best
+        hypothesis' weights, modification weights and positions, each spread over the characters of its string
+        (_char_weights), or with ``attn`` the attention rows of each hypothesis ([steps, cut] arrays, cut as
+        the reference's results["attention"] has it).  ``arrays`` (greedy / sampling): the columns themselves
+        instead, (tokens [n, S], scores [n]) numpy, then one [n, S] array per token for each output asked:
+        weights and modification weights uint16, positions int32."""
+        n, req, beam = job["n"], job["req"], job["kind"] == "beam"
         tok, sc, ln, at, done, ov = self._host(job, "tokens", "scores", "lens", "attn", "done_step", "overflow")
-        if self._overflowed(job, ov):
-            return self._rerun_exact(job)
-        w = self._beam_weights(job, tok, ln) if qual else None
-        if mods:
-            w, mw = w
-        ps = self._host(job, "positions")[0] if job.get("moves") else None
+        if _flagged(ov) and not job.get("exact"):
+            # range guard: the whole call again, and all that follows from it (a rerun never reruns again)
+            with self._exact_fp32():
+                again = job["again"]()
+                again["exact"] = True
+                return self._finish(again, arrays)
+        w = mw = ps = None
+        if req.weights:
+            w, mw = self._beam_weights(job, tok, ln) if beam else self._host(job, "weights", "mod_weights")
+            w, mw = w.view(np.uint16), mw.view(np.uint16) if req.mods else None
+        if req.positions:
+            ps = self._host(job, "positions")[0]
+        cols = req.asked((w, np.uint16), (mw, np.uint16), (ps, np.int32))
+        if arrays:
+            return (tok[:n], sc[:n]) + tuple(a[:n] for a, _ in cols)
+        out = []
         for i in range(n):
-            o = ([float(sc[i, k]) for k in range(self.n_best)],
-                 [tok[i, k, : ln[i, k]].tolist() for k in range(self.n_best)])
-            if qual:
-                o = o + (self._char_weights(o[1][0], w[i]),)
-            if mods:
-                o = o + (self._char_weights(o[1][0], mw[i]),)
-            if ps is not None:
-                o = o + (self._char_weights(o[1][0], ps[i], np.int32),)
-            if attn:
-                atts = []
-                for k in range(self.n_best):
-                    if self.fast:
-                        # translator.py:780-790: attention[:, i, j, :memory_lengths[i]] with i the
-                        # chunk's index among the batches alive at the hypothesis' last step
-                        step = int(ln[i, k]) - 1
-                        alive = [q for q in sorted_rows[int(grp[i])] if done[q] == 0 or done[q] > step]
-                        c = int(lens[alive[alive.index(i) // beam]])
-                    else:
-                        c = int(cut[i])
-                    atts.append(at[i, k, : ln[i, k], :c])
-                o = o + (atts,)
+            if beam:
+                o = ([float(sc[i, k]) for k in range(self.n_best)],
+                     [tok[i, k, : ln[i, k]].tolist() for k in range(self.n_best)])
+            else:
+                o = ([float(sc[i])], [tok[i].tolist()])
+            if cols:
+                o += tuple(self._char_weights(o[1][0], a[i], dtype) for a, dtype in cols)
+            if req.attn:
+                o += (self._attn_rows(job, i, at, ln, done),)
             out.append(o)
         return out
 
+    def _attn_rows(self, job, i: int, at, ln, done):
+        """The attention rows of chunk i's hypotheses, each cut at memory_lengths as the reference cuts it."""
+        lens = job["lens"]
+        if job["kind"] == "greedy":  # results["attention"]: rows cut at the chunk's length (translator.py:491-501)
+            return [at[i, :, : lens[i]]]
+        grp, sorted_rows, cut, beam = job["grp"], job["sorted_rows"], job["cut"], self.beam_size
+        atts = []
+        for k in range(self.n_best):
+            if self.fast:
+                # translator.py:780-790: attention[:, i, j, :memory_lengths[i]] with i the
+                # chunk's index among the batches alive at the hypothesis' last step
+                step = int(ln[i, k]) - 1
+                alive = [q for q in sorted_rows[int(grp[i])] if done[q] == 0 or done[q] > step]
+                c = int(lens[alive[alive.index(i) // beam]])
+            else:
+                c = int(cut[i])
+            atts.append(at[i, k, : ln[i, k], :c])
+        return atts
+
     def _beam_weights(self, job, tok, ln):
-        """The token weights [B, L] (uint16) of a finished beam call's best hypotheses: the existing
+        """The token weights [B, L] of a finished beam call's best hypotheses: the existing
         teacher-forced scoring pass (score_targets) over the call's own inputs, each gold row the hypothesis'
         tokens as returned (EOS included when it finished) and gold_len its length, then nd_token_weights of
         the pass's per-token log-probs.  The encoder runs a second time for this.  A call submitted with
-        ``mods`` asks the same pass for its full log-probs too and returns (weights, modification weights), the
-        latter nd_token_mod_weights of those log-probs."""
+        ``mods`` asks the same pass for its full log-probs too; returns (weights, modification weights), the
+        latter nd_token_mod_weights of those log-probs, or None without ``mods``.  The pass has a range guard
+        of its own: when it alone is flagged, it alone runs again."""
         sig, ln_in, sp = job["eng_in"]
-        B, mods = job["B"], job.get("mods", False)
-        want = dict(return_logp=True) if mods else {}
+        B, mods = job["B"], job["req"].mods
         n_tok = np.clip(ln[:B, 0].astype(np.int32), 1, min(tok.shape[2], self.engine.max_steps))
         L = min(self.engine.max_steps, (int(n_tok.max()) + 7) // 8 * 8)  # one captured graph per (B, T, L)
         gold = np.full((B, L), self.cfg.pad_idx, np.int32)
@@ -456,30 +533,15 @@ class Translator(object):
             gold[i, : n_tok[i]] = tok[i, 0, : n_tok[i]]
         gold[gold < 0] = self.cfg.eos_idx  # a row without a hypothesis (engine padding) scores a lone EOS
         gold_t, len_t = torch.from_numpy(gold), torch.from_numpy(n_tok)
-
-        def score():
-            r = self.engine.score_targets(sig, ln_in, sp, gold=gold_t, gold_len=len_t, return_tok_logp=True, **want)
-            if "event" in r:
-                r["event"].synchronize()
-            ov = r.get("overflow")
-            return r, ov is not None and int(ov.cpu().reshape(-1)[0]) != 0
-        r, over = score()
-        if over and not job.get("exact"):
-            # split-fp16 range guard: the pass again with every product in exact fp32 (see _rerun_exact)
-            self.engine.set_exact_fp32(True)
-            try:
-                r, _ = score()
-            finally:
-                self.engine.set_exact_fp32(False)
-        lane = {"lane": r["lane"]} if "lane" in r else {}
-        w = self.engine.token_weights(gold_t, tok_logp=r["tok_logp"], **lane)
+        r = self._run_guarded(lambda: self.engine.score_targets(sig, ln_in, sp, gold=gold_t, gold_len=len_t,
+                                                                return_tok_logp=True, **_asked(return_logp=mods)),
+                              exact=job.get("exact", False))
+        w = self.engine.token_weights(gold_t, tok_logp=r["tok_logp"], **_lane(r))
         # positions past a hypothesis' length hold pad_idx, which is neither C nor M: their weight is 0
-        mw = self.engine.token_mod_weights(gold_t, r["logp"], *self._cm_ids(), **lane) if mods else None
+        mw = self.engine.token_mod_weights(gold_t, r["logp"], *self._cm_ids(), **_lane(r)) if mods else None
         if "lane" in r:
-            self.engine.engines[r["lane"]].stream.synchronize()
-        if mods:
-            return w.cpu().numpy().view(np.uint16), mw.cpu().numpy().view(np.uint16)
-        return w.cpu().numpy().view(np.uint16)
+            self.engine.stream_of(r).synchronize()
+        return w.cpu().numpy(), mw.cpu().numpy() if mods else None
 
     def _char_weights(self, toks, w, dtype=np.uint16) -> np.ndarray:
         """The weight of every character of a hypothesis' string with the spaces removed (uint16): the
@@ -496,7 +558,7 @@ class Translator(object):
     def _run(self, chunks: List[np.ndarray], spans: Sequence[int], groups: Optional[Sequence[int]] = None,
              attn: bool = False):
         """One engine batch, synchronously (see _submit / _finish)."""
-        return self._finish(self._submit(chunks, spans, groups, attn))
+        return self._finish(self._submit(chunks, spans, groups, Request(attn=attn)))
 
     def _tokens_to_sent(self, toks) -> List[str]:
         """translate/translation.py:31-47."""
@@ -529,6 +591,15 @@ class Translator(object):
                              f"{self.engine.max_steps - 1}")
         return ids
 
+    @staticmethod
+    def _reference_spans(chunks, batch_size: int) -> List[int]:
+        """Per chunk the span of its reference batch: the longest of its ``batch_size`` consecutive chunks."""
+        spans = []
+        for b0 in range(0, len(chunks), batch_size):
+            part = chunks[b0: b0 + batch_size]
+            spans += [max(len(c) for c in part)] * len(part)
+        return spans
+
     def score(self, chunks, targets, batch_size, moves: bool = False):
         """Teacher-forced scores of given target sequences (Translator._score_target,
         translate/translator.py:928-941): per chunk (score, tok_logp list), score = the sum of the target's
@@ -546,37 +617,21 @@ class Translator(object):
         ids = [self._gold_ids(t) for t in targets]
         if self.cfg.self_attn_type == "average":
             raise NotImplementedError("scoring targets is not supported for average-attention decoders")
-        spans = []
-        for b0 in range(0, len(chunks), batch_size):
-            part = chunks[b0: b0 + batch_size]
-            spans += [max(len(c) for c in part)] * len(part)
+        spans = self._reference_spans(chunks, batch_size)
         out, cap = [], self.engine.max_batch
         for b0 in range(0, len(chunks), cap):
-            out += self._score_batch(chunks[b0: b0 + cap], spans[b0: b0 + cap], ids[b0: b0 + cap], moves=moves)
+            out += self._score_batch(chunks[b0: b0 + cap], spans[b0: b0 + cap], ids[b0: b0 + cap], moves)
         return out
 
-    def _score_batch(self, chunks, spans, ids, exact: bool = False, moves: bool = False):
-        """One engine batch of score(): stage, call, collect on the host.  With ``moves`` the call returns its
-        attention too, token_positions reduces it on the call's stream (its EnginePool lane), and only the
-        [B, L] positions come to the host."""
+    def _score_batch(self, chunks, spans, ids, moves: bool = False):
+        """One engine batch of score(): stage, call (under the range guard), collect on the host.  With
+        ``moves`` the call returns its attention too, token_positions reduces it on the call's stream (its
+        EnginePool lane), and only the [B, L] positions come to the host."""
         n = len(chunks)
-        lens = np.array([len(c) for c in chunks], np.int32)
-        if (lens < 1).any():
-            raise ValueError("empty signal chunk")
-        spans = np.asarray(spans, np.int32)
-        if spans.max() > self.engine.max_src_len:
-            raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
-        T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
-        B = _bucket(n, self.engine.max_batch)
+        sig, ln, sp, B, _ = self._pack(chunks, spans)
         # target rows padded to a multiple of 8 positions (one captured graph per (B, T, L); the padding
         # positions add exactly 0)
         L = min(self.engine.max_steps, (max(len(t) for t in ids) + 1 + 7) // 8 * 8)
-        sig, ln, sp, dev_in = self._stage(B, T)
-        for i, c in enumerate(chunks):
-            sig[i, : len(c)] = c
-        ln[:n], sp[:n] = lens, spans
-        if dev_in is not None:
-            sig, ln, sp = dev_in
         gold = np.full((B, L), self.cfg.pad_idx, np.int32)
         gold_len = np.ones(B, np.int32)
         gold[:, 0] = self.cfg.eos_idx  # the engine's padding rows score a lone EOS
@@ -584,23 +639,13 @@ class Translator(object):
             gold[i, : len(t)] = t
             gold[i, len(t)] = self.cfg.eos_idx
             gold_len[i] = len(t) + 1
-        want = dict(return_attn=True) if moves else {}
-        r = self.engine.score_targets(sig, ln, sp, gold=torch.from_numpy(gold), gold_len=torch.from_numpy(gold_len),
-                                      return_tok_logp=True, **want)
-        if "event" in r:
-            r["event"].synchronize()
-        ov = r.get("overflow")
-        if ov is not None and int(ov.cpu().reshape(-1)[0]) != 0 and not exact:
-            # split-fp16 range guard: the batch again with every product in exact fp32 (see _rerun_exact)
-            self.engine.set_exact_fp32(True)
-            try:
-                return self._score_batch(chunks, spans, ids, exact=True, moves=moves)
-            finally:
-                self.engine.set_exact_fp32(False)
+        gold_t, len_t = torch.from_numpy(gold), torch.from_numpy(gold_len)
+        r = self._run_guarded(lambda: self.engine.score_targets(sig, ln, sp, gold=gold_t, gold_len=len_t,
+                                                                return_tok_logp=True, **_asked(return_attn=moves)))
         if moves:
             self._positions(r, sp)
             if "lane" in r:
-                self.engine.engines[r["lane"]].stream.synchronize()
+                self.engine.stream_of(r).synchronize()
         sc, tl = r["scores"].cpu().numpy(), r["tok_logp"].cpu().numpy()
         if moves:
             ps = r["positions"].cpu().numpy()
@@ -633,10 +678,7 @@ class Translator(object):
             ids.append([self._gold_ids(t) for t in cl])
         if self.cfg.self_attn_type == "average":
             raise NotImplementedError("scoring targets is not supported for average-attention decoders")
-        spans = []
-        for b0 in range(0, len(chunks), batch_size):
-            part = chunks[b0: b0 + batch_size]
-            spans += [max(len(c) for c in part)] * len(part)
+        spans = self._reference_spans(chunks, batch_size)
 
         def slots(n):  # a power of two while one chunk of it fits a call
             k = 1
@@ -655,25 +697,11 @@ class Translator(object):
             out += self._score_cand_batch(chunks[b0:], spans[b0:], ids[b0:], K)
         return out
 
-    def _score_cand_batch(self, chunks, spans, ids, K: int, exact: bool = False):
+    def _score_cand_batch(self, chunks, spans, ids, K: int):
         """One engine call of score_candidates(): n chunks of at most K candidates each, n * K <= max_batch."""
-        n = len(chunks)
-        lens = np.array([len(c) for c in chunks], np.int32)
-        if (lens < 1).any():
-            raise ValueError("empty signal chunk")
-        spans = np.asarray(spans, np.int32)
-        if spans.max() > self.engine.max_src_len:
-            raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
-        T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
-        B = _bucket(n, self.engine.max_batch // K)
+        sig, ln, sp, B, _ = self._pack(chunks, spans, cap=self.engine.max_batch // K)
         # as _score_batch: rows padded to a multiple of 8 positions (one captured graph per (B, T, K, L))
         L = min(self.engine.max_steps, (max(len(t) for cl in ids for t in cl) + 1 + 7) // 8 * 8)
-        sig, ln, sp, dev_in = self._stage(B, T)
-        for i, c in enumerate(chunks):
-            sig[i, : len(c)] = c
-        ln[:n], sp[:n] = lens, spans
-        if dev_in is not None:
-            sig, ln, sp = dev_in
         # padding chunks and the slots a chunk does not fill are empty slots (cand_len 0)
         cand = np.full((B, K, L), self.cfg.pad_idx, np.int32)
         cand_len = np.zeros((B, K), np.int32)
@@ -682,17 +710,8 @@ class Translator(object):
                 cand[i, k, : len(t)] = t
                 cand[i, k, len(t)] = self.cfg.eos_idx
                 cand_len[i, k] = len(t) + 1
-        r = self.engine.score_candidates(sig, ln, sp, cand=torch.from_numpy(cand), cand_len=torch.from_numpy(cand_len))
-        if "event" in r:
-            r["event"].synchronize()
-        ov = r.get("overflow")
-        if ov is not None and int(ov.cpu().reshape(-1)[0]) != 0 and not exact:
-            # split-fp16 range guard: the call again with every product in exact fp32 (see _rerun_exact)
-            self.engine.set_exact_fp32(True)
-            try:
-                return self._score_cand_batch(chunks, spans, ids, K, exact=True)
-            finally:
-                self.engine.set_exact_fp32(False)
+        cand_t, len_t = torch.from_numpy(cand), torch.from_numpy(cand_len)
+        r = self._run_guarded(lambda: self.engine.score_candidates(sig, ln, sp, cand=cand_t, cand_len=len_t))
         sc, post, best = r["scores"].cpu().numpy(), r["post"].cpu().numpy(), r["best"].cpu().numpy()
         return [(sc[i, : len(cl)].tolist(), post[i, : len(cl)].tolist(), int(best[i])) for i, cl in enumerate(ids)]
 
@@ -712,10 +731,9 @@ class Translator(object):
         gold = self.score(chunks, tgt, batch_size)
         self.last_gold_scores = [g[0] for g in gold]
         sents = [t if isinstance(t, str) else " ".join(self.cfg.itos[i] for i in self._gold_ids(t)) for t in tgt]
-        results = [None]
-        for ri, res in self.stream_reads([chunks], batch_size, attn_debug):
-            results[ri] = res
-        return self._report(results, attn_debug, gold=list(zip(sents, self.last_gold_scores)))[0]
+        req = self._request(attn_debug)
+        results = [res for _, res in self._stream_reads([chunks], batch_size, req)]
+        return self._report(results, req, gold=list(zip(sents, self.last_gold_scores)))[0]
 
     def _write_attn(self, chunk: np.ndarray, sent: List[str], attn: np.ndarray):
         """translate/translator.py:285-336: the source samples and the
@@ -732,18 +750,50 @@ class Translator(object):
             output += row_format.format(*row) + "\n"
         self.out_file_attn.write(output)
 
-    def _want_qualities(self, qualities: bool, attn_debug: bool = False, mods: bool = False) -> bool:
-        qualities = qualities or mods  # the methylation values travel beside the qualities
-        if qualities:
-            if attn_debug:
-                raise ValueError("qualities are not available together with attn_debug")
-            self._check_supported(qualities=True, **({"mods": True} if mods else {}))
-        return bool(qualities)
+    # ------------------------------------------------------------- many reads
+    def _stream(self, reads: Iterable, batch_size: int, describe, submit, store):
+        """The loop of stream_reads and stream_raw_reads.  ``describe(read)`` gives the read's result holder
+        and one (what, length) per chunk; chunk descriptors (read, chunk, what, length, span, reference
+        batch) fill a pending list, span the longest of the chunk's reference batch (``batch_size``
+        consecutive chunks of its read).  At max_batch descriptors ``submit(items)`` enqueues an engine call
+        and returns its job; ``store(job, items, results)`` waits for a job and puts each chunk's result into
+        results[read][chunk].  A call is collected only when more than one call per lane is in flight after a
+        submit, so those stay on the device while the next batch is packed, and (read index, holder) is
+        yielded once a read's last chunk is stored, a read without chunks at once."""
+        cap, depth = self.engine.max_batch, self._depth()
+        pending, inflight = [], collections.deque()
+        results, remaining = {}, {}
+        nb = 0
 
-    def _want_moves(self, moves: bool, attn_debug: bool = False) -> bool:
-        if moves and attn_debug:
-            raise ValueError("signal positions are not available together with attn_debug")
-        return bool(moves)
+        def collect():
+            job, items = inflight.popleft()
+            store(job, items, results)
+            for it in items:
+                remaining[it[0]] -= 1
+                if remaining[it[0]] == 0:
+                    yield it[0], results.pop(it[0])
+
+        for ri, read in enumerate(reads):
+            holder, parts = describe(read)
+            if not parts:
+                yield ri, holder
+                continue
+            results[ri], remaining[ri] = holder, len(parts)
+            for b0 in range(0, len(parts), batch_size):
+                part = parts[b0: b0 + batch_size]
+                span = max(n for _, n in part)
+                for k, (what, n) in enumerate(part):
+                    pending.append((ri, b0 + k, what, n, span, nb))
+                    if len(pending) == cap:
+                        inflight.append((submit(pending), pending))
+                        pending = []
+                        while len(inflight) > depth:
+                            yield from collect()
+                nb += 1
+        if pending:
+            inflight.append((submit(pending), pending))
+        while inflight:
+            yield from collect()
 
     def stream_reads(self, reads: Iterable[Sequence], batch_size: int, attn_debug: bool = False,
                      qualities: bool = False, mods: bool = False, moves: bool = False):
@@ -768,54 +818,21 @@ class Translator(object):
         positions): the call returns its head-0 context attention and
         nd_token_positions reduces it on the call's stream, in every search
         mode (a beam call's hypothesis 0; no scoring pass)."""
-        import collections
-        qualities = self._want_qualities(qualities, attn_debug, mods)
-        moves = self._want_moves(moves, attn_debug)
-        cap = self.engine.max_batch
-        depth = self._depth()
-        pending, inflight = [], collections.deque()
-        results, remaining = {}, {}
-        nb = 0
+        yield from self._stream_reads(reads, batch_size, self._request(attn_debug, qualities, mods, moves))
 
-        def collect(jb):
-            job, items = jb
-            done = []
-            for (ri, ci, c, _, _), o in zip(items, self._finish(job)):
-                results[ri][ci] = o + (c,) if attn_debug else o
-                remaining[ri] -= 1
-                if remaining[ri] == 0:
-                    done.append(ri)
-            return done
+    def _stream_reads(self, reads, batch_size: int, req: Request):
+        def describe(read):
+            chunks = [parse_chunk(c) for c in read]
+            return [None] * len(chunks), [(c, len(c)) for c in chunks]
 
         def submit(items):
-            return self._submit([g[2] for g in items], [g[3] for g in items], [g[4] for g in items],
-                                attn=attn_debug, qual=qualities, **({"mods": True} if mods else {}),
-                                **({"moves": True} if moves else {})), items
+            return self._submit([it[2] for it in items], [it[4] for it in items], [it[5] for it in items], req)
 
-        for ri, read in enumerate(reads):
-            chunks = [parse_chunk(c) for c in read]
-            if not chunks:
-                yield ri, []
-                continue
-            results[ri], remaining[ri] = [None] * len(chunks), len(chunks)
-            for b0 in range(0, len(chunks), batch_size):
-                part = chunks[b0: b0 + batch_size]
-                span = max(len(c) for c in part)
-                for k, c in enumerate(part):
-                    pending.append((ri, b0 + k, c, span, nb))
-                    if len(pending) == cap:
-                        inflight.append(submit(pending))
-                        pending = []
-                        # `depth` calls stay on the device while the next batch is packed
-                        while len(inflight) > depth:
-                            for r in collect(inflight.popleft()):
-                                yield r, results.pop(r)
-                nb += 1
-        if pending:
-            inflight.append(submit(pending))
-        while inflight:
-            for r in collect(inflight.popleft()):
-                yield r, results.pop(r)
+        def store(job, items, results):
+            for it, o in zip(items, self._finish(job)):
+                results[it[0]][it[1]] = o + (it[2],) if req.attn else o  # -attn_debug dumps the chunk too
+
+        return self._stream(reads, batch_size, describe, submit, store)
 
     def translate_reads(self, reads: Sequence[Sequence], batch_size: int, attn_debug: bool = False,
                         qualities: bool = False, mods: bool = False, moves: bool = False):
@@ -824,13 +841,13 @@ class Translator(object):
         (all_scores, all_predictions, all_weights), all_weights per chunk the
         uint16 weights of its best hypothesis (see stream_reads); with ``mods``
         (which implies ``qualities``) also all_mod_weights, laid out like all_weights; with ``moves`` a last
-        entry all_positions, per chunk the int32 chunk-relative signal positions of the same characters."""
+        entry all_positions, per chunk the int32 chunk-relative signal positions of the same characters
+        (split_result takes such a result apart)."""
+        req = self._request(attn_debug, qualities, mods, moves)
         results = [None] * len(reads)
-        qualities = bool(qualities or mods)
-        for ri, res in self.stream_reads(reads, batch_size, attn_debug, **({"qualities": True} if qualities else {}),
-                                         **({"mods": True} if mods else {}), **({"moves": True} if moves else {})):
+        for ri, res in self._stream_reads(reads, batch_size, req):
             results[ri] = res
-        return self._report(results, attn_debug, qualities=qualities, mods=mods, **({"moves": True} if moves else {}))
+        return self._report(results, req)
 
     def translate_raw_reads(self, raws: Sequence[np.ndarray], batch_size: int, normalization: str = "median",
                             src_seq_length: int = 512, src_seq_stride: int = 512, qualities: bool = False,
@@ -839,18 +856,15 @@ class Translator(object):
         device (stream_raw_reads); returns per read (all_scores,
         all_predictions), with ``qualities`` also all_weights, with ``mods`` also all_mod_weights, with ``moves``
         a last entry all_positions."""
+        req = self._request(False, qualities, mods, moves)
         results = [None] * len(raws)
-        qualities = bool(qualities or mods)
-        for ri, res in self.stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
-                                             **({"qualities": True} if qualities else {}),
-                                             **({"mods": True} if mods else {}),
-                                             **({"moves": True} if moves else {})):
+        for ri, res in self._stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
+                                              False, req):
             results[ri] = res
-        return self._report(results, False, qualities=qualities, mods=mods, **({"moves": True} if moves else {}))
+        return self._report(results, req)
 
-    def _report(self, results, attn_debug: bool, gold=None, qualities: bool = False, mods: bool = False,
-                moves: bool = False):
-        """Per read (all_scores, all_predictions) from per-chunk results, with
+    def _report(self, results, req: Request, gold=None):
+        """Per read (all_scores, all_predictions), then what ``req`` asked for, from per-chunk results, with
         the reference's verbose / -dump_beam / report_score side outputs
         (translate/translator.py:255-369).  gold (translate with tgt): per chunk
         in order (gold sentence, gold score), logged after PRED SCORE."""
@@ -858,20 +872,15 @@ class Translator(object):
         counter = 0
         pred_score_total, pred_words_total = 0.0, 0
         for r in results:
-            all_scores, all_predictions, all_weights, all_mods, all_moves = [], [], [], [], []
+            per_read = [[] for _ in range(5)]  # scores, predictions, weights, modification weights, positions
             for res in r:
-                scores, toks = res[0], res[1]
+                scores, toks, *optional = req.split(res)
                 sents = [self._tokens_to_sent(t) for t in toks]
-                if attn_debug:
+                if req.attn:
                     self._write_attn(res[3], sents[0], res[2][0])
-                all_scores.append(scores[: self.n_best])
-                all_predictions.append([" ".join(s) for s in sents[: self.n_best]])
-                if qualities:
-                    all_weights.append(res[2])
-                if mods:
-                    all_mods.append(res[3])
-                if moves:  # after the weights and modification weights when those are present
-                    all_moves.append(res[2 + int(bool(qualities)) + int(bool(mods))])
+                for column, v in zip(per_read, [scores[: self.n_best], [" ".join(s) for s in sents[: self.n_best]]]
+                                     + optional):
+                    column.append(v)
                 pred_score_total += scores[0]
                 pred_words_total += len(sents[0])
                 if self.verbose:
@@ -889,8 +898,7 @@ class Translator(object):
                         self.logger.info(msg)
                     else:
                         os.write(1, msg.encode("utf-8"))
-            ret.append((all_scores, all_predictions) + ((all_weights,) if qualities else ()) +
-                       ((all_mods,) if mods else ()) + ((all_moves,) if moves else ()))
+            ret.append(req.join(*per_read))
         if self.dump_beam:
             # translator.py:365-368 dumps the beam trace accumulator.  (The
             # reference reads it through a `self.translator` attribute the
@@ -905,43 +913,31 @@ class Translator(object):
         return ret
 
     # ------------------------------------------------------ device front end
-    def _next_stream(self):
-        """The stream the engine's next call will run on (its EnginePool
-        lane, or the current stream for a single Engine)."""
-        if isinstance(self.engine, EnginePool):
-            return self.engine.engines[self.engine._next].stream
-        return torch.cuda.current_stream(self.engine.device)
-
-    def _submit_raw(self, items, batch_reads, normalization: str, qual: bool = False, mods: bool = False,
-                    moves: bool = False):
+    def _submit_raw(self, items, normalization: str, req: Request):
         """One engine batch from raw reads: chunk descriptors ``items`` =
-        (read, chunk, start, length, span, reference batch) and the reads
-        they cut (``batch_reads``: read -> float64 samples).  The front end
-        (frontend.device_batch) runs on the call's own stream, so the
-        normalised chunks go from HBM to the engine with no host pass."""
+        (read, chunk, (the read's float64 samples, start), length, span,
+        reference batch).  The front end (frontend.device_batch) runs on the
+        call's own stream, so the normalised chunks go from HBM to the engine
+        with no host pass."""
         from . import frontend
         n = len(items)
-        uniq = list(batch_reads)
-        local = {ri: j for j, ri in enumerate(uniq)}
+        reads = {}  # the reads this batch cuts, in order of appearance
+        for it in items:
+            reads.setdefault(it[0], it[2][0])
+        local = {ri: j for j, ri in enumerate(reads)}
         lens = np.fromiter((it[3] for it in items), np.int32, n)
-        spans = np.fromiter((it[4] for it in items), np.int32, n)
-        if spans.max() > self.engine.max_src_len:
-            raise ValueError(f"chunk longer than {self.engine.max_src_len} samples (src_seq_length) is not supported")
-        T = min(self.engine.max_src_len, ((int(spans.max()) + 63) // 64) * 64)
-        B = _bucket(n, self.engine.max_batch)
+        B, T, spans = self._batch_dims(n, np.fromiter((it[4] for it in items), np.int32, n))
         ls = np.ones(2 * B, np.int32)
         ls[:n], ls[B: B + n] = lens, spans
-        st = self._next_stream()
-        with torch.cuda.stream(st):
-            sig, keep = frontend.device_batch([batch_reads[r] for r in uniq],
+        with torch.cuda.stream(self.engine.next_stream()):
+            sig, keep = frontend.device_batch(list(reads.values()),
                                               np.fromiter((local[it[0]] for it in items), np.int32, n),
-                                              np.fromiter((it[2] for it in items), np.int32, n), lens,
+                                              np.fromiter((it[2][1] for it in items), np.int32, n), lens,
                                               normalization, B, T, self.engine.device)
             ls_d = torch.from_numpy(ls).pin_memory().to(self.engine.device, non_blocking=True)
-            job = self._enqueue(sig, ls_d[:B], ls_d[B:], B, n, lens, [it[5] for it in items], False,
-                                (sig, ls_d, keep), qual, **({"mods": True} if mods else {}),
-                                **({"moves": True} if moves else {}))
-        job["again"] = lambda: self._submit_raw(items, batch_reads, normalization, qual, mods, moves)
+            job = self._enqueue(sig, ls_d[:B], ls_d[B:], B, n, lens, [it[5] for it in items], req,
+                                (sig, ls_d, keep))
+        job["again"] = lambda: self._submit_raw(items, normalization, req)
         return job
 
     def stream_raw_reads(self, raws: Iterable, batch_size: int, normalization: str = "median",
@@ -964,96 +960,42 @@ class Translator(object):
         ``arrays`` a fifth array, the tokens' modification weights, laid out
         like the fourth.  ``moves`` as in stream_reads; with ``arrays`` a last
         array follows, the tokens' positions [n_chunks, max_length] int32."""
-        import collections
-
-        from . import frontend
         if arrays and self.beam_size != 1:
             raise ValueError("arrays=True is for greedy / sampling decoding")
-        qualities = self._want_qualities(qualities, mods=mods)
-        moves = self._want_moves(moves)
-        n_w = (2 if mods else 1) if qualities else 0  # uint16 arrays per read with ``arrays``
-        n_p = 1 if moves else 0  # int32 position arrays behind them
-        cap = self.engine.max_batch
-        depth = self._depth()
-        pending, batch_reads, inflight = [], {}, collections.deque()
-        results, remaining = {}, {}
-        nb = 0
+        req = self._request(False, qualities, mods, moves)
+        for ri, res in self._stream_raw_reads(raws, batch_size, normalization, src_seq_length, src_seq_stride,
+                                              arrays, req):
+            yield (ri,) + res if arrays else (ri, res)
 
-        def collect(jb):
-            job, items = jb
-            if arrays:
-                cols = self._finish_arrays(job)
-                outs = (tuple(a[i] for a in cols) for i in range(len(items)))
-            else:
-                outs = self._finish(job)
-            done = []
-            for (ri, ci, _, _, _, _), o in zip(items, outs):
-                if arrays:
-                    for dst, v in zip(results[ri], o):
-                        dst[ci] = v
-                else:
-                    results[ri][ci] = o
-                remaining[ri] -= 1
-                if remaining[ri] == 0:
-                    done.append(ri)
-            return done
+    def _stream_raw_reads(self, raws, batch_size: int, normalization: str, src_seq_length: int, src_seq_stride: int,
+                          arrays: bool, req: Request):
+        from . import frontend
+        S = self.max_length
+        per_token = req.asked((np.uint16, (S,)), (np.uint16, (S,)), (np.int32, (S,)))
+        columns = ((np.int32, (S,)), (np.float32, ())) + per_token  # tokens and scores first
 
-        def flush():
-            nonlocal pending, batch_reads
-            inflight.append((self._submit_raw(pending, batch_reads, normalization, qualities,
-                                              **({"mods": True} if mods else {}),
-                                              **({"moves": True} if moves else {})), pending))
-            pending, batch_reads = [], {}
+        def holder(n):  # a read's n chunk results: a list, or with ``arrays`` one [n, ...] array per column
+            return tuple(np.empty((n,) + shape, dtype) for dtype, shape in columns) if arrays else [None] * n
 
-        for ri, raw in enumerate(raws):
+        def describe(raw):
             raw = np.asarray(raw, dtype=np.float64).reshape(-1)
-            if raw.size == 0:
-                empty = (np.zeros((0, self.max_length), np.int32), np.zeros(0, np.float32)) + \
-                    tuple(np.zeros((0, self.max_length), np.uint16) for _ in range(n_w)) + \
-                    tuple(np.zeros((0, self.max_length), np.int32) for _ in range(n_p))
-                yield (ri,) + empty if arrays else (ri, [])
-                continue
-            wins = frontend.windows(int(raw.size), src_seq_length, src_seq_stride)
-            if arrays:
-                results[ri] = (np.empty((len(wins), self.max_length), np.int32), np.empty(len(wins), np.float32)) + \
-                    tuple(np.empty((len(wins), self.max_length), np.uint16) for _ in range(n_w)) + \
-                    tuple(np.empty((len(wins), self.max_length), np.int32) for _ in range(n_p))
-            else:
-                results[ri] = [None] * len(wins)
-            remaining[ri] = len(wins)
-            for b0 in range(0, len(wins), batch_size):
-                part = wins[b0: b0 + batch_size]
-                span = max(ln for _, ln in part)
-                for k, (st, ln) in enumerate(part):
-                    pending.append((ri, b0 + k, st, ln, span, nb))
-                    batch_reads[ri] = raw
-                    if len(pending) == cap:
-                        flush()
-                        while len(inflight) > depth:
-                            for r in collect(inflight.popleft()):
-                                yield (r,) + results.pop(r) if arrays else (r, results.pop(r))
-                nb += 1
-        if pending:
-            flush()
-        while inflight:
-            for r in collect(inflight.popleft()):
-                yield (r,) + results.pop(r) if arrays else (r, results.pop(r))
+            wins = frontend.windows(int(raw.size), src_seq_length, src_seq_stride) if raw.size else []
+            return holder(len(wins)), [((raw, st), ln) for st, ln in wins]
 
-    def _finish_arrays(self, job):
-        """(tokens [n, S], scores [n]) numpy of a greedy / sampling call; its tokens' weights [n, S] uint16
-        follow when the call was submitted with qualities, then their modification weights when with mods, then
-        their positions [n, S] int32 when with moves."""
-        tok, sc, ov = self._host(job, "tokens", "scores", "overflow")
-        if self._overflowed(job, ov):
-            return self._rerun_exact(job, self._finish_arrays)
-        tail = (self._host(job, "positions")[0][: job["n"]],) if job.get("moves") else ()
-        if job.get("mods"):
-            w, mw = self._host(job, "weights", "mod_weights")
-            return (tok[: job["n"]], sc[: job["n"]], w.view(np.uint16)[: job["n"]],
-                    mw.view(np.uint16)[: job["n"]]) + tail
-        if job.get("qual"):
-            return (tok[: job["n"]], sc[: job["n"]], self._host(job, "weights")[0].view(np.uint16)[: job["n"]]) + tail
-        return (tok[: job["n"]], sc[: job["n"]]) + tail
+        def submit(items):
+            return self._submit_raw(items, normalization, req)
+
+        def store(job, items, results):
+            if not arrays:
+                for it, o in zip(items, self._finish(job)):
+                    results[it[0]][it[1]] = o
+                return
+            cols = self._finish(job, arrays=True)
+            for i, it in enumerate(items):
+                for dst, a in zip(results[it[0]], cols):
+                    dst[it[1]] = a[i]
+
+        return self._stream(raws, batch_size, describe, submit, store)
 
     def translate_batch(self, batch, data=None, attn_debug=False, fast=False):
         """translate/translator.py:505-540 on a batch object with

@@ -268,3 +268,113 @@ def test_random_sampling_reaches_the_engine():
     tr2, eng2 = make_tr(random_sampling_topk=3, random_sampling_temp=0.7, seed=5)
     tr2.translate(chunks([100]), batch_size=1)
     assert eng2.calls[0][6] == s1
+
+
+# ---------------------------------------------------------------- streaming, the range guard
+def test_stream_order_and_calls_in_flight():
+    """stream_reads yields a read as soon as its last chunk's call is collected, an empty read at once, and
+    collects the oldest call only when more than one call per lane is in flight after a submit."""
+    tr, eng = make_tr(batch_size=1)
+    eng.lanes = 2                               # max_batch 8: calls of 8 chunks, two kept in flight
+    one = chunks([100])
+    reads = [one] * 20 + [[]] + [chunks([100, 90, 80])] + [one] * 19   # 41 reads, 42 chunks
+    seen = [(ri, len(eng.calls), res) for ri, res in tr.stream_reads(reads, 1)]
+    assert [s[0] for s in seen] == [20] + list(range(20)) + [21, 22] + list(range(23, 41))
+    assert [s[1] for s in seen] == [2] + [3] * 8 + [4] * 8 + [5] * 6 + [6] * 18
+    assert len(eng.calls) == 6
+    by_read = {ri: res for ri, _, res in seen}
+    assert by_read[20] == [] and len(by_read[21]) == 3
+    assert all(len(by_read[ri]) == 1 for ri in by_read if ri not in (20, 21))
+    tr2, _ = make_tr(batch_size=1)
+    for ri, (sc, preds) in enumerate(tr2.translate_reads(reads, batch_size=1)):
+        assert [r[0] for r in by_read[ri]] == sc
+        assert [[" ".join(tr._tokens_to_sent(t)) for t in r[1]] for r in by_read[ri]] == preds
+
+
+@pytest.mark.parametrize("mods", [False, True])
+def test_beam_weights_rerun_only_the_scoring_pass(mods):
+    """Beam qualities when only the scoring pass trips the split-fp16 range guard: the beam call runs once, the
+    scoring pass twice (the second time in exact fp32), and the weights are the second pass's."""
+    from nanodecoder_amd import frontend
+    from tests.test_mods_host import C_ID, M_ID, BeamModEngine, known_logp9
+    from tests.test_mods_host import make_tr as make_mod_tr
+
+    class ScoreOverflow(BeamModEngine):
+        exact = False
+
+        def set_exact_fp32(self, on):
+            self.exact = bool(on)
+
+        def score_targets(self, *a, **k):
+            out = super().score_targets(*a, **k)
+            out["overflow"] = torch.tensor([0 if self.exact else 1], dtype=torch.int32)
+            if self.exact:  # the exact pass's log-probs are shifted
+                out["tok_logp"] = out["tok_logp"] - 0.5
+                if "logp" in out:
+                    out["logp"] = out["logp"] - 0.5
+            return out
+
+    reads = [chunks([512, 511, 77], seed=1)]
+    tr, eng = make_mod_tr(ScoreOverflow, beam_size=4, fast=True)
+    want = dict(mods=True) if mods else dict(qualities=True)
+    (sc, preds, ws, *ms), = tr.translate_reads(reads, batch_size=1, **want)
+    assert [c[0] for c in eng.calls] == ["beam", "score", "score"] + ["token_mod_weights"] * mods
+    assert eng.calls[1] == eng.calls[2] == ("score", True, mods) and eng.exact is False
+    lp = known_logp9(8, 8) - np.float32(0.5)
+    for row, (p, w) in enumerate(zip(preds, ws)):
+        s = p[0].replace(" ", "")
+        toks = [tr.cfg.itos.index(c) for c in s]
+        assert len(s) == 3 and w.tolist() == [frontend.token_weight(lp[row, t, tok]) for t, tok in enumerate(toks)]
+        if mods:
+            assert ms[0][row].tolist() == [
+                frontend.token_mod_weight(lp[row, t, C_ID], lp[row, t, M_ID], c == "M") if c in "CM" else 0
+                for t, c in enumerate(s)]
+    assert len(ms) == int(mods)
+
+
+def test_exact_mode_is_restored_when_the_rerun_raises():
+    class Boom(FakeEngine):
+        def __init__(self):
+            super().__init__()
+            self.modes = []
+
+        def set_exact_fp32(self, on):
+            self.modes.append(bool(on))
+
+        def translate_greedy(self, *a, **k):
+            if self.modes[-1:] == [True]:
+                raise RuntimeError("boom in the exact rerun")
+            out = super().translate_greedy(*a, **k)
+            out["overflow"] = torch.tensor([1], dtype=torch.int32)
+            return out
+
+    tr, _ = make_tr()
+    tr.engine = eng = Boom()
+    with pytest.raises(RuntimeError, match="boom in the exact rerun"):
+        tr.translate(chunks([100, 90]), batch_size=2)
+    assert len(eng.calls) == 1 and eng.modes == [True, False]
+
+
+@pytest.mark.parametrize("moves", [False, True])
+@pytest.mark.parametrize("kind", ["none", "qualities", "mods"])
+def test_split_result_names_what_the_tests_index(kind, moves):
+    """Translator.split_result on a per-read result of translate_reads: the arrays found positionally today,
+    None for what was not asked."""
+    from tests.test_moves_host import MovesEngine
+    from tests.test_moves_host import make_tr as make_moves_tr
+    reads = [chunks([512, 512, 77], seed=1), chunks([511, 300], seed=2), []]
+    want = {"none": {}, "qualities": dict(qualities=True), "mods": dict(mods=True)}[kind]
+    if moves:
+        want["moves"] = True
+    tr, _ = make_moves_tr(MovesEngine)
+    n_w = {"none": 0, "qualities": 1, "mods": 2}[kind]
+    for res in tr.translate_reads(reads, batch_size=2, **want):
+        assert len(res) == 2 + n_w + int(moves)
+        sc, preds, w, mw, ps = tr.split_result(res, **want)
+        assert sc is res[0] and preds is res[1]
+        assert (w is res[2]) if n_w >= 1 else w is None
+        assert (mw is res[3]) if n_w == 2 else mw is None
+        assert (ps is res[2 + n_w]) if moves else ps is None
+        assert all(len(x) == len(preds) for x in (w, mw, ps) if x is not None)
+    with pytest.raises(ValueError, match="C and M"):
+        make_tr()[0].split_result(([], []), mods=True)
